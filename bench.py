@@ -50,7 +50,9 @@ ALGO_TB_PER_PATCH = 0.7036       # algorithmic bytes per 3x256x256
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--steps", type=int, default=400,
+                    help="timed reverse steps (cfg3: exactly this many; cfg5: rounded up to whole 50-step samples, the line's "
+                         "`steps` says how many ran)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "fp32"],
                     help="storage dtype; default: bf16 for cfg3 (BASELINE configs[2]), fp16 for cfg5 (configs[4])")
@@ -70,7 +72,13 @@ def parse():
                     help="two-term (hi + lo) convolution weights on the first N resolution levels (accuracy mode, DESIGN section 2); "
                          "the default line is measured with 0 and reports the cost of 2 in `two_term_weights`")
     ap.add_argument("--graph", type=int, default=-1, help="1: replay the reverse step from a captured HIP graph (default: eager launches)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32; "
+                         "cfg3: x_t of the local patches and the recomposed image, cfg5: the finished image; at most 64 MB in all, "
+                         "a fixed seeded sample of each array beyond that).  The inputs depend on the arguments only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.dtype is None:
         a.dtype = "fp16" if a.workload == "cfg5" else "bf16"
     return a
@@ -159,6 +167,28 @@ def launch_ranks(a):
         print(f"---- tail of {errs[bad]} ----\n{_tail(errs[bad])}", file=sys.stderr)
         return 1
     return 0
+
+
+DUMP_LIMIT = 64 * 10**6          # bytes that --dump-outputs may write in all (.npy headers included)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``d/<name>.npy`` in float32.  When they hold more than DUMP_LIMIT
+    bytes, each array is cut to a fixed, seeded sample of its flattened elements (sorted indices, seed 0, a share of the
+    budget proportional to its size): the same arguments give the same sample, so two builds compare output for output."""
+    os.makedirs(d, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(x.nbytes for x in host.values())
+    budget = DUMP_LIMIT - 4096 * len(host)                   # room for the .npy headers
+    for name, x in host.items():
+        note = f"{list(x.shape)}"
+        if total > budget:
+            n = max(1, x.size * budget // total)
+            idx = np.unique(np.random.default_rng(0).integers(0, x.size, n))
+            x = x.reshape(-1)[idx]
+            note = f"sample of {x.size} of {list(host[name].shape)} (seed 0, sorted flat indices)"
+        np.save(os.path.join(d, name + ".npy"), x)
+        print(f"bench.py: wrote {os.path.join(d, name + '.npy')}: {note}", file=sys.stderr)
 
 
 def cpu_model():
@@ -535,7 +565,7 @@ def roofline_leg(gd, jp, tp_value, dtype, H, lo, hi, z, nsteps=5, traffic_tag=No
     return roof
 
 
-def cfg5_run(dtype, steps, rank, world, dev, dist, images=None, want_roofline=True):
+def cfg5_run(dtype, steps, rank, world, dev, dist, images=None, want_roofline=True, dump_dir=None):
     """BASELINE.json configs[4] as stated: 1-channel 512x512, T=1000 strided to S=50 DDIM steps (eta 0), OOD / IND
     branches with a circular OOD mask (radius 64 at the centre), fusion at times[-4], fp16 unless --dtype says
     otherwise.  A "step" is one DDIM step of an image (both branches before the fusion time, one after); `value` =
@@ -596,6 +626,8 @@ def cfg5_run(dtype, steps, rank, world, dev, dist, images=None, want_roofline=Tr
     assert torch.isfinite(out_img).all() and float(out_img.min()) >= 0.0 and float(out_img.max()) <= 2.0
     if rank == 0 and os.environ.get("LD_BENCH_DUMP"):         # tests: the finished image(s) of the last timed sample
         np.save(os.environ["LD_BENCH_DUMP"], (gathered if (world > 1 and not unit_sharded) else out_img).cpu().numpy())
+    if rank == 0 and dump_dir:
+        dump_outputs(dump_dir, {"image": gathered if (world > 1 and not unit_sharded) else out_img})
     roof = None
     if rank == 0 and want_roofline and not unit_sharded:
         # per-launch table of the branch phase (47 of the 50 pairs): branch 0 timed launch by launch while branch 1's
@@ -638,7 +670,7 @@ def cfg5_run(dtype, steps, rank, world, dev, dist, images=None, want_roofline=Tr
 
 
 def bench_cfg5(a, rank, world, dev, dist):
-    out = cfg5_run(a.dtype, a.steps, rank, world, dev, dist, images=a.images, want_roofline=not a.no_roofline)
+    out = cfg5_run(a.dtype, a.steps, rank, world, dev, dist, images=a.images, want_roofline=not a.no_roofline, dump_dir=a.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
@@ -733,8 +765,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def measure(steps, warmup, Pn=P):
-        """W untimed + K timed reverse steps of ``Pn`` local patches in the model's current storage dtype -> (seconds, plan, z)."""
+    def measure(steps, warmup, Pn=P, keep=None):
+        """W untimed + K timed reverse steps of ``Pn`` local patches in the model's current storage dtype -> (seconds, plan, z).
+        ``keep`` (a dict): receives host copies of what the timed path handed back, taken after the timer stopped."""
         masks, conds = workload(Pn)
         jp = net.plan(Pn, H, H, table_T=T_STEPS)
         jp.cond_in.copy_(conds)
@@ -802,9 +835,14 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
         assert torch.isfinite(img).all(), "non-finite output"
+        if keep is not None:             # x_t after the last timed step (every rank's patches when N > 1) + the recomposed image
+            keep.update(x_t=(gathered if world > 1 else jp.x_in).float().cpu(), image=img.float().cpu())
         return elapsed, jp, z
 
-    elapsed, jp, z = measure(a.steps, a.warmup)
+    kept = {} if a.dump_outputs else None
+    elapsed, jp, z = measure(a.steps, a.warmup, keep=kept)
+    if rank == 0 and kept:
+        dump_outputs(a.dump_outputs, kept)
     for _rep in range(int(os.environ.get("LD_BENCH_REPEAT", "1")) - 1):     # diagnosis only: the line reports the FIRST measurement
         e_again, _, _ = measure(a.steps, a.warmup)
         print(f"measurement {_rep + 2}: {1e3 * e_again / a.steps:.4f} ms per step (first: {1e3 * elapsed / a.steps:.4f})", file=sys.stderr)

@@ -132,3 +132,54 @@ def test_default_line_carries_every_baseline_config():
     # a second sampler object must not serialise its sub-batches behind the first one's streams (round 6): cfg5 alone reads ~15
     assert c5["value"] > 11.0, c5
     assert j["other_dtype"]["dtype"] == "fp16" and "dtype_end_to_end" in j
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 .npy files, at most 64 MB in all: beyond that, every array is cut to the same seeded
+    sample of its elements (sorted flat indices), so two runs with the same arguments write comparable files."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = {"x_t": torch.arange(24, dtype=torch.float32).reshape(2, 3, 4), "image": torch.ones(1, 3, 2, 2, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 40000)
+    big = {"x_t": torch.randn(10000), "image": torch.randn(2500)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = [tmp_path / d / f"{k}.npy" for d in ("a", "b") for k in big]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 40000
+    for k in big:
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == np.float32 and 0 < a.size < big[k].numel() and np.array_equal(a, b)
+        assert np.isin(a, big[k].numpy()).all()
+
+
+def test_steps_below_one_is_refused():
+    r = _run(["--steps", "0", "--warmup", "0"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_with_the_same_arguments_agree(tmp_path):
+    """`--dump-outputs DIR`: the timed path's outputs after its last step (x_t of the 8 local patches + the recomposed image),
+    float32; the same arguments give the same inputs, so two runs agree up to the summation order of the kernels' atomics."""
+    import json
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-roofline", "--no-other-dtype"]
+    out = {}
+    for d in ("a", "b"):
+        r = _run(args + ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == 5
+        out[d] = {k: np.load(tmp_path / d / f"{k}.npy") for k in ("x_t", "image")}
+    assert out["a"]["x_t"].shape == (8, 3, 256, 256) and out["a"]["image"].shape == (1, 3, 256, 256)
+    for k in ("x_t", "image"):
+        a, b = out["a"][k], out["b"][k]
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        d = float(np.abs(a - b).max())
+        print(f"--dump-outputs {k}: run-to-run max-abs {d:.3e}")
+        assert d < 1e-3, (k, d)
