@@ -480,6 +480,46 @@ int ld_p_losses(const float* model_out, const float* x_start, const float* noise
 int ld_recompose(const float* patches /*[B,K,C,HW]*/, const float* masks /*[K,HW]*/, float* out,
                  int B, int K, int C, int HW, void* stream);
 
+/* ---- segmentation U-Net: the OOD-mask producer in front of sample() --------------------------------------------------
+ * UNet(n_channels, 1, bilinear=False) of unet_model.py:140-243, which test.py:214-221, 284-289 runs on the shifted
+ * conditioning image (mask = sigmoid(logits) > 0.5).  Every DoubleConv convolution (conv3x3, no bias) carries BatchNorm2d
+ * (eval) + ReLU as an fp32 epilogue on the fp32 accumulator: out = relu(acc * scale[c] + shift[c]), scale = gamma /
+ * sqrt(running_var + eps), shift = beta - running_mean * scale (host-made; the weights are not scaled).  Activations are
+ * NHWC in the storage dtype, weights fp32.  The diffusion path's kernels above are not involved. */
+#define LD_SEG_SRC_PLAIN 0    /* src0 [B, H, W, C0]                                                                  */
+#define LD_SEG_SRC_POOL 1     /* src0 [B, 2H, 2W, C0] read through a 2x2 max-pool (Down, unet_model.py:170-180)       */
+#define LD_SEG_SRC_CAT_D2S 2  /* cat([src0 [B, H, W, C0], depth_to_space(src1 [B, H/2, W/2, 4*C1])]) (Up, :197-206):  */
+                              /* channel c of pixel (y, x) of the second part is element ((y&1)*2 + (x&1))*C1 + c of    */
+                              /* low-res pixel (y>>1, x>>1) -- the layout ld_seg_conv(ksize 1) writes for a ConvTranspose2d */
+typedef struct ld_seg_conv_args {
+  const void* src0;        /* see LD_SEG_SRC_* */
+  const void* src1;        /* LD_SEG_SRC_CAT_D2S only */
+  int32_t C0, C1;          /* channels of src0 / of the depth-to-space part (multiples of 32; C1 = 0 unless CAT_D2S) */
+  int32_t mode;            /* LD_SEG_SRC_* */
+  int32_t ksize;           /* 3 (pad 1), or 1 with a plain source: ConvTranspose2d(2, 2) as a GEMM to 4*Cout channels */
+  const float* weight;     /* fp32 [ksize*ksize][C0 + C1][Cout] from ld_seg_pack_weight / ld_seg_pack_convt */
+  const float* scale;      /* [Cout] or NULL (= 1) */
+  const float* shift;      /* [Cout] or NULL (= 0): BN shift, or the repeated ConvTranspose2d bias */
+  int32_t relu;            /* 1: ReLU after the affine */
+  void* out;               /* NHWC [B, H, W, Cout], storage dtype */
+  int32_t B, H, W, Cout;   /* output size; Cout a multiple of 64; H, W even with LD_SEG_SRC_CAT_D2S */
+  int32_t dtype;
+} ld_seg_conv_args;
+int ld_seg_conv(const ld_seg_conv_args* args, void* stream);
+/* inc's first convolution (unet_model.py:224): NCHW fp32 image [B, Cin (1 or 3), H, W], OIHW fp32 weight [64, Cin, 3, 3]
+ * -> NHWC [B, H, W, 64] storage dtype, the same BN + ReLU epilogue (scale / shift [64]). */
+int ld_seg_conv_image(const float* x_nchw, const float* w_oihw, const float* scale, const float* shift, void* out,
+                      int B, int Cin, int H, int W, int dtype, void* stream);
+/* outc (unet_model.py:209-215, n_classes = 1): NHWC [B, H, W, C] -> logits [B, 1, H, W] fp32 = x . w[C] + bias[0];
+ * optionally prob = 1 / (1 + exp(-logit)) (nn.Sigmoid) and mask = (prob > 0.5) as 0 / 1 (test.py:286-288), both
+ * [B, 1, H, W] fp32.  Any of the three outputs may be NULL (not all). */
+int ld_seg_head(const void* x, const float* w, const float* bias, float* logits, float* prob, float* mask,
+                int B, int H, int W, int C, int dtype, void* stream);
+/* Weight repacks (fp32, once per model): OIHW [Cout, Cin, k, k] -> [k*k][Cin][Cout]; ConvTranspose2d [Cin, Cout, 2, 2]
+ * -> [Cin][(p1, p2, c)] with the bias [Cout] repeated 4x into bias_out [4*Cout] (bias may be NULL: zeros). */
+int ld_seg_pack_weight(const float* w_oihw, float* out, int cout, int cin, int ksize, void* stream);
+int ld_seg_pack_convt(const float* w, const float* bias, float* w_out, float* bias_out, int cin, int cout, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

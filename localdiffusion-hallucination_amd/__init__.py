@@ -30,7 +30,8 @@ from . import rng, schedule, tuning, weights  # noqa: F401,E402
 from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
-__all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "configure_runtime"]
+__all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
+           "configure_runtime"]
 
 
 def __getattr__(name):
@@ -40,4 +41,7 @@ def __getattr__(name):
     if name == "GaussianDiffusion":
         from .diffusion import GaussianDiffusion
         return GaussianDiffusion
+    if name == "SegUNet":
+        from .segnet import SegUNet
+        return SegUNet
     raise AttributeError(name)

@@ -20,6 +20,7 @@ OBJ = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}
 SCHED_COLS = 8
 STAT_STRIPES = 16      # LD_STAT_STRIPES
 COUNTER_CONV3X3_C32, COUNTER_CONV3X3_GENERIC, COUNTER_CONV3X3_S32 = 0, 1, 2
+SEG_SRC_PLAIN, SEG_SRC_POOL, SEG_SRC_CAT_D2S = 0, 1, 2
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -52,6 +53,12 @@ class GnApplyArgs(C.Structure):
 class StepBeginArgs(C.Structure):
     _fields_ = [("zero_a", vp), ("bytes_a", C.c_size_t), ("zero_b", vp), ("bytes_b", C.c_size_t), ("t_ptr", vp), ("delta", i32),
                 ("idx_ptr", vp), ("t_table", vp), ("film_rows", vp), ("row_floats", i32), ("film_cur", vp)]
+
+
+class SegConvArgs(C.Structure):
+    _fields_ = [("src0", vp), ("src1", vp), ("C0", i32), ("C1", i32), ("mode", i32), ("ksize", i32), ("weight", vp),
+                ("scale", vp), ("shift", vp), ("relu", i32), ("out", vp), ("B", i32), ("H", i32), ("W", i32),
+                ("Cout", i32), ("dtype", i32)]
 
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
@@ -134,6 +141,11 @@ _SIGS = {
     "ld_q_sample_t": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, i64, vp]),
     "ld_p_losses": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, vp]),
     "ld_recompose": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_conv": (C.c_int, [C.POINTER(SegConvArgs), vp]),
+    "ld_seg_conv_image": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_head": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_pack_weight": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_pack_convt": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -91,3 +91,24 @@ def save_reference_checkpoint(diffusion, path, step=0):
                                           "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
                                           "differentiable": False, "fused": None, "params": list(range(n_params))}]}
     torch.save({"step": int(step), "model": sd, "opt": opt, "ema": ema, "scaler": None}, path)
+
+
+def load_seg_checkpoint(path_or_dict, seg, trust_pickle=False):
+    """Load the segmentation U-Net's weights into ``seg`` (a ``SegUNet``): a bare ``state_dict`` as ``train_seg.py`` saves
+    it and ``test.py:219`` reads it (``seg_model.load_state_dict(torch.load(path))``), BatchNorm running statistics and
+    ``num_batches_tracked`` included.  Same restricted unpickler as ``load_reference_checkpoint``; names and shapes must
+    match exactly (RuntimeError otherwise).  Returns {'n_tensors'}."""
+    data = _read(path_or_dict, trust_pickle)
+    if not isinstance(data, dict):
+        raise RuntimeError(f"segmentation checkpoint: expected a state_dict, got {type(data).__name__}")
+    sd = {k[7:] if k.startswith("module.") else k: v for k, v in data.items()}     # (an nn.DataParallel wrapper's prefix)
+    own = seg.state_dict()
+    bad = [k for k in sd if k in own and tuple(sd[k].shape) != tuple(own[k].shape)]
+    if bad:
+        raise RuntimeError(f"checkpoint tensors with the wrong shape: {bad[:5]}")
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    if missing or unexpected:
+        raise RuntimeError(f"checkpoint does not match the model: missing {missing[:5]} unexpected {unexpected[:5]}")
+    seg.load_state_dict({k: v.to(own[k].dtype) for k, v in sd.items()})
+    return {"n_tensors": len(sd)}

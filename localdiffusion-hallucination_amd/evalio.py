@@ -72,6 +72,25 @@ def anomaly_map_to_mask(anomaly_map, threshold):
     return m ** 2, binary
 
 
+def seg_preprocess(lr, mean_t1, std_t1, translate_zero=True):
+    """The segmentation net's input (test.py:213-216): lr - |(0 - mean_t1) / std_t1|.  The reference defines that
+    constant (``mini``) only under ``translate_zero``; without it test.py:216 raises NameError, and so does this."""
+    if not translate_zero:
+        raise NameError("name 'mini' is not defined: the reference's segmentation path (test.py:214-216) uses the "
+                        "translate_zero shift, which is only defined with translate_zero=True")
+    mini = (0 - mean_t1) / std_t1
+    return lr - abs(float(torch.tensor(mini)))
+
+
+def seg_ood_mask(seg, lr, mean_t1, std_t1, translate_zero=True):
+    """The reference's segmentation OOD mask (test.py:203-221, 284-289): ``seg`` (a ``SegUNet``) on lr - |mini|, then
+    sigmoid(logits) > 0.5.  Returns (mask_pred, binary_mask), both [B, 1, H, W] fp32 on ``lr``'s device, with
+    mask_pred = binary_mask as test.py:289 sets it."""
+    lr_ad = seg_preprocess(lr.float(), mean_t1, std_t1, translate_zero)
+    _, binary = seg.predict_mask(lr_ad)
+    return binary, binary
+
+
 def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda", batch_size=1):
     """test.py's loop: sample every LR image, compare with HR.  Returns a dict of metrics."""
     preds, losses, times = [], [], []

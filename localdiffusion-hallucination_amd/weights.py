@@ -221,3 +221,74 @@ def procedural_state_dict(cfg: UnetConfig, seed=0, final_gain=3.0):
 
 def num_params(cfg: UnetConfig):
     return sum(int(np.prod(s)) for s in unet_param_shapes(cfg).values())
+
+
+# ----------------------------------------------------------------------------- segmentation U-Net (mask producer)
+SEG_WIDTHS = (64, 128, 256, 512, 1024)      # inc, down1..down4 of unet_model.py:222-229 (bilinear=False)
+_BN_BUFFERS = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+
+
+def _double_conv_shapes(sh, p, cin, cout):
+    sh[p + "double_conv.0.weight"] = (cout, cin, 3, 3)
+    for k in _BN_BUFFERS:
+        sh[p + "double_conv.1." + k] = () if k == "num_batches_tracked" else (cout,)
+    sh[p + "double_conv.3.weight"] = (cout, cout, 3, 3)
+    for k in _BN_BUFFERS:
+        sh[p + "double_conv.4." + k] = () if k == "num_batches_tracked" else (cout,)
+
+
+def seg_param_shapes(n_channels=1, n_classes=1) -> "OrderedDict[str, tuple]":
+    """name -> shape of ``unet_model.UNet(n_channels, n_classes, bilinear=False).state_dict()`` in its order (118 entries
+    for one class): DoubleConv = conv3x3 (no bias) + BatchNorm2d, twice; Up = ConvTranspose2d(2, 2) + DoubleConv."""
+    w = SEG_WIDTHS
+    sh = OrderedDict()
+    _double_conv_shapes(sh, "inc.", n_channels, w[0])
+    for i in range(1, 5):
+        _double_conv_shapes(sh, f"down{i}.maxpool_conv.1.", w[i - 1], w[i])
+    for i in range(1, 5):
+        cin = w[5 - i]
+        sh[f"up{i}.up.weight"] = (cin, cin // 2, 2, 2)
+        sh[f"up{i}.up.bias"] = (cin // 2,)
+        _double_conv_shapes(sh, f"up{i}.conv.", cin, cin // 2)
+    sh["outc.conv.weight"] = (n_classes, w[0], 1, 1)
+    sh["outc.conv.bias"] = (n_classes,)
+    return sh
+
+
+def procedural_seg_state_dict(seed=0, bn_stats=None, n_channels=1, n_classes=1):
+    """Name-keyed procedural weights of the segmentation U-Net (numpy, the reference's names and dtypes):
+    convolutions uniform(+-1/sqrt(fan_in)) (a ConvTranspose2d(2, 2) output sees Cin inputs: bound 1/sqrt(Cin), its bias
+    too), BatchNorm gamma = 1 + 0.1 u, beta = 0.1 u.  The running statistics are NOT invented: ``bn_stats`` maps
+    ``<bn>.running_mean`` / ``.running_var`` / ``.num_batches_tracked`` -- and any other name it holds, such as the
+    head bias G18 places in a gap of its logits -- to the values a calibration produced (tests/golden/g18_segunet.npz);
+    without it they are the fresh-module values 0 / 1 / 0."""
+    shapes = seg_param_shapes(n_channels, n_classes)
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        if bn_stats is not None and name in bn_stats:
+            t = np.asarray(bn_stats[name])
+            if name.endswith("num_batches_tracked"):
+                out[name] = np.asarray(t, dtype=np.int64).reshape(())
+            else:
+                out[name] = np.ascontiguousarray(t, dtype=np.float32).reshape(shape)
+            continue
+        if name.endswith("num_batches_tracked"):
+            out[name] = np.asarray(0, dtype=np.int64)
+            continue
+        if name.endswith("running_mean"):
+            out[name] = np.zeros(shape, np.float32)
+            continue
+        if name.endswith("running_var"):
+            out[name] = np.ones(shape, np.float32)
+            continue
+        u = procedural_tensor("seg." + name, shape, seed)
+        if ".double_conv.1." in name or ".double_conv.4." in name:
+            t = (1.0 + 0.1 * u) if name.endswith(".weight") else 0.1 * u
+        elif ".up." in name:
+            cin = shapes[name[:-len(".bias")] + ".weight"][0] if name.endswith(".bias") else shape[0]
+            t = u / np.sqrt(cin)
+        else:
+            wshape = shapes[name[:-len(".bias")] + ".weight"] if name.endswith(".bias") else shape
+            t = u / np.sqrt(_fan_in(wshape))
+        out[name] = np.ascontiguousarray(t, dtype=np.float32)
+    return out

@@ -936,6 +936,102 @@ def g17(ddpm):
     save("g17_unet_options", **out)
 
 
+# config.yaml:55-56: the MRI intensity normalisation that test.py:213-216 undoes in front of the segmentation net
+MEAN_T1, STD_T1 = 610.7180906353575, 1018.7631901605115
+SEG_SEED = 18
+
+
+def mri_like_slices(B, H, seed):
+    """Synthetic MRI-like LR slices in the translated units test.py feeds the net (background 0): an elliptical head with a
+    smooth low-frequency texture and one bright blob (the 'lesion').  [B, 1, H, H] float32."""
+    yy, xx = np.mgrid[0:H, 0:H].astype(np.float64) / H
+    out = np.zeros((B, 1, H, H), np.float32)
+    for b in range(B):
+        u = rng.uniform((12,), seed, 1800 + b, 0.0, 1.0).astype(np.float64)
+        cy, cx = 0.5 + 0.08 * (u[0] - 0.5), 0.5 + 0.08 * (u[1] - 0.5)
+        r = np.sqrt(((yy - cy) / (0.36 + 0.04 * u[2])) ** 2 + ((xx - cx) / (0.30 + 0.04 * u[3])) ** 2)
+        head = 1.0 / (1.0 + np.exp((r - 1.0) * 25.0))
+        tex = 0.9 + 0.15 * np.sin(2 * np.pi * (2 + 2 * u[4]) * yy + 6.28 * u[5]) * np.cos(2 * np.pi * (1 + 2 * u[6]) * xx + 6.28 * u[7])
+        by, bx = cy + 0.35 * (u[8] - 0.5), cx + 0.3 * (u[9] - 0.5)
+        rb = np.sqrt((yy - by) ** 2 + (xx - bx) ** 2) / (0.06 + 0.05 * u[10])
+        blob = (2.0 + u[11]) / (1.0 + np.exp((rb - 1.0) * 8.0))
+        out[b, 0] = (head * tex + head * blob).astype(np.float32)
+    return out
+
+
+def g18(ddpm):
+    """The reference's segmentation U-Net (unet_model.py:140-243, UNet() as test.py:218 builds it) with the procedural
+    weights of weights.procedural_seg_state_dict and BatchNorm running statistics calibrated the way train_seg.py would
+    leave them (train mode, cumulative averages over procedural batches, no optimiser); then the reference's own forward
+    on four inputs.  The 128^2 slice is chosen so that no logit sits within 1e-3 of the largest one of zero (its mask is
+    unambiguous), and it holds both classes."""
+    print("G18 segmentation U-Net (OOD-mask producer)")
+    import unet_model
+    ref = unet_model.UNet()
+    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in weights.procedural_seg_state_dict(SEG_SEED).items()}
+    ref_sd = ref.state_dict()
+    assert list(ref_sd.keys()) == list(sd.keys()), set(ref_sd) ^ set(sd)
+    for k in ref_sd:
+        assert tuple(ref_sd[k].shape) == tuple(sd[k].shape) and ref_sd[k].dtype == sd[k].dtype, k
+    ref.load_state_dict(sd)
+    for m in ref.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.momentum = None                     # cumulative moving average
+    ref.train()
+    mini = abs((0 - MEAN_T1) / STD_T1)
+    with torch.no_grad():
+        for k in range(4):
+            xb = torch.from_numpy(mri_like_slices(4, 64, 180 + k)) - mini
+            xb = xb + 0.05 * torch.from_numpy(rng.randn(tuple(xb.shape), SEG_SEED, 1900 + k))
+            ref(xb)
+    ref.eval()
+    # The head bias is calibrated too: moved (by at most 0.25) into the widest gap of the 128^2 slice's logits around zero,
+    # so that the slice's mask is unambiguous -- no logit within 1e-4 of the largest one of the 0.5-probability threshold
+    # (the logits of a random-weight net are spatially rough: without this, some of 16384 pixels always sit at ~1e-5).
+    mini_t = torch.abs(torch.tensor((0 - MEAN_T1) / STD_T1))                    # test.py:215
+    b0 = float(ref.outc.conv.bias[0])
+    best = None
+    with torch.no_grad():
+        for c in range(16):                                                       # first slice with a wide enough gap
+            lr = torch.from_numpy(mri_like_slices(1, 128, 128000 + c))
+            feat = (ref(lr - mini_t) - b0).numpy().ravel().astype(np.float64)
+            cand = np.sort(-feat[(-feat > b0 - 0.25) & (-feat < b0 + 0.25)])
+            i = int(np.argmax(np.diff(cand)))
+            bias, half = float(np.float32((cand[i] + cand[i + 1]) / 2)), (cand[i + 1] - cand[i]) / 2
+            best = (lr, bias)
+            if half > 2e-4 * np.abs(feat + bias).max():
+                break
+        lr128, bias = best
+        ref.outc.conv.bias.fill_(bias)
+    out = {"mean_t1": np.float64(MEAN_T1), "std_t1": np.float64(STD_T1), "seed": np.int64(SEG_SEED)}
+    for k, v in ref.state_dict().items():
+        if "running_" in k or k.endswith("num_batches_tracked") or k == "outc.conv.bias":
+            out[k] = v.numpy().copy()
+    with torch.no_grad():
+        x32 = torch.from_numpy(mri_like_slices(2, 32, 32)) - mini
+        x64 = torch.from_numpy(mri_like_slices(1, 64, 64)) - mini
+        out["x32"], out["logits32"] = x32.numpy(), ref(x32).numpy()
+        out["x64"], out["logits64"] = x64.numpy(), ref(x64).numpy()
+        for H in (128, 256):
+            lr = lr128 if H == 128 else torch.from_numpy(mri_like_slices(1, H, 1000 * H))
+            lr_ad = lr - mini_t                                                   # test.py:216
+            logits = ref(lr_ad)
+            mask = (torch.sigmoid(logits) > 0.5).float()                          # test.py:287-288
+            frac = float(mask.mean())
+            lmin, lmax = float(logits.abs().min()), float(logits.abs().max())
+            print(f"  {H}^2: logits in [{float(logits.min()):.3f}, {float(logits.max()):.3f}], min |logit| {lmin:.2e}, "
+                  f"mask fraction {frac:.3f}")
+            if H == 128:
+                assert 0.02 < frac < 0.98 and lmin > 1e-4 * lmax, (frac, lmin, lmax)
+            out[f"lr{H}"], out[f"logits{H}"], out[f"mask{H}"] = lr.numpy(), logits.numpy(), mask.numpy()
+    for H, key in ((32, "logits32"), (64, "logits64")):
+        print(f"  {H}^2 logits in [{out[key].min():.3f}, {out[key].max():.3f}]")
+    save("g18_segunet", **out)
+    with open(os.path.join(GOLD, "g18_segunet_inventory.txt"), "w") as f:
+        for k, v in ref.state_dict().items():
+            f.write(f"{k} {list(v.shape)} {str(v.dtype).replace('torch.', '')}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -945,7 +1041,7 @@ def main():
     ddpm = import_reference()
     os.makedirs(GOLD, exist_ok=True)
     todo = [("G0", g0_inventory), ("G1", g1), ("G2", g2), ("G3", g3), ("G4", g4), ("G6", g6),
-            ("G7", g7), ("G8", g8), ("G9", g9), ("G10", g10), ("G12", g12), ("G14", g14), ("G15", g15), ("G17", g17), ("G5", g5), ("G11", g11), ("G13", g13), ("G16", g16)]
+            ("G7", g7), ("G8", g8), ("G9", g9), ("G10", g10), ("G12", g12), ("G14", g14), ("G15", g15), ("G17", g17), ("G18", g18), ("G5", g5), ("G11", g11), ("G13", g13), ("G16", g16)]
     only = set(filter(None, a.only.split(",")))
     for name, fn in todo:
         if only and name not in only:
