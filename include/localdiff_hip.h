@@ -520,6 +520,63 @@ int ld_seg_head(const void* x, const float* w, const float* bias, float* logits,
 int ld_seg_pack_weight(const float* w_oihw, float* out, int cout, int cin, int ksize, void* stream);
 int ld_seg_pack_convt(const float* w, const float* bias, float* w_out, float* bias_out, int cin, int cout, void* stream);
 
+/* ---- PatchCore: the default OOD anomaly-map producer in front of sample() ----------------------------------------------
+ * PatchcoreModel (models.py:42-254, eval) with the wide_resnet50_2 trunk up to layer3: features after layer2 / layer3,
+ * AvgPool2d(3, 1, 1), bilinear resample of layer3 onto the layer2 grid, concat -> [N, 1536] rows, nearest neighbour in
+ * the memory bank, the image score of models.py:222-254 and anomalib's AnomalyMapGenerator (nearest upsample + 33x33
+ * Gaussian blur, sigma 4, reflect padding).  Everything is fp32 in storage and arithmetic; activations are NHWC.
+ * Convolutions carry BatchNorm (eval) as out = relu?(acc * scale[c] + shift[c] (+ residual)), the affine host-made from
+ * the running statistics (the weights are not scaled).  The GEMMs run on v_mfma_f32_32x32x2_f32 (exact f32). */
+typedef struct ld_pc_conv_args {
+  const float* src;        /* NHWC [B, Hi, Wi, Cin], Cin a multiple of 32 */
+  const float* weight;     /* fp32 [Cout][ksize][ksize][Cin] (OIHW permuted to OHWI) */
+  const float* scale;      /* [Cout] */
+  const float* shift;      /* [Cout] */
+  const float* residual;   /* NHWC [B, Ho, Wo, Cout] added after the affine, before the ReLU; or NULL */
+  float* out;              /* NHWC [B, Ho, Wo, Cout], Cout a multiple of 64 */
+  int32_t B, Hi, Wi, Cin, Ho, Wo, Cout;
+  int32_t ksize;           /* 1 (pad 0) or 3 (pad 1); Ho = (Hi + 2 pad - ksize) / stride + 1, likewise Wo */
+  int32_t stride;          /* 1 or 2 */
+  int32_t relu;
+} ld_pc_conv_args;
+int ld_pc_conv(const ld_pc_conv_args* args, void* stream);
+/* The stem: conv1 7x7 s2 p3 (3 -> 64) from the NCHW fp32 image, bn1 + ReLU -> NHWC [B, Ho, Wo, 64] with
+ * Ho = (H - 1) / 2 + 1; w is the OIHW weight [64, 3, 7, 7]. */
+int ld_pc_stem(const float* x_nchw, const float* w_oihw, const float* scale, const float* shift, float* out,
+               int B, int H, int W, void* stream);
+/* MaxPool2d(3, 2, 1): NHWC [B, H, W, C] -> [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C], C a multiple of 4. */
+int ld_pc_maxpool(const float* x, float* out, int B, int H, int W, int C, void* stream);
+/* The embedding (models.py:98-102, 129-145, 147-162): AvgPool2d(3, 1, 1) (count_include_pad: / 9) of layer2 [B, h2, w2,
+ * C2] and of layer3 [B, h3, w3, C3], bilinear (align_corners=False) resample of the pooled layer3 to h2 x w2, concat ->
+ * rows [B*h2*w2, C2 + C3] in (b, y, x) order, and each row's |x|^2 into norms [B*h2*w2].  C2, C3 multiples of 4. */
+int ld_pc_embed(const float* l2, const float* l3, float* rows, float* norms, int B, int h2, int w2, int C2, int h3,
+                int w3, int C3, void* stream);
+/* |x|^2 of each of the n rows of x [n, d] (the memory bank's norms, once per bank). */
+int ld_pc_row_norms(const float* x, float* norms, int64_t n, int d, void* stream);
+/* Nearest bank row of every query (models.py:179-217, n_neighbors = 1): d2 = (|q|^2 - 2 q.m) + |m|^2, clamped at 0, its
+ * min and first argmin over the M rows of bank [M, D] without materialising the N x M matrix.  Query tiles of 128 rows,
+ * the bank split over workgroups, merged with a 64-bit atomicMin on (d2 bits << 32 | index).  work: [N] uint64 scratch.
+ * dist [N] = sqrt(min d2), idx [N] int32.  D a multiple of 32, M < 2^31. */
+int ld_pc_knn(const float* q, const float* qn, int N, const float* bank, const float* bn, int64_t M, int D,
+              unsigned long long* work, float* dist, int32_t* idx, void* stream);
+/* The k nearest bank rows of each query (k <= 16, topk(largest=False): ascending, the lower index first on equal
+ * distances): d2 [N, M] fp32 scratch, dist [N, k] = sqrt(d2), idx [N, k] int32.  k <= M. */
+int ld_pc_knn_topk(const float* q, const float* qn, int N, const float* bank, const float* bn, int64_t M, int D, int k,
+                   float* d2, float* dist, int32_t* idx, void* stream);
+/* Image score, part 1 (models.py:241-246): per image the first argmax p* of its P patch scores, and bank row m* = loc[p*]
+ * copied to q [B, D] with its norm to qn [B] (the query of the support search).  argmax [B] int32. */
+int ld_pc_score_prepare(const float* patch_scores, const int32_t* loc, const float* bank, const float* bn, int B, int P,
+                        int D, float* q, float* qn, int32_t* argmax, void* stream);
+/* Part 2 (:247-254): distances from row p* of rows [B*P, D] (norms row_norms) to the k support rows support [B, k] of
+ * the bank, pred_score[b] = (1 - softmax(d)[0]) * s*.  k = 0: pred_score = max patch score (num_neighbors == 1). */
+int ld_pc_score(const float* rows, const float* row_norms, const float* patch_scores, const int32_t* argmax,
+                const float* bank, const float* bn, const int32_t* support, int B, int P, int D, int k, float* pred_score,
+                void* stream);
+/* AnomalyMapGenerator: nearest upsample of the patch scores [B, h, w] to [B, H, W], then the ks-tap Gaussian g (ks odd,
+ * reflect padding ks / 2 < min(H, W)) along x into tmp and along y into out, both [B, H, W] fp32. */
+int ld_pc_anomaly_map(const float* scores, const float* g, int ks, float* tmp, float* out, int B, int h, int w, int H,
+                      int W, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

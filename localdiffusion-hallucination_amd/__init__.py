@@ -31,7 +31,7 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "configure_runtime"]
+           "PatchCore", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -44,4 +44,7 @@ def __getattr__(name):
     if name == "SegUNet":
         from .segnet import SegUNet
         return SegUNet
+    if name == "PatchCore":
+        from .patchcore import PatchCore
+        return PatchCore
     raise AttributeError(name)

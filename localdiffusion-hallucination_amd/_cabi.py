@@ -61,6 +61,12 @@ class SegConvArgs(C.Structure):
                 ("Cout", i32), ("dtype", i32)]
 
 
+class PcConvArgs(C.Structure):
+    _fields_ = [("src", vp), ("weight", vp), ("scale", vp), ("shift", vp), ("residual", vp), ("out", vp), ("B", i32),
+                ("Hi", i32), ("Wi", i32), ("Cin", i32), ("Ho", i32), ("Wo", i32), ("Cout", i32), ("ksize", i32),
+                ("stride", i32), ("relu", i32)]
+
+
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
 _SIGS = {
     "ld_last_error": (C.c_char_p, []),
@@ -146,6 +152,16 @@ _SIGS = {
     "ld_seg_head": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_seg_pack_weight": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ld_seg_pack_convt": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "ld_pc_conv": (C.c_int, [C.POINTER(PcConvArgs), vp]),
+    "ld_pc_stem": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_pc_maxpool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_pc_embed": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_pc_row_norms": (C.c_int, [vp, vp, i64, C.c_int, vp]),
+    "ld_pc_knn": (C.c_int, [vp, vp, C.c_int, vp, vp, i64, C.c_int, vp, vp, vp, vp]),
+    "ld_pc_knn_topk": (C.c_int, [vp, vp, C.c_int, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ld_pc_score_prepare": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ld_pc_score": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "ld_pc_anomaly_map": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -112,3 +112,49 @@ def load_seg_checkpoint(path_or_dict, seg, trust_pickle=False):
         raise RuntimeError(f"checkpoint does not match the model: missing {missing[:5]} unexpected {unexpected[:5]}")
     seg.load_state_dict({k: v.to(own[k].dtype) for k, v in sd.items()})
     return {"n_tensors": len(sd)}
+
+
+_PC_PREFIXES = ("feature_extractor.feature_extractor.", "feature_extractor.", "module.")
+
+
+def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
+    """Load a ``PatchCore``: the ``wide_resnet50_2`` weights and the memory bank (test.py:157-175).
+
+    ``backbone_sd`` is a state_dict (or a file holding one) of torchvision's / timm's ``wide_resnet50_2``, bare or under
+    anomalib's ``feature_extractor.`` / ``feature_extractor.feature_extractor.`` prefixes; ``layer4.*`` and ``fc.*`` are
+    dropped (layers 2 and 3 do not use them), and so is a ``memory_bank`` entry when ``memory_bank_npy`` is given.
+    ``memory_bank_npy`` is a ``.npy`` path (``np.load``ed as test.py:169-175 does) or an array [M, 1536], or None to take
+    the state_dict's ``memory_bank``.  Names and shapes of the trunk must match exactly (RuntimeError otherwise).
+    Returns {'n_tensors', 'bank_rows'}."""
+    import numpy as np
+    data = _read(backbone_sd, trust_pickle)
+    if not isinstance(data, dict):
+        raise RuntimeError(f"PatchCore backbone: expected a state_dict, got {type(data).__name__}")
+    sd, bank = {}, None
+    for k, v in data.items():
+        for p in _PC_PREFIXES:
+            if k.startswith(p):
+                k = k[len(p):]
+                break
+        if k == "memory_bank":
+            bank = v
+        elif not k.startswith(("layer4.", "fc.")):
+            sd[k] = v
+    own = model.feature_extractor.state_dict()
+    bad = [k for k in sd if k in own and tuple(sd[k].shape) != tuple(own[k].shape)]
+    if bad:
+        raise RuntimeError(f"PatchCore backbone tensors with the wrong shape: {bad[:5]}")
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    if missing or unexpected:
+        raise RuntimeError(f"PatchCore backbone does not match wide_resnet50_2: missing {missing[:5]} "
+                           f"unexpected {unexpected[:5]}")
+    model.feature_extractor.load_state_dict({k: torch.as_tensor(v).to(own[k].dtype) for k, v in sd.items()})
+    model.invalidate()
+    if memory_bank_npy is not None:
+        bank = np.load(memory_bank_npy) if isinstance(memory_bank_npy, (str, bytes)) or hasattr(memory_bank_npy, "__fspath__") \
+            else memory_bank_npy
+    if bank is None:
+        raise RuntimeError("PatchCore: no memory bank (pass memory_bank_npy, or a state_dict with 'memory_bank')")
+    model.set_memory_bank(bank)
+    return {"n_tensors": len(sd), "bank_rows": int(model.memory_bank.shape[0])}

@@ -91,6 +91,109 @@ def seg_ood_mask(seg, lr, mean_t1, std_t1, translate_zero=True):
     return binary, binary
 
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+PATCHCORE_RULES = {"8to3": "mnist", "8to5": "mnist", "t12flair": "mri", "flair2t1": "mri", "transistor": "mvtec",
+                   "toothbrush": "mvtec", "grid": "mvtec"}
+
+
+def patchcore_preprocess(lr, data, mean_t1=None, std_t1=None, translate_zero=True):
+    """PatchCore's input from the conditioning image lr [B, C, H, W] (test.py:200-238, 243): three channels, then
+    * mri: the translate_zero shift undone (lr - |mini|), channel 0 de-normalised (* std_t1 + mean_t1), / 4096, repeated
+      to three channels -- as test.py writes it, [B, H, W].repeat(1, 3, 1, 1) is [1, 3B, H, W];
+    * mnist / mvtec*: / 2 when max > 1, bilinear resize (align_corners=False) to 84 (mnist) or 224 (mvtec);
+    and the ImageNet ``Normalize``.  ``data`` is the config's ``data`` ('mnist', 'mri' or a name containing 'mvtec')."""
+    lr_ad = lr.repeat(1, 3, 1, 1) if lr.shape[1] != 3 else lr.clone()
+    if data == "mri":
+        if mean_t1 is None or std_t1 is None:
+            raise ValueError("patchcore_preprocess: mri needs mean_t1 and std_t1")
+        if translate_zero:
+            mini = (0 - mean_t1) / std_t1
+            lr_ad = lr_ad - torch.abs(torch.tensor(mini))
+        lr_ad = lr_ad[:, 0] * std_t1 + mean_t1
+        lr_ad = lr_ad / 4096.0
+        lr_ad = lr_ad.repeat(1, 3, 1, 1)
+    elif "mvtec" in data or data == "mnist":
+        if lr_ad.shape[1] == 1:
+            lr_ad = lr_ad.repeat(1, 3, 1, 1)
+        if lr_ad.max() > 1.0:
+            lr_ad = lr_ad / 2
+        size = 224 if "mvtec" in data else 84
+        lr_ad = F.interpolate(lr_ad, size=(size, size), mode="bilinear", align_corners=False)
+    else:
+        raise ValueError(f"patchcore_preprocess: data {data!r} (mnist, mri or mvtec*)")
+    mean = torch.tensor(IMAGENET_MEAN, dtype=lr_ad.dtype, device=lr_ad.device).view(-1, 1, 1)
+    std = torch.tensor(IMAGENET_STD, dtype=lr_ad.dtype, device=lr_ad.device).view(-1, 1, 1)
+    return (lr_ad - mean) / std
+
+
+def _pc_threshold(rule, a):
+    """(threshold, clip floor) of test.py's branch for ``rule`` on the map a, or None where it falls back to ones."""
+    mx = a.max()
+    if rule == "8to3":
+        if not mx > 37.0:
+            return None
+        thr = 41.7 if mx > 44 else (38.2 if mx > 40.0 else 35.0)
+        return thr, thr - a.std()
+    if rule == "8to5":
+        if not mx > 58.5:
+            return None
+        thr = 61.0 if mx > 71.0 else (57.0 if mx > 65 else 55.0)
+        return thr, thr - a.std()
+    if rule == "t12flair":
+        if not mx > 43:
+            return None
+        thr = mx - 12 if mx > 60 else (47 if mx > 51 else (44 if mx > 48.5 else 42))
+        return thr, thr - a.std()
+    if rule == "flair2t1":
+        if not mx > 43:
+            return None
+        thr = 47 if mx > 60 else (43 if mx > 50 else 42)
+        return thr, thr - a.std()
+    if rule == "transistor":
+        if not mx > 32:
+            return None
+        if mx > 40.0:
+            thr = 33.5
+        elif mx > 36.8:
+            thr = mx - 2 * a.std()
+        elif mx > 35.0:
+            thr = mx - 1 * a.std()
+        else:
+            thr = 29.5
+        return thr, thr - 0.5 * a.std()
+    if rule == "toothbrush":
+        if not mx > 35:
+            return None
+        return (40.0 if mx > 49 else 28.0), a.min()
+    if rule == "grid":
+        if not mx > 27:
+            return None
+        return (35.0 if mx > 40 else (30.0 if mx > 35.0 else 26.5)), a.min()
+    raise ValueError(f"patchcore_ood_mask: rule {rule!r} (one of {sorted(PATCHCORE_RULES)})")
+
+
+def patchcore_ood_mask(anomaly_map, rule, img_size=None):
+    """The reference's OOD mask from a PatchCore anomaly map (test.py:245-375): for the mnist and mvtec rules the map is
+    first resized (bilinear, align_corners=False) to img_size x img_size when img_size is given (test.py:245-246); then
+    the rule's threshold ladder (mnist '8to3' / '8to5', mri 't12flair' / 'flair2t1', mvtec 'transistor' / 'toothbrush' /
+    'grid'), the clip to [floor, threshold] and the squared min-max scaling, or all ones below the rule's first cut.
+    Returns (mask_pred, binary_mask) [B, 1, H, W] fp32 on the CPU, as test.py holds them."""
+    if rule not in PATCHCORE_RULES:
+        raise ValueError(f"patchcore_ood_mask: rule {rule!r} (one of {sorted(PATCHCORE_RULES)})")
+    a = anomaly_map.detach().float()
+    if img_size is not None and PATCHCORE_RULES[rule] in ("mnist", "mvtec"):
+        a = F.interpolate(a, size=(img_size, img_size), mode="bilinear", align_corners=False)
+    a = a.cpu()
+    cut = _pc_threshold(rule, a)
+    if cut is None:
+        return torch.ones_like(a), torch.ones_like(a)
+    thr, floor = cut
+    binary = (a > thr).float()
+    m = torch.clip(a, min=floor, max=thr)
+    m = (m - m.min()) / (thr - m.min())
+    return m ** 2, binary
+
+
 def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda", batch_size=1):
     """test.py's loop: sample every LR image, compare with HR.  Returns a dict of metrics."""
     preds, losses, times = [], [], []

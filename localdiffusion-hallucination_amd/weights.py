@@ -292,3 +292,83 @@ def procedural_seg_state_dict(seed=0, bn_stats=None, n_channels=1, n_classes=1):
             t = u / np.sqrt(_fan_in(wshape))
         out[name] = np.ascontiguousarray(t, dtype=np.float32)
     return out
+
+
+# ----------------------------------------------------------------------------- PatchCore backbone (wide_resnet50_2)
+PC_STAGES = (("layer1", 3, 128, 256, 1), ("layer2", 4, 256, 512, 2), ("layer3", 6, 512, 1024, 2))  # blocks, width, out, stride
+
+
+def _bn_shapes(sh, p, c):
+    for k in _BN_BUFFERS:
+        sh[p + k] = () if k == "num_batches_tracked" else (c,)
+
+
+def patchcore_param_shapes() -> "OrderedDict[str, tuple]":
+    """name -> shape of the torchvision / timm ``wide_resnet50_2`` state_dict up to layer3, in its order (what timm's
+    ``features_only`` trunk for layers 2 and 3 keeps: conv1, bn1, layer1..3; layer4 and fc are not used)."""
+    sh = OrderedDict()
+    sh["conv1.weight"] = (64, 3, 7, 7)
+    _bn_shapes(sh, "bn1.", 64)
+    cin = 64
+    for name, blocks, width, cout, _ in PC_STAGES:
+        for i in range(blocks):
+            p = f"{name}.{i}."
+            sh[p + "conv1.weight"] = (width, cin, 1, 1)
+            _bn_shapes(sh, p + "bn1.", width)
+            sh[p + "conv2.weight"] = (width, width, 3, 3)
+            _bn_shapes(sh, p + "bn2.", width)
+            sh[p + "conv3.weight"] = (cout, width, 1, 1)
+            _bn_shapes(sh, p + "bn3.", cout)
+            if i == 0:
+                sh[p + "downsample.0.weight"] = (cout, cin, 1, 1)
+                _bn_shapes(sh, p + "downsample.1.", cout)
+            cin = cout
+    return sh
+
+
+def procedural_patchcore_state_dict(seed=0, calib_size=48, calib_batch=2):
+    """Name-keyed procedural ``wide_resnet50_2`` trunk weights (numpy, torchvision's names): convolutions
+    uniform(+-sqrt(3 / fan_in)) (unit gain), BatchNorm gamma = 1 + 0.1 u, beta = 0.1 u, except the residual branches'
+    last BatchNorm (bn3), which is scaled by 1/4 so the residual stream does not grow block by block.  The statistics are
+    calibrated: a procedural ImageNet-normalised batch [calib_batch, 3, calib_size, calib_size] goes through the trunk in
+    eval order on the CPU, and each BatchNorm gets its input's per-channel batch mean and (biased) variance, so the
+    activations stay O(1) through layer3.  num_batches_tracked = 1."""
+    import torch
+    import torch.nn.functional as F
+    shapes = patchcore_param_shapes()
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        if name.endswith(("running_mean", "running_var", "num_batches_tracked")):
+            continue
+        u = procedural_tensor("pc." + name, shape, seed)
+        if len(shape) == 4:
+            t = u * np.sqrt(3.0 / _fan_in(shape))
+        else:
+            t = (1.0 + 0.1 * u) if name.endswith(".weight") else 0.1 * u
+            if ".bn3." in name:
+                t = 0.25 * t
+        out[name] = np.ascontiguousarray(t, dtype=np.float32)
+    x = torch.from_numpy(rng.uniform((calib_batch, 3, calib_size, calib_size), seed, 7001, -2.0, 2.0))
+
+    def conv_bn(x, p_conv, p_bn, stride=1, pad=0, relu=True):
+        y = F.conv2d(x, torch.from_numpy(out[p_conv]), stride=stride, padding=pad)
+        mean, var = y.mean(dim=(0, 2, 3)), y.var(dim=(0, 2, 3), unbiased=False)
+        out[p_bn + "running_mean"] = mean.numpy().astype(np.float32)
+        out[p_bn + "running_var"] = var.numpy().astype(np.float32)
+        out[p_bn + "num_batches_tracked"] = np.asarray(1, dtype=np.int64)
+        y = F.batch_norm(y, mean, var, torch.from_numpy(out[p_bn + "weight"]), torch.from_numpy(out[p_bn + "bias"]),
+                         False, 0.0, 1e-5)
+        return F.relu(y) if relu else y
+
+    with torch.no_grad():
+        x = conv_bn(x.float(), "conv1.weight", "bn1.", 2, 3)
+        x = F.max_pool2d(x, 3, 2, 1)
+        for name, blocks, _, _, stride in PC_STAGES:
+            for i in range(blocks):
+                p, s = f"{name}.{i}.", (stride if i == 0 else 1)
+                idn = conv_bn(x, p + "downsample.0.weight", p + "downsample.1.", s, 0, False) if i == 0 else x
+                y = conv_bn(x, p + "conv1.weight", p + "bn1.")
+                y = conv_bn(y, p + "conv2.weight", p + "bn2.", s, 1)
+                y = conv_bn(y, p + "conv3.weight", p + "bn3.", relu=False)
+                x = F.relu(y + idn)
+    return OrderedDict((k, out[k]) for k in shapes)
