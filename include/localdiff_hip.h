@@ -577,6 +577,20 @@ int ld_pc_score(const float* rows, const float* row_norms, const float* patch_sc
 int ld_pc_anomaly_map(const float* scores, const float* g, int ks, float* tmp, float* out, int B, int h, int w, int H,
                       int W, void* stream);
 
+/* ---- PatchCore memory banks: anomalib's KCenterGreedy coreset (models.py:165-172), csrc/coreset.hip ---- */
+/* The projection F = E @ R^T: E [N, D] row-major (D a multiple of 4, at most 2048), R [k, D] in CSR form (rowptr [k + 1],
+ * cols / vals [rowptr[k]]; any R, dense ones included), written feature-major: out [k, ld], ld >= N a multiple of 4,
+ * columns N..ld-1 untouched.  E and out 16-byte aligned. */
+int ld_pc_project(const float* e, int64_t N, int D, const int32_t* rowptr, const int32_t* cols, const float* vals, int k,
+                  float* out, int64_t ld, void* stream);
+/* The greedy selection over features ft [k, ld] (the layout of ld_pc_project, 16-byte aligned): min_d = dist(F, F[start]),
+ * then n times idx = first argmax(min_d), min_d[idx] = 0, min_d = minimum(min_d, dist(F, F[idx])) with dist the
+ * F.pairwise_distance |x - c + 1e-6|_2.  One launch per step on `stream`, no host synchronisation.  min_d: [ld] fp32
+ * scratch (16-byte aligned), keys: [n] uint64 scratch (zeroed here), idx: [n] int64, the picks in order.
+ * 1 <= n <= N < 2^31, 0 <= start < N, 1 <= k <= 8192. */
+int ld_pc_coreset(const float* ft, int64_t ld, int64_t N, int k, int64_t n, int64_t start, float* min_d,
+                  unsigned long long* keys, int64_t* idx, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -31,7 +31,7 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "PatchCore", "configure_runtime"]
+           "PatchCore", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -44,6 +44,9 @@ def __getattr__(name):
     if name == "SegUNet":
         from .segnet import SegUNet
         return SegUNet
+    if name == "coreset":
+        import importlib
+        return importlib.import_module(".coreset", __name__)
     if name == "PatchCore":
         from .patchcore import PatchCore
         return PatchCore

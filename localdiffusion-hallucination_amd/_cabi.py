@@ -162,6 +162,8 @@ _SIGS = {
     "ld_pc_score_prepare": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "ld_pc_score": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ld_pc_anomaly_map": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_pc_project": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, C.c_int, vp, i64, vp]),
+    "ld_pc_coreset": (C.c_int, [vp, i64, i64, C.c_int, i64, i64, vp, vp, vp, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -117,6 +117,16 @@ def load_seg_checkpoint(path_or_dict, seg, trust_pickle=False):
 _PC_PREFIXES = ("feature_extractor.feature_extractor.", "feature_extractor.", "module.")
 
 
+def save_patchcore_bank(model, path):
+    """``np.save`` of the model's memory bank as fp32 [M, 1536] (anomaly_model_train.py:376-385): the file that
+    ``load_patchcore(..., memory_bank_npy=path, ...)`` and test.py:169-175 read back."""
+    import numpy as np
+    bank = model.memory_bank.detach().to("cpu", torch.float32).numpy()
+    if bank.ndim != 2 or bank.shape[0] < 1:
+        raise ValueError(f"save_patchcore_bank: the model's memory bank {bank.shape} is empty")
+    np.save(path, np.ascontiguousarray(bank))
+
+
 def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
     """Load a ``PatchCore``: the ``wide_resnet50_2`` weights and the memory bank (test.py:157-175).
 

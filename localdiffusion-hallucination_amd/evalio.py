@@ -126,6 +126,19 @@ def patchcore_preprocess(lr, data, mean_t1=None, std_t1=None, translate_zero=Tru
     return (lr_ad - mean) / std
 
 
+def patchcore_bank_preprocess(x, data):
+    """PatchCore's input when a memory bank is built (anomaly_model_train.py:354-361), which differs from
+    ``patchcore_preprocess``: three channels; outside 'mri', / 2 when the max of the whole batch is above 1; bilinear
+    resize (align_corners=False) to 224 x 224 in every mode, mnist included; the ImageNet ``Normalize``."""
+    x = x.repeat(1, 3, 1, 1) if x.shape[1] != 3 else x
+    if data != "mri" and x.max() > 1.0:
+        x = x / 2.0
+    x = F.interpolate(x, size=(224, 224), mode="bilinear", align_corners=False)
+    mean = torch.tensor(IMAGENET_MEAN, dtype=x.dtype, device=x.device).view(-1, 1, 1)
+    std = torch.tensor(IMAGENET_STD, dtype=x.dtype, device=x.device).view(-1, 1, 1)
+    return (x - mean) / std
+
+
 def _pc_threshold(rule, a):
     """(threshold, clip floor) of test.py's branch for ``rule`` on the map a, or None where it falls back to ones."""
     mx = a.max()

@@ -14,7 +14,9 @@ layer1..3; what anomalib's attribute holds) plus the ``memory_bank`` buffer.  Th
 * the anomaly map: nearest upsample to ``input_size`` and the 33x33 Gaussian blur (sigma 4, reflect padding).
 
 All fp32.  BatchNorm always uses the running statistics: the module must be in ``eval()`` mode.  No CPU fallback.
-Not covered: other backbones or layers, the tiler, building a memory bank (coreset subsampling), training.
+A memory bank is built with ``build_memory_bank`` / ``subsample_embedding`` (anomaly_model_train.py:339-385): the
+training embeddings, then anomalib's KCenterGreedy coreset on the kernels of ``csrc/coreset.hip`` (``coreset.py``).
+Not covered: other backbones or layers, the tiler, training the trunk.
 """
 import ctypes as C
 
@@ -332,3 +334,26 @@ class PatchCore(nn.Module):
         cabi.check(lib.ld_pc_anomaly_map(scores.data_ptr(), g.data_ptr(), g.numel(), tmp.data_ptr(), amap.data_ptr(), B, h,
                                          w, Ho, Wo, st), "pc_anomaly_map")
         return {"anomaly_map": amap, "pred_score": pred}
+
+    # ------------------------------------------------------------------ memory-bank construction
+    def subsample_embedding(self, embedding, sampling_ratio, **kw):
+        """models.py:165-172: the KCenterGreedy coreset of embedding [N, 1536] (on the GPU) becomes the memory bank,
+        ``memory_bank = embedding[indices]``.  ``kw`` goes to ``coreset.kcenter_greedy`` (projection, features, start,
+        seed).  Returns the indices (int64, pick order).  ValueError when int(N * sampling_ratio) is 0."""
+        from .coreset import coreset_size, kcenter_greedy
+        if embedding.dim() != 2 or embedding.shape[1] != EMBED_DIM:
+            raise ValueError(f"PatchCore: embedding {tuple(embedding.shape)}, expected [N, {EMBED_DIM}]")
+        if coreset_size(embedding.shape[0], sampling_ratio) < 1:
+            raise ValueError(f"PatchCore: sampling_ratio {sampling_ratio} of {embedding.shape[0]} rows selects none")
+        idx = kcenter_greedy(embedding, sampling_ratio=sampling_ratio, **kw)
+        self.set_memory_bank(embedding.detach()[idx])
+        return idx
+
+    def build_memory_bank(self, batches, sampling_ratio=0.1, **kw):
+        """anomaly_model_train.py:348-372: embed every prepared batch (``evalio.patchcore_bank_preprocess``, ImageNet
+        normalised [B, 3, H, W]), stack the rows on the device, and ``subsample_embedding`` them.  Returns the indices."""
+        dev = self.feature_extractor.conv1.weight.device
+        rows = [self.embed(b.to(dev)) for b in batches]
+        if not rows:
+            raise ValueError("PatchCore.build_memory_bank: no batches")
+        return self.subsample_embedding(torch.cat(rows), sampling_ratio, **kw)
