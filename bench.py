@@ -16,11 +16,15 @@ process K/T of a patch, so   value = n_gpus * patches_per_gpu * K / (T * seconds
 The conditioning encoder runs once per sample in the product (its input is constant over t), so
 one encoder evaluation is executed INSIDE the timed region.
 
-Prints ONE JSON line on rank 0 (see the task contract), including
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run does only what that line's headline needs: set-up,
+warm-up, the K timed steps, --dump-outputs, the line.  With --full the line also carries what takes runs of its own:
   roofline     -- dominant kernel family: algorithmic bytes (or flops) per launch / live per-launch HIP-event time,
                   with the per-family table (launches per step, bytes and flops per launch, average duration) that
                   the fraction can be recomputed from, by hand or from profiles/*_kernel_stats.csv
+  other_dtype, two_term_weights, dtype_end_to_end -- the other 16-bit storage type, the accuracy mode, golden G16's distance
+  cfg4_share, cfg5 -- short legs of the other BASELINE configs (N = 1, the default shape)
   cpu_baseline -- the oracle (plain PyTorch fp32 CPU port of the reference) on this box's cores.
+The --no-* switches narrow a --full run; a plain run has none of these blocks.
 
 N > 1: under torch.distributed.run (WORLD_SIZE set) every process is one rank; called plainly as
 `python bench.py --gpus N` the script starts N rank processes itself (before anything touches the GPU) and relays
@@ -47,7 +51,7 @@ MFMA_PEAK_TF = {"bf16": 2500.0, "fp16": 2500.0, "fp32": 157.3}   # dense MFMA pe
 ALGO_TB_PER_PATCH = 0.7036       # algorithmic bytes per 3x256x256 bf16 patch over T=1000
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400,
@@ -58,27 +62,34 @@ def parse():
                     help="storage dtype; default: bf16 for cfg3 (BASELINE configs[2]), fp16 for cfg5 (configs[4])")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--patches", type=int, default=8, help="local patches per GPU (K masks of one image)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-dtype", action="store_true", help="skip the short extra run in the other 16-bit storage type")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what the line does not need: the roofline legs, the other 16-bit "
+                         "storage type, the two-term weights, the G16 distance, the cfg4_share / cfg5 legs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-launch roofline legs")
+    ap.add_argument("--no-other-dtype", action="store_true",
+                    help="--full: skip the short extra runs in the other 16-bit storage type and with two-term weights, the G16 "
+                         "distance and the cfg4_share / cfg5 legs")
     ap.add_argument("--workload", default="cfg3", choices=["cfg3", "cfg5"],
                     help="cfg3 (default, the headline metric) | cfg5: BASELINE configs[4] as stated -- one 1x512x512 image per GPU, "
                          "DDIM 50 of 1000 steps, OOD/IND branches with a circular mask, fusion at times[-4]; reports images/s")
     ap.add_argument("--images", type=int, default=None,
                     help="cfg5 only: images in the whole job (default: one per GPU, image-sharded).  Fewer images than ranks: the "
                          "branch-patch units of every image are spread over the ranks (dist.sample_kmask_sharded)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the short cfg4-share (64 patches per GPU) and cfg5 legs of the default line")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the short cfg4-share (64 patches per GPU) and cfg5 legs")
     ap.add_argument("--weight-split-levels", type=int, default=None,
                     help="two-term (hi + lo) convolution weights on the first N resolution levels (accuracy mode, DESIGN section 2); "
-                         "the default line is measured with 0 and reports the cost of 2 in `two_term_weights`")
+                         "the default line is measured with 0; --full reports the cost of 2 in `two_term_weights`")
     ap.add_argument("--graph", type=int, default=-1, help="1: replay the reverse step from a captured HIP graph (default: eager launches)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32; "
                          "cfg3: x_t of the local patches and the recomposed image, cfg5: the finished image; at most 64 MB in all, "
                          "a fixed seeded sample of each array beyond that).  The inputs depend on the arguments only")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:                   # a plain run: the headline measurement alone
+        a.no_cpu_baseline = a.no_roofline = a.no_other_dtype = a.no_legs = True
     if a.dtype is None:
         a.dtype = "fp16" if a.workload == "cfg5" else "bf16"
     return a
@@ -679,7 +690,7 @@ def bench_cfg5(a, rank, world, dev, dist):
 
 
 def _compact_leg(line):
-    """A whole bench line -> the short form the default line carries for the other BASELINE configs: throughput, step time
+    """A whole bench line -> the short form the --full line carries for the other BASELINE configs: throughput, step time
     and the dominant kernel family with its roofline fraction (no per-family table)."""
     keep = {k: line[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "dtype") if k in line}
     r = line.get("roofline")
@@ -895,7 +906,7 @@ def main():
         if pin is not None:
             out["dtype_end_to_end"] = pin
     if rank == 0 and world == 1 and not a.no_legs and not a.no_other_dtype and a.dtype in ("bf16", "fp16") and P == 8 and H == 256:
-        # The other BASELINE configs' throughput where the driver sees it, AFTER the headline measurement and
+        # --full: the other BASELINE configs' throughput in the same line, AFTER the headline measurement and
         # its per-launch legs: short runs, compact blocks (the whole lines: `--patches 64`, `--workload cfg5`).
         #   cfg4_share -- configs[3]'s share of one GPU: 64 local patches per GPU (two sub-batches of 32), 20 timed steps;
         #   cfg5       -- configs[4] as stated on one GPU: 1x512x512, fp16, DDIM 50 of 1000, OOD + IND branches, fusion: three samples.

@@ -114,12 +114,12 @@ def test_cfg5_one_image_on_two_ranks_spreads_its_branch_units_and_equals_the_one
 
 
 @pytest.mark.gpu
-def test_default_line_carries_every_baseline_config():
-    """The default bench line (what the driver runs, N = 1): the headline cfg3 measurement first, then the compact `cfg4_share`
+def test_full_line_carries_every_baseline_config():
+    """The --full bench line (N = 1): the headline cfg3 measurement first, then the compact `cfg4_share`
     (64 patches per GPU) and `cfg5` (512^2, fp16, DDIM 50, branch + fusion) legs with throughput, step time and their dominant
     family's roofline fraction, the other storage dtype, the dtype's end-to-end distance -- ONE JSON line."""
     import json
-    r = _run(["--steps", "6", "--warmup", "3", "--no-cpu-baseline"])
+    r = _run(["--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -156,6 +156,36 @@ def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path, monkey
         a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
         assert a.dtype == np.float32 and 0 < a.size < big[k].numel() and np.array_equal(a, b)
         assert np.isin(a, big[k].numpy()).all()
+
+
+EXTRA_BLOCKS = ("roofline", "other_dtype", "two_term_weights", "dtype_end_to_end", "cfg4_share", "cfg5", "cpu_baseline")
+
+
+def test_only_full_runs_what_the_headline_does_not_need():
+    """A plain run is the headline measurement alone; --full adds every extra leg, and the --no-* switches narrow --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    extras = ("no_cpu_baseline", "no_roofline", "no_other_dtype", "no_legs")
+    plain = bench.parse(["--steps", "4", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in extras)
+    full = bench.parse(["--steps", "4", "--warmup", "2", "--full"])
+    assert full.full and not any(getattr(full, k) for k in extras)
+    narrowed = bench.parse(["--full", "--no-roofline"])
+    assert narrowed.no_roofline and not narrowed.no_cpu_baseline and not narrowed.no_other_dtype
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone():
+    """`bench.py --steps K --warmup W` prints ONE line with the headline fields and none of the --full blocks."""
+    import json
+    r = _run(["--steps", "4", "--warmup", "2"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"].startswith("local patches/sec") and j["unit"] == "patches/s" and j["higher_is_better"] is True
+    assert j["steps"] == 4 and j["warmup"] == 2 and j["dtype"] == "bf16" and j["value"] > 0 and j["ms_per_step"] > 0
+    assert not any(k in j for k in EXTRA_BLOCKS), sorted(j)
 
 
 def test_steps_below_one_is_refused():

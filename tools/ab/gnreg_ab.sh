@@ -12,7 +12,7 @@ import sys,json; d=json.loads(sys.stdin.read()); print('gn_reg_coef=%-3s' % '$m'
   done
 done
 for m in $SET; do
-  LD_GN_REG_COEF=$m LD_BENCH_OPS=/tmp/ops_$m.txt python bench.py --no-cpu-baseline --no-other-dtype --no-legs --steps 100 > /dev/null 2>&1
+  LD_GN_REG_COEF=$m LD_BENCH_OPS=/tmp/ops_$m.txt python bench.py --full --no-cpu-baseline --no-other-dtype --no-legs --steps 100 > /dev/null 2>&1
   python - <<PY
 import re
 rows=[l for l in open('/tmp/ops_$m.txt')]

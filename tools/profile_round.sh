@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: the evidence set of one round, all from ONE box.  usage: bash tools/profile_round.sh r02_a
-#   1. default bench line (two concurrent sub-batches)                    -> gpurun_out/<tag>_bench.json
+#   1. the --full bench line (two concurrent sub-batches)                 -> <tag>_bench.json
 #   2. the same with LD_SUB_BATCHES=1 (one batch, one stream: the regime `roofline.frac` prices)  -> <tag>_s1_bench.json
 #   3. rocprofv3 --kernel-trace --stats of both commands (fewer steps)    -> <tag>_kernel_stats.csv, <tag>_s1_kernel_stats.csv
 #   4. separate --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of the solo regime -> <tag>_s1_pmc_traffic.json / _pmc_summary.txt
@@ -12,11 +12,11 @@ TAG=${1:-rXX}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $OUT/${TAG}_bench.log 2>&1 < /dev/null
+python3 $R/bench.py --full > $OUT/${TAG}_bench.log 2>&1 < /dev/null
 tail -1 $OUT/${TAG}_bench.log > $OUT/${TAG}_bench.json
-LD_SUB_BATCHES=1 python3 $R/bench.py --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_s1_bench.log 2>&1 < /dev/null
+LD_SUB_BATCHES=1 python3 $R/bench.py --full --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_s1_bench.log 2>&1 < /dev/null
 tail -1 $OUT/${TAG}_s1_bench.log > $OUT/${TAG}_s1_bench.json
-python3 $R/bench.py --dtype fp16 --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_fp16_bench.log 2>&1 < /dev/null
+python3 $R/bench.py --dtype fp16 --full --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_fp16_bench.log 2>&1 < /dev/null
 tail -1 $OUT/${TAG}_fp16_bench.log > $OUT/${TAG}_fp16_bench.json
 rm -rf /tmp/prof_ks /tmp/prof_ks1 /tmp/prof_f /tmp/prof_w
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -o r -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-roofline --no-other-dtype > $OUT/${TAG}_ks.log 2>&1 < /dev/null
@@ -34,7 +34,7 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/prof_f2 -o r -- python3 $
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/prof_w2 -o r -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-roofline --no-other-dtype > $OUT/${TAG}_pw2.log 2>&1 < /dev/null
 python3 $R/tools/pmc_summarize.py /tmp/prof_f2 /tmp/prof_w2 $OUT/${TAG}_pmc_traffic.json $OUT/${TAG}_bench.json > $OUT/${TAG}_pmc_summary.txt 2>&1
 # 6. cfg5 (512^2, DDIM 50, branch + fusion, fp16): bench line with its roofline block + kernel trace
-python3 $R/bench.py --workload cfg5 --no-cpu-baseline > $OUT/${TAG}_cfg5_bench.log 2>&1 < /dev/null
+python3 $R/bench.py --workload cfg5 --full --no-cpu-baseline > $OUT/${TAG}_cfg5_bench.log 2>&1 < /dev/null
 tail -1 $OUT/${TAG}_cfg5_bench.log > $OUT/${TAG}_cfg5_bench.json
 rm -rf /tmp/prof_k5
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k5 -o r -- python3 $R/bench.py --workload cfg5 --steps 100 --no-cpu-baseline --no-roofline > $OUT/${TAG}_cfg5_ks.log 2>&1 < /dev/null
@@ -46,7 +46,7 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/prof_w5 -o r -- python3 $
 python3 $R/tools/pmc_summarize.py /tmp/prof_f5 /tmp/prof_w5 $OUT/${TAG}_cfg5_pmc_traffic.json $OUT/${TAG}_cfg5_bench.json > $OUT/${TAG}_cfg5_pmc_summary.txt 2>&1
 # 6c. the same for cfg4's per-GPU share (64 patches per GPU) -> <tag>_p64_pmc_traffic.json (the default line's cfg4_share leg quotes it)
 rm -rf /tmp/prof_f6 /tmp/prof_w6
-python3 $R/bench.py --patches 64 --steps 20 --warmup 5 --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_p64s_bench.log 2>&1 < /dev/null
+python3 $R/bench.py --patches 64 --steps 20 --warmup 5 --full --no-cpu-baseline --no-other-dtype > $OUT/${TAG}_p64s_bench.log 2>&1 < /dev/null
 tail -1 $OUT/${TAG}_p64s_bench.log > $OUT/${TAG}_p64s_bench.json
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/prof_f6 -o r -- python3 $R/bench.py --patches 64 --steps 6 --warmup 2 --no-cpu-baseline --no-roofline --no-other-dtype > $OUT/${TAG}_pf6.log 2>&1 < /dev/null
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/prof_w6 -o r -- python3 $R/bench.py --patches 64 --steps 6 --warmup 2 --no-cpu-baseline --no-roofline --no-other-dtype > $OUT/${TAG}_pw6.log 2>&1 < /dev/null
