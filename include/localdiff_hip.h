@@ -591,6 +591,40 @@ int ld_pc_project(const float* e, int64_t N, int D, const int32_t* rowptr, const
 int ld_pc_coreset(const float* ft, int64_t ld, int64_t N, int k, int64_t n, int64_t start, float* min_d,
                   unsigned long long* keys, int64_t* idx, void* stream);
 
+/* ---- the hallucination gate around PatchCore (Classifier_PatchCore, models.py:257-430), csrc/classifier.hip ---- */
+/* Max of each of the `groups` rows of x [groups, n] fp32 (groups = 1: the whole tensor, models.py:408; groups = B: each
+ * sample), accumulated into words[g] with atomicMax on an order-preserving uint32 code of the float.  words must be 0
+ * (the code's identity) on entry: ld_clf_resize zeroes a set of words for the next call (zero_words). */
+int ld_clf_max(const float* x, int groups, int64_t n, uint32_t* words, void* stream);
+enum { LD_CLF_PLAIN = 0, LD_CLF_HALVE = 1, LD_CLF_AFFINE = 2 };
+/* Bilinear resize (align_corners=False, no antialiasing, torch's source-index rule) of NCHW fp32 x [B, Cin, Hi, Wi] to
+ * out [B, Cout, Ho, Wo]; Cin == Cout, or Cin == 1 read for every output channel (models.py:405-406 without the repeat).
+ * mode LD_CLF_HALVE: a sample is halved when the max that ld_clf_max left in max_words[per_sample ? b : 0] is above 1.0
+ * (:407-409); LD_CLF_AFFINE: every input value becomes ((v - sub) * mul + add) / div first (:411-422).  normalize: the
+ * output is (v - mean[c]) / std[c] (Cout == 3; transforms.Normalize, :424).  zero_words / n_zero: words to clear for the
+ * next call's ld_clf_max, or NULL / 0.  pred / threshold / decision / n_decision: also write decision[i] = pred[i] >
+ * threshold (int32 1 / 0, :428-430) for i < n_decision; pred NULL: no decision.  One launch, no host synchronisation. */
+typedef struct ld_clf_resize_args {
+  const float* x;
+  float* out;
+  int32_t B, Cin, Cout, Hi, Wi, Ho, Wo;
+  int32_t mode;
+  const uint32_t* max_words;
+  int32_t per_sample;
+  uint32_t* zero_words;
+  int32_t n_zero;
+  float sub, mul, add, div;
+  int32_t normalize;
+  float mean[3], std[3];
+  const float* pred;
+  float threshold;
+  int32_t* decision;
+  int32_t n_decision;
+} ld_clf_resize_args;
+int ld_clf_resize(const ld_clf_resize_args* args, void* stream);
+/* decision[i] = pred_score[i] > threshold ? 1 : 0 for i < n, on its own (when no map is resized back). */
+int ld_clf_decide(const float* pred_score, float threshold, int32_t* decision, int n, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -31,7 +31,7 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "PatchCore", "coreset", "configure_runtime"]
+           "PatchCore", "PatchCoreClassifier", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -50,4 +50,7 @@ def __getattr__(name):
     if name == "PatchCore":
         from .patchcore import PatchCore
         return PatchCore
+    if name == "PatchCoreClassifier":
+        from .classifier import PatchCoreClassifier
+        return PatchCoreClassifier
     raise AttributeError(name)

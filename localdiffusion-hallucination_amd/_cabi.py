@@ -21,6 +21,7 @@ SCHED_COLS = 8
 STAT_STRIPES = 16      # LD_STAT_STRIPES
 COUNTER_CONV3X3_C32, COUNTER_CONV3X3_GENERIC, COUNTER_CONV3X3_S32 = 0, 1, 2
 SEG_SRC_PLAIN, SEG_SRC_POOL, SEG_SRC_CAT_D2S = 0, 1, 2
+CLF_PLAIN, CLF_HALVE, CLF_AFFINE = 0, 1, 2
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
@@ -65,6 +66,13 @@ class PcConvArgs(C.Structure):
     _fields_ = [("src", vp), ("weight", vp), ("scale", vp), ("shift", vp), ("residual", vp), ("out", vp), ("B", i32),
                 ("Hi", i32), ("Wi", i32), ("Cin", i32), ("Ho", i32), ("Wo", i32), ("Cout", i32), ("ksize", i32),
                 ("stride", i32), ("relu", i32)]
+
+
+class ClfResizeArgs(C.Structure):
+    _fields_ = [("x", vp), ("out", vp), ("B", i32), ("Cin", i32), ("Cout", i32), ("Hi", i32), ("Wi", i32), ("Ho", i32),
+                ("Wo", i32), ("mode", i32), ("max_words", vp), ("per_sample", i32), ("zero_words", vp), ("n_zero", i32),
+                ("sub", f32), ("mul", f32), ("add", f32), ("div", f32), ("normalize", i32), ("mean", f32 * 3),
+                ("std", f32 * 3), ("pred", vp), ("threshold", f32), ("decision", vp), ("n_decision", i32)]
 
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
@@ -164,6 +172,9 @@ _SIGS = {
     "ld_pc_anomaly_map": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_pc_project": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, C.c_int, vp, i64, vp]),
     "ld_pc_coreset": (C.c_int, [vp, i64, i64, C.c_int, i64, i64, vp, vp, vp, vp]),
+    "ld_clf_max": (C.c_int, [vp, C.c_int, i64, vp, vp]),
+    "ld_clf_resize": (C.c_int, [C.POINTER(ClfResizeArgs), vp]),
+    "ld_clf_decide": (C.c_int, [vp, f32, vp, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

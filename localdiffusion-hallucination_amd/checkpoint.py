@@ -168,3 +168,19 @@ def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
         raise RuntimeError("PatchCore: no memory bank (pass memory_bank_npy, or a state_dict with 'memory_bank')")
     model.set_memory_bank(bank)
     return {"n_tensors": len(sd), "bank_rows": int(model.memory_bank.shape[0])}
+
+
+def load_patchcore_classifier(backbone_sd, memory_bank_npy, config, obj, threshold=None, calibration=None, device="cuda",
+                              return_map=True, trust_pickle=False):
+    """Build the hallucination gate (models.py:257-294): a ``PatchCore`` of the mode's input size (84 x 84 for mnist,
+    224 x 224 otherwise, ``num_neighbors=9``), loaded by ``load_patchcore`` and moved to ``device`` in ``eval()``, inside
+    a ``PatchCoreClassifier``.  ``memory_bank_npy=None`` takes the ``memory_bank`` entry of ``backbone_sd``, the form of
+    the reference's mnist checkpoint (a whole-module state_dict, models.py:279); its mvtec / mri banks are ``.npy`` files
+    (:281-287).  ``threshold`` / ``calibration`` as in ``PatchCoreClassifier``."""
+    from .classifier import PatchCoreClassifier, gate_input_size
+    from .patchcore import PatchCore
+    S = gate_input_size(str(config["data"]))
+    model = PatchCore((S, S), layers=("layer2", "layer3"), backbone="wide_resnet50_2", num_neighbors=9)
+    load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=trust_pickle)
+    model = model.to(device).eval()
+    return PatchCoreClassifier(config, obj, model, threshold=threshold, calibration=calibration, return_map=return_map)

@@ -306,9 +306,10 @@ class PatchCore(nn.Module):
                                       EMBED_DIM, k, d2.data_ptr(), dist.data_ptr(), idx.data_ptr(), st), "pc_knn_topk")
         return dist, idx
 
-    def forward(self, x):
-        """x: ImageNet-normalised NCHW fp32 [B, 3, H, W] on the GPU -> {"anomaly_map": [B, 1, *input_size],
-        "pred_score": [B]} (models.py:108-127)."""
+    def score(self, x):
+        """The part of ``forward`` in front of the anomaly map: x as there -> (pred_score [B], patch scores [B*h*w],
+        (h, w)).  What a caller that only needs the image score launches (the gate of ``classifier.py`` when the map is
+        discarded); ``anomaly_map_of`` makes the map from the patch scores."""
         x = self._check_input(x)
         rows, norms, (h, w) = self._features(x)
         B, dev = x.shape[0], x.device
@@ -327,13 +328,25 @@ class PatchCore(nn.Module):
         support = self.topk(q, k, qn)[1] if k > 0 else None    # k = 0 (num_neighbors == 1): the max patch score
         cabi.check(lib.ld_pc_score(rows.data_ptr(), norms.data_ptr(), scores.data_ptr(), amax.data_ptr(), bank.data_ptr(),
                                    bn.data_ptr(), cabi.ptr(support), B, P, EMBED_DIM, k, pred.data_ptr(), st), "pc_score")
+        return pred, scores, (h, w)
+
+    def anomaly_map_of(self, scores, B, h, w):
+        """Patch scores [B*h*w] (of ``score``) -> the anomaly map [B, 1, *input_size]."""
+        dev = scores.device
+        st = torch.cuda.current_stream(dev).cuda_stream
         Ho, Wo = self.input_size
-        g = self._prep["gauss"]
+        g = self._prepare(dev)["gauss"]
         tmp = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev)
         amap = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=dev)
-        cabi.check(lib.ld_pc_anomaly_map(scores.data_ptr(), g.data_ptr(), g.numel(), tmp.data_ptr(), amap.data_ptr(), B, h,
-                                         w, Ho, Wo, st), "pc_anomaly_map")
-        return {"anomaly_map": amap, "pred_score": pred}
+        cabi.check(cabi.lib().ld_pc_anomaly_map(scores.data_ptr(), g.data_ptr(), g.numel(), tmp.data_ptr(), amap.data_ptr(),
+                                                B, h, w, Ho, Wo, st), "pc_anomaly_map")
+        return amap
+
+    def forward(self, x):
+        """x: ImageNet-normalised NCHW fp32 [B, 3, H, W] on the GPU -> {"anomaly_map": [B, 1, *input_size],
+        "pred_score": [B]} (models.py:108-127)."""
+        pred, scores, (h, w) = self.score(x)
+        return {"anomaly_map": self.anomaly_map_of(scores, x.shape[0], h, w), "pred_score": pred}
 
     # ------------------------------------------------------------------ memory-bank construction
     def subsample_embedding(self, embedding, sampling_ratio, **kw):
