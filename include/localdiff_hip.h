@@ -520,6 +520,61 @@ int ld_seg_head(const void* x, const float* w, const float* bias, float* logits,
 int ld_seg_pack_weight(const float* w_oihw, float* out, int cout, int cin, int ksize, void* stream);
 int ld_seg_pack_convt(const float* w, const float* bias, float* w_out, float* bias_out, int cin, int cout, void* stream);
 
+/* ---- training the segmentation U-Net (train_seg.py:78-95): csrc/segtrain.hip -------------------------------------------
+ * One optimisation step in fp32, NHWC.  The training-mode forward and the data gradient of every convolution are
+ * ld_pc_conv launches (scale = 1, shift = 0 or the ConvTranspose2d bias, no ReLU; the data gradient reads the weight
+ * flipped in (ky, kx) and transposed in (Cout, Cin), see ld_seg_permute3).  The entry points below are the rest of the
+ * step.  None allocates: reductions take a scratch buffer of LD_SEG_RED_WORK_BYTES, and every reduction adds its partial
+ * results in a fixed order (no floating-point atomics), so a step is reproducible bit for bit. */
+#define LD_SEG_RED_WORK_BYTES (2048 * 2 * 64 * 8)   /* `work` of the per-channel reductions and of ld_seg_loss */
+/* Weight gradient of a 3x3 (pad 1) or 1x1 convolution without bias: dw [Cout][ksize][ksize][Cin] (the OHWI layout
+ * ld_pc_conv reads) = sum over pixels of dy [B, H, W, Cout] x a [B, H, W, Cin] shifted by the tap, zero outside the
+ * image.  An implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32) with the pixel axis cut into `splits` parts, each
+ * writing its own slab of work [splits][Cout * ksize^2 * Cin], which a second kernel adds in order.  Cin, Cout multiples
+ * of 64; 1 <= splits <= ceil(B H W / 32).  ld_seg_wgrad_splits is the split count that fills the chip (0 for a shape
+ * ld_seg_wgrad refuses).  ksize 1 with dy = the gradient of the (p1, p2, c) GEMM output is ConvTranspose2d(2, 2)'s. */
+int ld_seg_wgrad_splits(int B, int H, int W, int Cin, int Cout, int ksize);
+int ld_seg_wgrad(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
+                 int ksize, int splits, void* stream);
+/* BatchNorm2d in training mode + ReLU over y [M, C] (M = B H W values per channel, at least 2; C a multiple of 64):
+ * stat [3][C] = batch mean, biased variance, 1 / sqrt(var + eps) (sums in fp64); out = relu((y - mean) invstd gamma +
+ * beta); running_mean / running_var (both or neither) updated as nn.BatchNorm2d does, the variance unbiased. */
+int ld_seg_bn_train(const float* y, const float* gamma, const float* beta, double* work, float* stat, float* running_mean,
+                    float* running_var, float momentum, float eps, float* out, int64_t M, int C, void* stream);
+/* Backward of the above: g = da * (act > 0) with act the SAVED activation, dbeta = sum g, dgamma = sum g x^,
+ * dy = gamma invstd (g - dbeta / M - x^ dgamma / M).  dy may be da (in place). */
+int ld_seg_bn_backward(const float* da, const float* act, const float* y, const float* gamma, const float* stat, double* work,
+                       float* dgamma, float* dbeta, float* dy, int64_t M, int C, void* stream);
+/* out [C / fold] = sum over the M rows of x [M, C] and over the `fold` groups of C / fold channels (fold 4: the bias
+ * gradient of a ConvTranspose2d(2, 2) from the gradient of its (p1, p2, c) GEMM output).  C a multiple of 64. */
+int ld_seg_colsum(const float* x, double* work, float* out, int64_t M, int C, int fold, void* stream);
+/* MaxPool2d(2): x [B, 2H, 2W, C] -> out [B, H, W, C], and its backward: dx [B, 2H, 2W, C] = dskip (NULL: 0) + dpool at
+ * the first maximum of each window in row-major order (ATen's rule).  C a multiple of 4. */
+int ld_seg_pool(const float* x, float* out, int B, int H, int W, int C, void* stream);
+int ld_seg_pool_backward(const float* x, const float* dpool, const float* dskip, float* dx, int B, int H, int W, int C,
+                         void* stream);
+/* out [B, H, W, C0 + C1] = cat([skip [B, H, W, C0], depth_to_space(low [B, H/2, W/2, 4*C1])]) (LD_SEG_SRC_CAT_D2S made
+ * real), and the split of its gradient into the two parts.  H, W even; C0, C1 multiples of 4. */
+int ld_seg_cat_d2s(const float* skip, const float* low, float* out, int B, int H, int W, int C0, int C1, void* stream);
+int ld_seg_cat_d2s_backward(const float* dcat, float* dskip, float* dlow, int B, int H, int W, int C0, int C1, void* stream);
+/* train_seg.py:89 over M logits: out [3] = {loss, bce, dice loss}, bce = BCEWithLogitsLoss(pos_weight) (mean), dice loss
+ * = 1 - (2 sum p t + eps) / (sum p + sum t + eps) with p = sigmoid(logit) over the whole batch, loss = their sum; dz [M]
+ * (or NULL) = d loss / d logit.  Sums in fp64. */
+int ld_seg_loss(const float* logits, const float* target, double* work, float* out, float* dz, int64_t M, float pos_weight,
+                float dice_eps, void* stream);
+/* outc backward: dw [C] = sum_p dz[p] x[p, c], db [1] = sum dz, dx [M, C] = dz[p] w[c].  C a multiple of 64. */
+int ld_seg_head_backward(const float* dz, const float* x, const float* w, double* work, float* dw, float* db, float* dx,
+                         int64_t M, int C, void* stream);
+/* torch.optim.Adam's update (no weight decay, no amsgrad) of one parameter tensor seen as [d0][d1][d2] (contiguous, m
+ * and v alike), whose gradient element sits at i0 s0 + i1 s1 + i2 s2 of grad.  step_size = lr / (1 - beta1^t) and
+ * bc2_sqrt = sqrt(1 - beta2^t) come from the host in double; 1 - beta is rounded to fp32 once, as torch does. */
+int ld_seg_adam(float* param, const float* grad, float* m, float* v, int d0, int d1, int d2, int64_t s0, int64_t s1,
+                int64_t s2, double beta1, double beta2, double eps, double step_size, double bc2_sqrt, void* stream);
+/* out[off + i0 s0 + i1 s1 + i2 s2] = in[(i0 d1 + i1) d2 + i2]: the weight layouts of the training step from the
+ * parameters' own (OIHW -> OHWI; OIHW -> the data gradient's [Cin][2 - ky][2 - kx][Cout] with a negative stride). */
+int ld_seg_permute3(const float* in, float* out, int d0, int d1, int d2, int64_t off, int64_t s0, int64_t s1, int64_t s2,
+                    void* stream);
+
 /* ---- PatchCore: the default OOD anomaly-map producer in front of sample() ----------------------------------------------
  * PatchcoreModel (models.py:42-254, eval) with the wide_resnet50_2 trunk up to layer3: features after layer2 / layer3,
  * AvgPool2d(3, 1, 1), bilinear resample of layer3 onto the layer2 grid, concat -> [N, 1536] rows, nearest neighbour in

@@ -31,7 +31,7 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "PatchCore", "PatchCoreClassifier", "coreset", "configure_runtime"]
+           "SegTrainer", "PatchCore", "PatchCoreClassifier", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -44,6 +44,9 @@ def __getattr__(name):
     if name == "SegUNet":
         from .segnet import SegUNet
         return SegUNet
+    if name == "SegTrainer":
+        from .segtrain import SegTrainer
+        return SegTrainer
     if name == "coreset":
         import importlib
         return importlib.import_module(".coreset", __name__)

@@ -160,6 +160,20 @@ _SIGS = {
     "ld_seg_head": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_seg_pack_weight": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ld_seg_pack_convt": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "ld_seg_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ld_seg_wgrad": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_bn_train": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, i64, C.c_int, vp]),
+    "ld_seg_bn_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, vp]),
+    "ld_seg_colsum": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, vp]),
+    "ld_seg_pool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_pool_backward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_cat_d2s": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_cat_d2s_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_seg_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, vp]),
+    "ld_seg_head_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, vp]),
+    "ld_seg_adam": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, C.c_double, C.c_double, C.c_double,
+                    C.c_double, C.c_double, vp]),
+    "ld_seg_permute3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, vp]),
     "ld_pc_conv": (C.c_int, [C.POINTER(PcConvArgs), vp]),
     "ld_pc_stem": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ld_pc_maxpool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

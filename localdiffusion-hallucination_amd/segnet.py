@@ -6,11 +6,13 @@
 statistics and ``num_batches_tracked`` included) and ``test.py``'s ``seg_model.load_state_dict(torch.load(path))`` works
 unchanged.  The forward is 23 launches: per DoubleConv two 3x3 convolutions with BatchNorm (eval) + ReLU as an fp32
 epilogue, Down's max-pool read by the next convolution, each Up's ConvTranspose2d(2, 2) as a 1x1 GEMM whose output the
-next convolution reads through depth-to-space beside the skip tensor, and the 1x1 head.  BatchNorm always uses the
-running statistics: the module must be in ``eval()`` mode, as test.py:221 puts it.  No CPU fallback.
+next convolution reads through depth-to-space beside the skip tensor, and the 1x1 head.  In ``eval()`` mode, as
+test.py:221 puts it, BatchNorm uses the running statistics.  In ``train()`` mode ``forward`` uses batch statistics and
+updates the running ones, as the reference module does (fp32 only, the kernels of ``csrc/segtrain.hip``); the optimisation
+step of train_seg.py is ``segtrain.SegTrainer``.  No CPU fallback.
 
 Not covered: ``bilinear=True``, sizes that are not multiples of 16 (the reference's F.pad path, :193-199), more than
-one class, training.
+one class, 16-bit storage while training.
 """
 import ctypes as C
 
@@ -79,11 +81,13 @@ class SegUNet(nn.Module):
             raise ValueError(f"SegUNet: compute_dtype {compute_dtype!r} (fp32, bf16 or fp16)")
         self._prep = None            # device-side packed weights + BN affines (per device / weights)
         self._plans = {}             # (B, H, W, dtype) -> launch list with its activation buffers
+        self._train = None           # segtrain._TrainState: training-layout weights, gradients, saved activations
 
     # ------------------------------------------------------------------ cache control
     def invalidate(self):
         self._prep = None
         self._plans = {}
+        self._train = None
 
     def set_compute_dtype(self, dtype):
         if dtype not in _TDT:
@@ -197,8 +201,8 @@ class SegUNet(nn.Module):
 
     def _check_input(self, x):
         if self.training:
-            raise RuntimeError("SegUNet runs BatchNorm with its running statistics only: call .eval() first "
-                               "(test.py:221 does); training the segmentation net is not covered")
+            raise RuntimeError("SegUNet.predict_mask runs BatchNorm with its running statistics: call .eval() first "
+                               "(test.py:221 does); in train() mode use forward() or segtrain.SegTrainer")
         if x.dim() != 4 or x.shape[1] != self.n_channels:
             raise ValueError(f"SegUNet: input {tuple(x.shape)}, expected [B, {self.n_channels}, H, W]")
         B, _, H, W = x.shape
@@ -229,7 +233,11 @@ class SegUNet(nn.Module):
                                    cabi.ptr(mask), B, H, W, SEG_WIDTHS[0], code, st), "seg_head")
 
     def forward(self, x):
-        """x: NCHW fp32 [B, n_channels, H, W] on the GPU -> logits NCHW fp32 [B, 1, H, W] (unet_model.py:232-243)."""
+        """x: NCHW fp32 [B, n_channels, H, W] on the GPU -> logits NCHW fp32 [B, 1, H, W] (unet_model.py:232-243).  In
+        ``train()`` mode: batch statistics, and the running ones are updated (fp32 only)."""
+        if self.training:
+            from . import segtrain
+            return segtrain.train_forward(self, x)
         x = self._check_input(x)
         logits = torch.empty((x.shape[0], 1, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
         self._run(x, logits=logits)

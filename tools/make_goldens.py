@@ -1032,6 +1032,144 @@ def g18(ddpm):
             f.write(f"{k} {list(v.shape)} {str(v.dtype).replace('torch.', '')}\n")
 
 
+SEG_TRAIN_BATCHES, SEG_TRAIN_B, SEG_TRAIN_H = 6, 4, 32
+
+
+def seg_train_batches(seeds):
+    """G19's batches: mri_like_slices shifted as G18 does, target = the slice's lesion (slice > 1.6)."""
+    mini = abs((0 - MEAN_T1) / STD_T1)
+    out = []
+    for s in seeds:
+        sl = mri_like_slices(SEG_TRAIN_B, SEG_TRAIN_H, s)
+        out.append((torch.from_numpy(sl) - mini, torch.from_numpy((sl > 1.6).astype(np.float32))))
+    return out
+
+
+def g19(ddpm):
+    """The reference's segmentation training step (train_seg.py:78-95): its own unet_model.UNet(), DiceLoss,
+    BCEWithLogitsLoss(pos_weight=10) and torch.optim.Adam(lr=1e-3) on six batches of B = 4 at 32^2, in fp64 (the yardstick)
+    and in fp32 in three arithmetic orders (the reference's own spread, which the whole-net tolerances of the GPU tests are
+    multiples of).  Two files (each below the size limit): g19_segtrain.npz and g19_segtrain_grads.npz (the gradients of
+    the tensors of at most 4,096 elements)."""
+    print("G19 segmentation U-Net training step")
+    import unet_model
+    import train_seg
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import segtrain_ref
+    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in weights.procedural_seg_state_dict(SEG_SEED).items()}
+
+    def fresh(dtype, channels_last=False):
+        m = unet_model.UNet()
+        m.load_state_dict(sd)
+        m = m.to(dtype)
+        if channels_last:
+            m = m.to(memory_format=torch.channels_last)
+        for p in m.parameters():
+            p.requires_grad = True
+        return m.train()
+
+    def criterion(m, x, t):
+        pred = m(x)
+        pw = torch.tensor([10]).to(pred.dtype)
+        return torch.nn.BCEWithLogitsLoss(pos_weight=pw)(pred, t) + train_seg.DiceLoss()(torch.sigmoid(pred), t)
+
+    def grads_at_init(dtype, x, t, channels_last=False, with_stats=False):
+        m = fresh(dtype, channels_last)
+        stats, hooks = {}, []
+        if with_stats:
+            for name, mod in m.named_modules():
+                if isinstance(mod, torch.nn.BatchNorm2d):
+                    def hook(_m, inp, name=name):
+                        stats[name + ".mean"] = inp[0].detach().mean(dim=(0, 2, 3)).numpy().copy()
+                        stats[name + ".var"] = inp[0].detach().var(dim=(0, 2, 3), unbiased=False).numpy().copy()
+                    hooks.append(mod.register_forward_pre_hook(hook))
+        x, t = x.to(dtype), t.to(dtype)
+        if channels_last:
+            x = x.contiguous(memory_format=torch.channels_last)
+        loss = criterion(m, x, t)
+        loss.backward()
+        return float(loss.detach()), [p.grad.detach().clone().contiguous() for p in m.parameters()], stats
+
+    def six_steps(dtype, batches, channels_last=False):
+        m = fresh(dtype, channels_last)
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+        losses, first = [], None
+        for x, t in batches:
+            opt.zero_grad()
+            x, t = x.to(dtype), t.to(dtype)
+            if channels_last:
+                x = x.contiguous(memory_format=torch.channels_last)
+            loss = criterion(m, x, t)
+            loss.backward()
+            opt.step()
+            losses.append(float(loss))
+            if first is None:
+                first = {k: v.detach().clone().numpy() for k, v in m.state_dict().items()
+                         if "running_" in k or k.endswith("num_batches_tracked")}
+        return losses, first
+
+    names = [k for k, _ in unet_model.UNet().named_parameters()]
+    assert len(names) == 64
+    orders = ("default", "channels_last", "onednn_off")
+
+    def run_order(order, fn):
+        if order == "onednn_off":
+            with torch.backends.mkldnn.flags(enabled=False):
+                return fn(False)
+        return fn(order == "channels_last")
+
+    probe_cache = {}
+    for attempt in range(8):
+        seeds = [190 + 10 * attempt + k for k in range(SEG_TRAIN_BATCHES)]
+        batches = seg_train_batches(seeds)
+        out = {"seeds": np.asarray(seeds, np.int64), "seed": np.int64(SEG_SEED),
+               "x": np.stack([b[0].numpy() for b in batches]), "target": np.stack([b[1].numpy() for b in batches]).astype(np.uint8)}
+        small = {}
+        ref_grads = []
+        losses0, norms, dots = [], np.zeros((SEG_TRAIN_BATCHES, 64)), np.zeros((SEG_TRAIN_BATCHES, 64, 4))
+        for b, (x, t) in enumerate(batches):
+            loss, grads, stats = grads_at_init(torch.float64, x, t, with_stats=True)
+            losses0.append(loss)
+            ref_grads.append(grads)
+            for i, g in enumerate(grads):
+                norms[b, i] = float(g.norm())
+                dots[b, i] = segtrain_ref.probe_dots(i, g, probe_cache)
+                if g.numel() <= 4096:
+                    small[f"grad{b}.{names[i]}"] = g.numpy().copy()
+            for k, v in stats.items():
+                out[f"bn{b}.{k}"] = v
+        out["loss_init"], out["grad_norm"], out["grad_dots"] = np.asarray(losses0), norms, dots
+        losses64, first = six_steps(torch.float64, batches)
+        out["loss_steps"] = np.asarray(losses64)
+        for k, v in first.items():
+            out["step1." + k] = v
+        frac = float(np.mean(out["target"]))
+        print(f"  seeds {seeds}: positives {100 * frac:.1f} %, fp64 losses {['%.4f' % l for l in losses64]}")
+        grad_spread, loss_spread, clean = 0.0, 0.0, np.zeros((3, SEG_TRAIN_BATCHES), np.int64)
+        first_loss_err = 0.0
+        for o, order in enumerate(orders):
+            for b, (x, t) in enumerate(batches):
+                loss, grads, _ = run_order(order, lambda cl: grads_at_init(torch.float32, x, t, channels_last=cl))
+                rel = [segtrain_ref.rel_l2(g, r) for g, r in zip(grads, ref_grads[b])]
+                grad_spread = max(grad_spread, max(rel))
+                clean[o, b] = sum(r <= 1e-4 for r in rel)
+                first_loss_err = max(first_loss_err, abs(loss - losses0[b]))
+            l32, _ = run_order(order, lambda cl: six_steps(torch.float32, batches, channels_last=cl))
+            loss_spread = max(loss_spread, max(abs(a - c) for a, c in zip(l32, losses64)))
+            print(f"  fp32 {order}: parameters within 1e-4 per batch {clean[o].tolist()}")
+        print(f"  grad_spread {grad_spread:.3e}, loss_spread {loss_spread:.3e}, first-step loss error {first_loss_err:.2e}")
+        out["grad_spread"], out["loss_spread"], out["clean"] = np.float64(grad_spread), np.float64(loss_spread), clean
+        out["first_loss_err"] = np.float64(first_loss_err)
+        if all(int((clean[o] >= 32).sum()) >= 2 for o in range(3)):
+            break
+        print("  an fp32 order misses the tight tier on these batches: other seeds")
+    else:
+        raise AssertionError("no batch seeds on which all three fp32 orders meet the tight tier")
+    assert 0.005 < frac < 0.2 and losses64[-1] < 0.8 * losses64[0], (frac, losses64)
+    save("g19_segtrain", **out)
+    save("g19_segtrain_grads", **small)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -1041,7 +1179,7 @@ def main():
     ddpm = import_reference()
     os.makedirs(GOLD, exist_ok=True)
     todo = [("G0", g0_inventory), ("G1", g1), ("G2", g2), ("G3", g3), ("G4", g4), ("G6", g6),
-            ("G7", g7), ("G8", g8), ("G9", g9), ("G10", g10), ("G12", g12), ("G14", g14), ("G15", g15), ("G17", g17), ("G18", g18), ("G5", g5), ("G11", g11), ("G13", g13), ("G16", g16)]
+            ("G7", g7), ("G8", g8), ("G9", g9), ("G10", g10), ("G12", g12), ("G14", g14), ("G15", g15), ("G17", g17), ("G18", g18), ("G19", g19), ("G5", g5), ("G11", g11), ("G13", g13), ("G16", g16)]
     only = set(filter(None, a.only.split(",")))
     for name, fn in todo:
         if only and name not in only:
