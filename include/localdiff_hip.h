@@ -680,6 +680,61 @@ int ld_clf_resize(const ld_clf_resize_args* args, void* stream);
 /* decision[i] = pred_score[i] > threshold ? 1 : 0 for i < n, on its own (when no map is resized back). */
 int ld_clf_decide(const float* pred_score, float threshold, int32_t* decision, int n, void* stream);
 
+/* ---- the MNIST digit classifier and its training step (train_mnist_cls.py: SimpleCNN), csrc/mnistcls.hip ----------------
+ * conv1 (1 -> 32) + ReLU + pool, conv2 (32 -> 64) + ReLU + pool, fc1 (3136 -> 128) + ReLU, fc2 (128 -> 10), softmax
+ * cross-entropy (mean), Adam.  fp32, activations NHWC.  conv2 and its two gradients are ld_pc_conv / ld_seg_wgrad launches
+ * on a pooled map that carries conv1's 32 channels with a stride of 64 (the upper 32 stay zero); fc1 reads the features in
+ * NHWC order (y, x, c), its weight repacked from the reference's (c, y, x).  Every reduction adds in a fixed order (no
+ * floating-point atomics). */
+/* conv1 + bias + ReLU + MaxPool2d(2): x [B, 28, 28] (one channel), w [32][9], bias [32] -> out [B, 14, 14] pixels of 64
+ * floats (only the first 32 are written) and idx [B, 14, 14, 32] (or NULL): the position 0..3 of the first maximum of each
+ * 2x2 window in row-major order. */
+int ld_mc_conv1(const float* x, const float* w, const float* bias, float* out, unsigned char* idx, int B, void* stream);
+/* MaxPool2d(2): x [B, 2H, 2W, C] -> out [B, H, W, C] and idx (or NULL) as above; its backward: dx [B, 2H, 2W, C] = dpool
+ * at the stored position where the pooled value (a ReLU output) is positive, 0 elsewhere (ReLU's gradient at 0 is 0). */
+int ld_mc_pool(const float* x, float* out, unsigned char* idx, int B, int H, int W, int C, void* stream);
+int ld_mc_pool_backward(const float* dpool, const float* pooled, const unsigned char* idx, float* dx, int B, int H, int W,
+                        int C, void* stream);
+/* out[z][m cm + n] = sum over the K range of split z of a[m am + k ak] * b[n bn + k bk], m < M, n < N, on
+ * v_mfma_f32_32x32x2_f32 (exact f32); slab z starts at z M cm.  splits 1 writes the product itself.  Strides in floats,
+ * positive; cm >= N; 1 <= splits <= ceil(K / 32), every split owning whole chunks of 32 and at least one. */
+int ld_mc_gemm(const float* a, const float* b, float* out, int M, int N, int K, int64_t am, int64_t ak, int64_t bn, int64_t bk,
+               int64_t cm, int splits, void* stream);
+/* h [B][N] = relu(work[0] + work[1] + ... in order + bias[n]) over the `splits` slabs [B][N] of an ld_mc_gemm. */
+int ld_mc_fc1_finish(const float* work, const float* bias, float* h, int B, int N, int splits, void* stream);
+/* fc2 and the loss: h [B][128], w2 [10][128], b2 [10] -> logits [B][10], pred [B] (or NULL: the lowest index of the largest
+ * logit).  With label [B] (int64; NULL: inference): loss_b [B] = logsumexp(z) - z[label] (the row maximum subtracted),
+ * dz [B][10] = (softmax - onehot) / B, dh [B][128] = dz . w2 where h > 0.  A label outside 0..9 indexes nothing: its
+ * loss_b is NaN, its dz and dh are 0 and *bad_label is set to 1 (never cleared here). */
+int ld_mc_head(const float* h, const float* w2, const float* b2, const int64_t* label, float* logits, int64_t* pred,
+               float* loss_b, float* dz, float* dh, int32_t* bad_label, int B, void* stream);
+/* gw2 [10][128] = dz^T h, gb2 [10] = sum_b dz, gb1 [128] = sum_b dh (fc1's bias), loss [1] = mean of loss_b. */
+int ld_mc_small_grads(const float* dz, const float* h, const float* dh, const float* loss_b, float* gw2, float* gb2, float* gb1,
+                      float* loss, int B, void* stream);
+/* conv1's weight [32][9] and bias [32] gradient from dp1 (the gradient of ld_mc_conv1's out, same layout), out itself
+ * (the ReLU mask) and idx; work holds ld_mc_conv1_wgrad_work_floats(B) floats. */
+int64_t ld_mc_conv1_wgrad_work_floats(int B);
+int ld_mc_conv1_wgrad(const float* x, const float* p1, const float* dp1, const unsigned char* idx, float* work, float* gw,
+                      float* gb, int B, void* stream);
+/* ld_seg_adam's update over up to LD_MC_ADAM_MAX tensors in one launch.  Each is seen as [d0][d1][d2] (param, m, v
+ * contiguous); its gradient element sits at i0 gs0 + i1 gs1 + i2 gs2 of grad; the updated value is also written to
+ * mirror0 / mirror1 (or NULL) at off + i0 s0 + i1 s1 + i2 s2: the kernel-layout copies of the weight. */
+#define LD_MC_ADAM_MAX 8
+typedef struct ld_mc_adam_tensor {
+  float* param;
+  const float* grad;
+  float* m;
+  float* v;
+  int32_t d0, d1, d2;
+  int64_t gs0, gs1, gs2;
+  float* mirror0;
+  int64_t m0_off, m0_s0, m0_s1, m0_s2;
+  float* mirror1;
+  int64_t m1_off, m1_s0, m1_s1, m1_s2;
+} ld_mc_adam_tensor;
+int ld_mc_adam(const ld_mc_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
+               double bc2_sqrt, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -31,7 +31,8 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "SegTrainer", "PatchCore", "PatchCoreClassifier", "coreset", "configure_runtime"]
+           "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "coreset",
+           "configure_runtime"]
 
 
 def __getattr__(name):
@@ -56,4 +57,10 @@ def __getattr__(name):
     if name == "PatchCoreClassifier":
         from .classifier import PatchCoreClassifier
         return PatchCoreClassifier
+    if name == "MnistClassifier":
+        from .mnistcls import MnistClassifier
+        return MnistClassifier
+    if name == "MnistClassifierTrainer":
+        from .mnistcls import MnistClassifierTrainer
+        return MnistClassifierTrainer
     raise AttributeError(name)

@@ -75,6 +75,12 @@ class ClfResizeArgs(C.Structure):
                 ("std", f32 * 3), ("pred", vp), ("threshold", f32), ("decision", vp), ("n_decision", i32)]
 
 
+class McAdamTensor(C.Structure):
+    _fields_ = [("param", vp), ("grad", vp), ("m", vp), ("v", vp), ("d0", i32), ("d1", i32), ("d2", i32), ("gs0", i64),
+                ("gs1", i64), ("gs2", i64), ("mirror0", vp), ("m0_off", i64), ("m0_s0", i64), ("m0_s1", i64), ("m0_s2", i64),
+                ("mirror1", vp), ("m1_off", i64), ("m1_s0", i64), ("m1_s1", i64), ("m1_s2", i64)]
+
+
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
 _SIGS = {
     "ld_last_error": (C.c_char_p, []),
@@ -189,6 +195,16 @@ _SIGS = {
     "ld_clf_max": (C.c_int, [vp, C.c_int, i64, vp, vp]),
     "ld_clf_resize": (C.c_int, [C.POINTER(ClfResizeArgs), vp]),
     "ld_clf_decide": (C.c_int, [vp, f32, vp, C.c_int, vp]),
+    "ld_mc_conv1": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ld_mc_pool": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_mc_pool_backward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_mc_gemm": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, i64, C.c_int, vp]),
+    "ld_mc_fc1_finish": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_mc_head": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ld_mc_small_grads": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ld_mc_conv1_wgrad_work_floats": (i64, [C.c_int]),
+    "ld_mc_conv1_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ld_mc_adam": (C.c_int, [C.POINTER(McAdamTensor), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -114,6 +114,27 @@ def load_seg_checkpoint(path_or_dict, seg, trust_pickle=False):
     return {"n_tensors": len(sd)}
 
 
+def load_mnist_classifier(path_or_dict, model, trust_pickle=False):
+    """Load the digit classifier's weights into ``model`` (a ``MnistClassifier``): a bare ``state_dict`` as
+    ``train_mnist_cls.py:116`` saves it (``torch.save(model.state_dict(), path)``) and as ``MnistClassifierTrainer.fit``
+    writes it.  Same restricted unpickler as ``load_reference_checkpoint``; names and shapes must match exactly
+    (RuntimeError otherwise).  Returns {'n_tensors'}."""
+    data = _read(path_or_dict, trust_pickle)
+    if not isinstance(data, dict):
+        raise RuntimeError(f"digit classifier checkpoint: expected a state_dict, got {type(data).__name__}")
+    sd = {k[7:] if k.startswith("module.") else k: v for k, v in data.items()}     # (an nn.DataParallel wrapper's prefix)
+    own = model.state_dict()
+    bad = [k for k in sd if k in own and tuple(sd[k].shape) != tuple(own[k].shape)]
+    if bad:
+        raise RuntimeError(f"checkpoint tensors with the wrong shape: {bad[:5]}")
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    if missing or unexpected:
+        raise RuntimeError(f"checkpoint does not match the model: missing {missing[:5]} unexpected {unexpected[:5]}")
+    model.load_state_dict({k: torch.as_tensor(v).to(own[k].dtype) for k, v in sd.items()})
+    return {"n_tensors": len(sd)}
+
+
 _PC_PREFIXES = ("feature_extractor.feature_extractor.", "feature_extractor.", "module.")
 
 

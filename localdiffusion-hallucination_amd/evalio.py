@@ -91,6 +91,27 @@ def seg_ood_mask(seg, lr, mean_t1, std_t1, translate_zero=True):
     return binary, binary
 
 
+def digit_report(classifier, images, labels, batch_size=512):
+    """The MNIST experiment's read-out: which digit does ``classifier`` (a ``MnistClassifier``) see in each image?
+    ``images`` [N, 1, 28, 28] (or [N, 28, 28]) in the dataset's range [0, 2] -- HR images or the sampler's output for
+    ``min_max_val = (0, 2)`` -- as a tensor or numpy array, ``labels`` [N] the true digits.  Returns
+    {'pred': int64 [N], 'accuracy': float, 'confusion': int64 [10, 10] with rows = true digit, columns = predicted}."""
+    x = torch.as_tensor(np.asarray(images) if not torch.is_tensor(images) else images).to(torch.float32)
+    if x.dim() == 3:
+        x = x[:, None]
+    y = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).astype(np.int64).reshape(-1)
+    if x.dim() != 4 or x.shape[0] != y.shape[0]:
+        raise ValueError(f"digit_report: images {tuple(x.shape)} for {y.shape[0]} labels")
+    if y.size and (y.min() < 0 or y.max() > 9):
+        raise ValueError("digit_report: label outside 0..9")
+    dev = next(classifier.parameters()).device
+    preds = [classifier.predict(x[i:i + batch_size].to(dev))[0] for i in range(0, x.shape[0], batch_size)]
+    pred = torch.cat(preds).cpu().numpy() if preds else np.zeros(0, np.int64)
+    confusion = np.zeros((10, 10), np.int64)
+    np.add.at(confusion, (y, pred), 1)
+    return {"pred": pred, "accuracy": float((pred == y).mean()) if y.size else float("nan"), "confusion": confusion}
+
+
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 PATCHCORE_RULES = {"8to3": "mnist", "8to5": "mnist", "t12flair": "mri", "flair2t1": "mri", "transistor": "mvtec",
                    "toothbrush": "mvtec", "grid": "mvtec"}

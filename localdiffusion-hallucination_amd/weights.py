@@ -294,6 +294,26 @@ def procedural_seg_state_dict(seed=0, bn_stats=None, n_channels=1, n_classes=1):
     return out
 
 
+# ----------------------------------------------------------------------------- MNIST digit classifier (SimpleCNN)
+def mnistcls_param_shapes() -> "OrderedDict[str, tuple]":
+    """name -> shape of ``SimpleCNN().state_dict()`` (train_mnist_cls.py:31-47) in its order."""
+    return OrderedDict([("conv1.weight", (32, 1, 3, 3)), ("conv1.bias", (32,)), ("conv2.weight", (64, 32, 3, 3)),
+                        ("conv2.bias", (64,)), ("fc1.weight", (128, 64 * 7 * 7)), ("fc1.bias", (128,)),
+                        ("fc2.weight", (10, 128)), ("fc2.bias", (10,))])
+
+
+def procedural_mnistcls_state_dict(seed=0):
+    """Name-keyed procedural weights of the digit classifier (numpy fp32): uniform(+-1/sqrt(fan_in)) for weights and
+    biases alike, PyTorch's default bounds for ``nn.Conv2d`` / ``nn.Linear``, without any torch RNG."""
+    shapes = mnistcls_param_shapes()
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        wshape = shapes[name[:-len(".bias")] + ".weight"] if name.endswith(".bias") else shape
+        u = procedural_tensor("mnistcls." + name, shape, seed)
+        out[name] = np.ascontiguousarray(u / np.sqrt(_fan_in(wshape)), dtype=np.float32)
+    return out
+
+
 # ----------------------------------------------------------------------------- PatchCore backbone (wide_resnet50_2)
 PC_STAGES = (("layer1", 3, 128, 256, 1), ("layer2", 4, 256, 512, 2), ("layer3", 6, 512, 1024, 2))  # blocks, width, out, stride
 
