@@ -735,6 +735,48 @@ typedef struct ld_mc_adam_tensor {
 int ld_mc_adam(const ld_mc_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
                double bc2_sqrt, void* stream);
 
+/* ---- training the denoiser, first slice (backward half): csrc/denoiser_grad.hip ----------------------------
+ * The gradient of the training loss with respect to the denoiser's output, and the pieces of a trainable ResnetBlock
+ * (ddpm.py:170-212) that are not convolutions.  fp32, activations NHWC with a pixel stride ldc >= C: channels C..ldc-1
+ * are padding, never read into a statistic or a gradient and written as zeros (what lets ld_pc_conv / ld_seg_wgrad serve
+ * a channel count that is a multiple of 32 only).  Every reduction adds in a fixed order with fp64 partial sums (no
+ * floating-point atomics); nothing allocates. */
+/* Backward of ld_p_losses followed by the batch mean (ddpm.py:1201): d_model_out[b, i] = g * 2 * loss_weight[t_b] *
+ * (model_out[b, i] - target[b, i]) / (B * elems_per_sample), target as in ld_p_losses; g = the upstream scalar. */
+int ld_p_losses_grad(const float* model_out, const float* x_start, const float* noise, const int* t, const float* sqrt_ab,
+                     const float* sqrt_1mab, const float* loss_weight, float g, float* d_model_out, int B,
+                     int64_t elems_per_sample, int objective, void* stream);
+/* Bytes of the `work` scratch of the two entry points below (0 for a shape they refuse). */
+int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C);
+/* GroupNorm (training mode: statistics of this batch) -> FiLM -> SiLU over y [B, H, W, ldc] (a convolution output, bias
+ * added): stat [B][groups][2] = (mean, 1 / sqrt(biased var + 1e-5)), out = silu(((y - mean) rstd gamma + beta) (1 + s) +
+ * sh) + residual, (s, sh) the halves of film [B][2 C].  film NULL: s = sh = 0; residual ([B, H, W, ldc]) NULL: none; out
+ * may be residual.  C a multiple of 4 * groups, ldc a multiple of 4, pointers 16-byte aligned. */
+int ld_dn_gn_forward(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
+                     double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups, void* stream);
+/* Its backward from dout (the gradient of silu(a)), the saved y and stat; a is recomputed.  dgamma, dbeta [C], dfilm
+ * [B][2 C] (NULL exactly when film is), dy [B, H, W, ldc] (may be dout).  One reduction pass over dout and y, a
+ * finalisation, one elementwise pass. */
+int ld_dn_gn_backward(const float* dout, const float* y, const float* stat, const float* gamma, const float* beta,
+                      const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B, int H,
+                      int W, int C, int ldc, int groups, void* stream);
+/* out [C] = the sum of x [B, H, W, ldc] over batch and pixels, channels 0..C-1 (the bias gradient of a convolution from
+ * the gradient of its output; ld_seg_colsum's sibling with a pixel stride, B x runs workgroups per 256 channels instead
+ * of one column of workgroups per 64).  work: ld_dn_gn_work_bytes(B, H, W, C) bytes.  C, ldc multiples of 4. */
+int ld_dn_colsum(const float* x, double* work, float* out, int B, int H, int W, int C, int ldc, void* stream);
+/* The time projection of a ResnetBlock (ddpm.py:192-195): film [B][N] = silu(temb [B][T]) w[N][T]^T + bias, and its
+ * backward: dw = dfilm^T silu(temb), db = sum_b dfilm, dtemb = (dfilm w) * silu'(temb). */
+int ld_dn_time_proj(const float* temb, const float* w, const float* bias, float* film, int B, int T, int N, void* stream);
+int ld_dn_time_proj_backward(const float* dfilm, const float* temb, const float* w, float* dw, float* db, float* dtemb, int B,
+                             int T, int N, void* stream);
+/* out [B, H, W, ldc] (channels C..ldc-1 zero) from a tensor [B, C, H, W] with strides (sb, sc, sh, sw) in floats. */
+int ld_dn_pack_nhwc(const float* x, float* out, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                    int ldc, void* stream);
+/* out [d0][d1][d2] (contiguous) = in[off + i0 s0 + i1 s1 + i2 s2]: the inverse of ld_seg_permute3 (a padded OHWI weight
+ * gradient back to the parameter's OIHW). */
+int ld_dn_gather3(const float* in, float* out, int d0, int d1, int d2, int64_t off, int64_t s0, int64_t s1, int64_t s2,
+                  void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

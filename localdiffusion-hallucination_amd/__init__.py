@@ -31,8 +31,8 @@ from .tuning import Tuning  # noqa: F401,E402
 from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
-           "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "coreset",
-           "configure_runtime"]
+           "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
+           "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -63,4 +63,7 @@ def __getattr__(name):
     if name == "MnistClassifierTrainer":
         from .mnistcls import MnistClassifierTrainer
         return MnistClassifierTrainer
+    if name == "ResnetBlock":
+        from .resblock import ResnetBlock
+        return ResnetBlock
     raise AttributeError(name)

@@ -205,6 +205,16 @@ _SIGS = {
     "ld_mc_conv1_wgrad_work_floats": (i64, [C.c_int]),
     "ld_mc_conv1_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ld_mc_adam": (C.c_int, [C.POINTER(McAdamTensor), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "ld_p_losses_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, vp, C.c_int, i64, C.c_int, vp]),
+    "ld_dn_gn_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ld_dn_gn_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_gn_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, vp]),
+    "ld_dn_colsum": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_time_proj": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_time_proj_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_pack_nhwc": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, C.c_int, vp]),
+    "ld_dn_gather3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -699,7 +699,9 @@ class GaussianDiffusion(nn.Module):
         timesteps ``t``, one denoiser evaluation, the objective's target, the per-sample mean squared error times
         ``loss_weight[t]``, the batch mean.  ``noise`` None: draws from the run's noise stream in the reference's order
         (noise, then the [B,C] offset noise when its strength is positive, :1165-1167).  Returns the scalar loss
-        (and the per-sample losses with ``per_sample=True``).  Backward / optimiser are out of scope."""
+        (and the per-sample losses with ``per_sample=True``).  No backward pass runs here: ``p_losses_grad`` gives the gradient
+        of this loss with respect to the denoiser's output, ``ResnetBlock`` is the first trainable piece of the denoiser;
+        the backward of the whole ``Unet`` and the optimiser are not built yet."""
         assert not self.self_condition
         lib, st, dev = cabi.lib(), self._st(), self.device
         x0 = x_start.to(dev, torch.float32).contiguous()
@@ -725,6 +727,26 @@ class GaussianDiffusion(nn.Module):
                    "p_losses")
         total = loss.mean()
         return (total, loss) if per_sample else total
+
+    @torch.no_grad()
+    def p_losses_grad(self, model_out, x_start, noise, t, grad_output=1.0):
+        """d loss / d ``model_out`` for the loss ``p_losses`` returns (the batch mean of ``loss_weight[t]`` times the
+        per-sample mean squared error against the objective's target, ddpm.py:1186-1201), all three objectives;
+        ``grad_output`` is the upstream scalar.  ``model_out``, ``x_start``, ``noise``: [B, ...] of one shape, ``t`` [B]."""
+        dev = self.device
+        mo = model_out.detach().to(dev, torch.float32).contiguous()
+        x0 = x_start.to(dev, torch.float32).contiguous()
+        nz = noise.to(dev, torch.float32).contiguous()
+        if mo.shape != x0.shape or mo.shape != nz.shape or t.shape != (mo.shape[0],):
+            raise ValueError(f"p_losses_grad: model_out {tuple(mo.shape)}, x_start {tuple(x0.shape)}, noise {tuple(nz.shape)} "
+                             f"must agree and t must be [{mo.shape[0]}]")
+        t32 = t.to(dev, torch.int32).contiguous()
+        out = torch.empty_like(mo)
+        cabi.check(cabi.lib().ld_p_losses_grad(mo.data_ptr(), x0.data_ptr(), nz.data_ptr(), t32.data_ptr(),
+                                               self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                                               self.loss_weight.data_ptr(), float(grad_output), out.data_ptr(), mo.shape[0],
+                                               mo[0].numel(), cabi.OBJ[self.objective], self._st()), "p_losses_grad")
+        return out
 
     def forward(self, img, cond_img, train, *args, **kwargs):
         """ddpm.py:1203-1214: draws the timesteps with torch's generator as the reference does (``train=False`` re-seeds
