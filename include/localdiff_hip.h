@@ -777,6 +777,46 @@ int ld_dn_pack_nhwc(const float* x, float* out, int B, int C, int H, int W, int6
 int ld_dn_gather3(const float* in, float* out, int d0, int d1, int d2, int64_t off, int64_t s0, int64_t s1, int64_t s2,
                   void* stream);
 
+/* ---- training the denoiser, second slice: csrc/linattn_grad.hip ------------------------------------------------------------
+ * What a trainable LinearAttention (ddpm.py:214-251) needs besides its two 1x1 convolutions: RMSNorm (ddpm.py:126-132) and
+ * the attention core, each with its backward.  fp32, the layout above: activations NHWC with a pixel stride, the padding
+ * never read into a sum and written as zeros.  qkv is [B, H, W, ld3] with q at channel 0, k at hidden = 32 heads, v at
+ * 2 hidden, a head's 32 channels contiguous at 32 head inside each; the attention output and its gradient are [B, H, W,
+ * ldo].  Every sum over pixels is added in a fixed order (fp64 across tiles of 64 pixels, parts and samples), the number
+ * of parts depends on the shape alone, there are no floating-point atomics and nothing allocates.  Every activation
+ * pointer is 16-byte aligned; C, ldc, ld3, ldo are multiples of 4. */
+/* Bytes of ld_dn_rms_backward's `work` (0 for a shape it refuses). */
+int64_t ld_dn_rms_work_bytes(int B, int H, int W, int C);
+/* out [B, H, W, ldc] = x r g[c] sqrt(C) with r = 1 / max(|x_p|_2, 1e-12) over the C real channels of pixel p (an all-zero
+ * pixel gives zeros); rinv [B H W] = r, what the backward wants (NULL: not stored). */
+int ld_dn_rms_forward(const float* x, const float* g, float* rinv, float* out, int B, int H, int W, int C, int ldc,
+                      void* stream);
+/* Its backward from dout, the saved x and rinv: with u = x r and e = dout g sqrt(C), dx = r (e - u sum_c u_c e_c) (may be
+ * dout) and dg [C] = sqrt(C) sum over batch and pixels of dout_c u_c.  A column-sum pass and its finalisation, then one
+ * element-wise pass. */
+int ld_dn_rms_backward(const float* dout, const float* x, const float* g, const float* rinv, double* work, float* dg, float* dx,
+                       int B, int H, int W, int C, int ldc, void* stream);
+/* Parts the pixel axis is cut into by the two reductions below (0 for a refused shape), and the bytes of their `work`. */
+int ld_dn_la_splits(int B, int heads, int H, int W);
+int64_t ld_dn_la_work_bytes(int B, int heads, int H, int W);
+/* The context of every (b, head): kstat [B, heads, 32, 2] = (m[d] = max_n k[d, n], Z[d] = sum_n exp(k[d, n] - m[d])) and
+ * ctx [B, heads, 32, 32], ctx[d][e] = sum_n exp(k[d, n] - m[d]) v[e, n] / Z[d].  Every part reduces under its own maximum;
+ * a second launch merges the parts in index order, rescaled to the common maximum. */
+int ld_dn_la_context(const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W, int heads, int ld3,
+                     void* stream);
+/* out[n][32 head + e] = 32^-0.5 sum_d ctx[d][e] softmax_d(q[:, n])[d]; channels 32 heads .. ldo-1 zero. */
+int ld_dn_la_out(const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The backward's one reduction over pixels, from dout = the gradient of ld_dn_la_out's out: dctx [B, heads, 32, 32],
+ * dctx[d][e] = 32^-0.5 sum_n softmax_d(q[:, n])[d] dout[e, n], and rk [B, heads, 32], rk[d] = sum_e dctx[d][e] ctx[d][e]
+ * (= sum_n ks[d, n] dks[d, n]: what the backward of the softmax over pixels needs). */
+int ld_dn_la_backward_reduce(const float* qkv, const float* dout, const float* ctx, double* work, float* dctx, float* rk, int B,
+                             int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The backward's element-wise pass: dqkv [B, H, W, ld3] (channels 96 heads .. ld3-1 zero) with, per pixel and head, p =
+ * softmax_d(q), ks = exp(k - m) / Z, dq[d] = 32^-0.5 p[d] (s[d] - sum_d' p[d'] s[d']) for s[d] = sum_e ctx[d][e] dout[e],
+ * dk[d] = ks[d] (sum_e dctx[d][e] v[e] - rk[d]), dv[e] = sum_d dctx[d][e] ks[d]. */
+int ld_dn_la_backward_apply(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
+                            const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

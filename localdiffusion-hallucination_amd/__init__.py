@@ -32,7 +32,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "coreset", "configure_runtime"]
+           "LinearAttention", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -66,4 +66,7 @@ def __getattr__(name):
     if name == "ResnetBlock":
         from .resblock import ResnetBlock
         return ResnetBlock
+    if name == "LinearAttention":
+        from .linattn_grad import LinearAttention
+        return LinearAttention
     raise AttributeError(name)

@@ -14,9 +14,9 @@ that is not a multiple of 64 is carried the way ``MnistClassifier`` carries conv
 pixel stride of the next multiple of 64 floats, the upper part zero, and the kernel-layout weights are zero there.  The
 GroupNorm kernels know the real channel count, so padding enters no statistic and no gradient.
 
-NOT covered (follow-ups that build on this module's layout): attention and its RMSNorm, Down/Upsample, the 7x7 stem, the
-ResUnet encoder, the time MLP in front of the blocks, any optimiser / EMA / ``Trainer``, 16-bit storage, and ``Unet``
-assembling the backward of its blocks.
+NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``): full
+attention, Down/Upsample, the 7x7 stem, the ResUnet encoder, the time MLP in front of the blocks, any optimiser / EMA /
+``Trainer``, 16-bit storage, and ``Unet`` assembling the backward of its blocks.
 """
 import ctypes as C
 
@@ -31,6 +31,32 @@ def _pad64(c):
 
 def _st(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+class _PackedWeights:
+    """Mixin of a trainable module: the cache of the kernel-layout copies of its weights (``_pack(dev)`` builds them)."""
+
+    _packed = None
+
+    def invalidate(self):
+        """Drop the kernel-layout copies of the weights; they are rebuilt on next use.  ``.to()``, ``load_state_dict`` and any
+        in-place change of a parameter (an optimiser step: its ``_version`` moves) do this by themselves."""
+        self._packed = None
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate()
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        self.invalidate()
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    def _packed_for(self, dev):
+        key = (dev,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._packed is None or self._packed[0] != key:
+            with torch.no_grad():
+                self._packed = (key, self._pack(dev))
+        return self._packed[1]
 
 
 class _Block(nn.Module):
@@ -222,7 +248,7 @@ class _ResnetBlockFn(torch.autograd.Function):
         return (None, None, dx, dtemb) + tuple(g.get(n) for n in ctx.names)
 
 
-class ResnetBlock(nn.Module):
+class ResnetBlock(_PackedWeights, nn.Module):
     """``ResnetBlock(dim, dim_out, time_emb_dim=None, groups=8)`` of ddpm.py:188-212, forward and backward in HIP (fp32).
 
     ``forward(x, time_emb=None)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is
@@ -245,28 +271,9 @@ class ResnetBlock(nn.Module):
         self.block2 = _Block(dim_out, dim_out, groups)
         self.has_res_conv = dim != dim_out
         self.res_conv = nn.Conv2d(dim, dim_out, 1) if self.has_res_conv else nn.Identity()
-        self._packed = None
 
-    # ------------------------------------------------------------------------------------------------ packed weights
-    def invalidate(self):
-        """Drop the kernel-layout copies of the weights; they are rebuilt on next use.  ``.to()``, ``load_state_dict`` and any
-        in-place change of a parameter (an optimiser step: its ``_version`` moves) do this by themselves."""
-        self._packed = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate()
-        return super()._apply(fn, *args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        self.invalidate()
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
-
-    def _packed_for(self, dev):
-        key = (dev,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed is None or self._packed[0] != key:
-            with torch.no_grad():
-                self._packed = (key, _Packed(self, dev))
-        return self._packed[1]
+    def _pack(self, dev):
+        return _Packed(self, dev)
 
     # ------------------------------------------------------------------------------------------------ forward
     def _check(self, x, time_emb):
