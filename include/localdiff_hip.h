@@ -817,6 +817,25 @@ int ld_dn_la_backward_reduce(const float* qkv, const float* dout, const float* c
 int ld_dn_la_backward_apply(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
                             const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
 
+/* ---- training the denoiser, third slice: csrc/attention_grad.hip ------------------------------------------------------------
+ * The core of a trainable full Attention (ddpm.py:253-282, attend.py's non-flash path): softmax(q k^T 32^-0.5) v per
+ * (sample, head), fp32 with exact fp32 products, on the layout above (qkv [B, H, W, ld3], out / dout [B, H, W, ldo]); q is
+ * not pre-scaled.  Nothing of size n x n (n = H W) is written to memory: the forward is an online softmax over tiles of 64
+ * keys, the backward recomputes the probabilities from qkv and lse.  Every sum is added in a fixed order, there are no
+ * atomics and nothing allocates; padded channels are never read, and written as zeros.  qkv, out, dout and dqkv are 16-byte
+ * aligned; ld3 >= 96 heads and ldo >= 32 heads are multiples of 4. */
+/* out[n][32 head + e] = sum_j softmax_j(q_n . k_j 32^-0.5) v_j[e], channels 32 heads .. ldo-1 zero; lse [B, heads, n] = the
+ * row's max + log of its normaliser, what the backward wants (NULL: not stored). */
+int ld_dn_fa_forward(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* Bytes of ld_dn_fa_backward's `work` (delta = rowsum(dout out), [B, heads, n] floats); 0 for a shape it refuses. */
+int64_t ld_dn_fa_work_bytes(int B, int heads, int H, int W);
+/* dqkv [B, H, W, ld3] (channels 96 heads .. ld3-1 zero) from dout = the gradient of ld_dn_fa_forward's out, with p_nj =
+ * exp(q_n . k_j 32^-0.5 - lse_n) and ds_nj = p_nj (dout_n . v_j - delta_n): dq_n = 32^-0.5 sum_j ds_nj k_j, dk_j = 32^-0.5
+ * sum_n ds_nj q_n, dv_j = sum_n p_nj dout_n.  A row pass (one workgroup per 64 queries: delta and dq) and a column pass
+ * (one per 64 keys: dk and dv). */
+int ld_dn_fa_backward(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
+                      int H, int W, int heads, int ld3, int ldo, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -32,7 +32,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "LinearAttention", "coreset", "configure_runtime"]
+           "LinearAttention", "Attention", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -69,4 +69,7 @@ def __getattr__(name):
     if name == "LinearAttention":
         from .linattn_grad import LinearAttention
         return LinearAttention
+    if name == "Attention":
+        from .attention_grad import Attention
+        return Attention
     raise AttributeError(name)

@@ -50,10 +50,11 @@ class _Packed:
             self.keep.append(w)
             return fwd, dgr
 
+        out = mod.to_out[0] if isinstance(mod.to_out, nn.Sequential) else mod.to_out      # (full Attention: a bare Conv2d)
         self.wqf, self.wqd = conv1(mod.to_qkv.weight, 3 * mod.hidden, mod.ld3, mod.dim, mod.cp)
-        self.wof, self.wod = conv1(mod.to_out[0].weight, mod.dim, mod.cp, mod.hidden, mod.hp)
+        self.wof, self.wod = conv1(out.weight, mod.dim, mod.cp, mod.hidden, mod.hp)
         self.bo = torch.zeros(mod.cp, **f32)
-        self.bo[:mod.dim].copy_(mod.to_out[0].bias.detach())
+        self.bo[:mod.dim].copy_(out.bias.detach())
         n = max(mod.cp, mod.hp, mod.ld3)
         self.ones, self.zeros = torch.ones(n, **f32), torch.zeros(n, **f32)
 

@@ -14,9 +14,9 @@ that is not a multiple of 64 is carried the way ``MnistClassifier`` carries conv
 pixel stride of the next multiple of 64 floats, the upper part zero, and the kernel-layout weights are zero there.  The
 GroupNorm kernels know the real channel count, so padding enters no statistic and no gradient.
 
-NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``): full
-attention, Down/Upsample, the 7x7 stem, the ResUnet encoder, the time MLP in front of the blocks, any optimiser / EMA /
-``Trainer``, 16-bit storage, and ``Unet`` assembling the backward of its blocks.
+NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``, full
+attention is in ``attention_grad.py``): Down/Upsample, the 7x7 stem, the ResUnet encoder, the time MLP in front of the
+blocks, any optimiser / EMA / ``Trainer``, 16-bit storage, and ``Unet`` assembling the backward of its blocks.
 """
 import ctypes as C
 
