@@ -14,49 +14,19 @@ that is not a multiple of 64 is carried the way ``MnistClassifier`` carries conv
 pixel stride of the next multiple of 64 floats, the upper part zero, and the kernel-layout weights are zero there.  The
 GroupNorm kernels know the real channel count, so padding enters no statistic and no gradient.
 
+This file holds what is the block's own: which weights it packs, the GroupNorm and time-projection launches, and the two
+launch sequences.  The layout helpers, the packed-weight cache, the launches every module uses, the ``autograd.Function`` and
+the input checks are ``trainable.py``'s, shared with the two attention modules.
+
 NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``, full
 attention is in ``attention_grad.py``): Down/Upsample, the 7x7 stem, the ResUnet encoder, the time MLP in front of the
 blocks, any optimiser / EMA / ``Trainer``, 16-bit storage, and ``Unet`` assembling the backward of its blocks.
 """
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _cabi as cabi
-
-def _pad64(c):
-    return (c + 63) // 64 * 64
-
-
-def _st(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-class _PackedWeights:
-    """Mixin of a trainable module: the cache of the kernel-layout copies of its weights (``_pack(dev)`` builds them)."""
-
-    _packed = None
-
-    def invalidate(self):
-        """Drop the kernel-layout copies of the weights; they are rebuilt on next use.  ``.to()``, ``load_state_dict`` and any
-        in-place change of a parameter (an optimiser step: its ``_version`` moves) do this by themselves."""
-        self._packed = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate()
-        return super()._apply(fn, *args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        self.invalidate()
-        return super().load_state_dict(state_dict, strict=strict, assign=assign)
-
-    def _packed_for(self, dev):
-        key = (dev,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed is None or self._packed[0] != key:
-            with torch.no_grad():
-                self._packed = (key, self._pack(dev))
-        return self._packed[1]
+from .trainable import Run, TrainableModule, ones_zeros, pack_conv, pack_vec, pad64, stream
 
 
 class _Block(nn.Module):
@@ -72,79 +42,28 @@ class _Packed:
     """Kernel-layout copies of one block's weights on one device (zero in the padded channels)."""
 
     def __init__(self, blk, dev):
-        lib, st = cabi.lib(), _st(dev)
+        lib, st = cabi.lib(), stream(dev)
         ci, co, cip, cop = blk.dim, blk.dim_out, blk.cip, blk.cop
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.keep = []
-
-        def conv(w, cin, cinp, k):
-            """OIHW [co, cin, k, k] -> forward layout [cop][k*k][cinp] and data-gradient layout [cinp][flipped k*k][cop]."""
-            w = w.detach().contiguous()
-            kk = k * k
-            fwd, dgr = torch.zeros(cop * kk * cinp, **f32), torch.zeros(cinp * kk * cop, **f32)
-            cabi.check(lib.ld_seg_permute3(w.data_ptr(), fwd.data_ptr(), co, cin, kk, 0, kk * cinp, 1, cinp, st), "permute3")
-            cabi.check(lib.ld_seg_permute3(w.data_ptr(), dgr.data_ptr(), co, cin, kk, (kk - 1) * cop, 1, kk * cop, -cop, st),
-                       "permute3")
-            self.keep.append(w)
-            return fwd, dgr
-
-        def vec(v, n, fill=0.0):
-            out = torch.full((n,), fill, **f32)
-            out[:v.numel()].copy_(v.detach())
-            return out
-
-        self.w1f, self.w1d = conv(blk.block1.proj.weight, ci, cip, 3)
-        self.w2f, self.w2d = conv(blk.block2.proj.weight, co, cop, 3)
-        self.b1, self.b2 = vec(blk.block1.proj.bias, cop), vec(blk.block2.proj.bias, cop)
-        self.g1, self.be1 = vec(blk.block1.norm.weight, co), vec(blk.block1.norm.bias, co)
-        self.g2, self.be2 = vec(blk.block2.norm.weight, co), vec(blk.block2.norm.bias, co)
+        self.w1f, self.w1d = pack_conv(lib, st, blk.block1.proj.weight, co, cop, ci, cip, 3)
+        self.w2f, self.w2d = pack_conv(lib, st, blk.block2.proj.weight, co, cop, co, cop, 3)
+        self.b1, self.b2 = pack_vec(blk.block1.proj.bias, cop), pack_vec(blk.block2.proj.bias, cop)
+        self.g1, self.be1 = pack_vec(blk.block1.norm.weight, co), pack_vec(blk.block1.norm.bias, co)
+        self.g2, self.be2 = pack_vec(blk.block2.norm.weight, co), pack_vec(blk.block2.norm.bias, co)
         self.wrf = self.wrd = self.br = None
         if blk.has_res_conv:
-            self.wrf, self.wrd = conv(blk.res_conv.weight, ci, cip, 1)
-            self.br = vec(blk.res_conv.bias, cop)
-        n = max(cip, cop)
-        self.ones, self.zeros = torch.ones(n, **f32), torch.zeros(n, **f32)
+            self.wrf, self.wrd = pack_conv(lib, st, blk.res_conv.weight, co, cop, ci, cip, 1)
+            self.br = pack_vec(blk.res_conv.bias, cop)
+        self.ones, self.zeros = ones_zeros(max(cip, cop), dev)
 
 
-class _Run:
+class _Run(Run):
     """The launches of one forward / backward of a block on one device."""
 
-    def __init__(self, blk, packed, dev, B, H, W):
-        self.blk, self.p, self.dev, self.B, self.H, self.W = blk, packed, dev, B, H, W
-        self.lib, self.st = cabi.lib(), _st(dev)
-        self.fill = blk.debug_fill
-
-    def empty(self, *shape, dtype=torch.float32):
-        t = torch.empty(*shape, dtype=dtype, device=self.dev)
-        if self.fill is not None:
-            t.fill_(self.fill)                  # (debug hook: nothing may depend on what a fresh buffer holds)
-        return t
-
-    def nhwc(self, t, c, cp):
-        """[B, c, H, W] of any strides -> NHWC with pixel stride cp; no copy when it already is that."""
-        B, H, W = self.B, self.H, self.W
-        if c == cp and t.stride() == (H * W * c, 1, W * c, c) and t.data_ptr() % 16 == 0:
-            return t
-        out = self.empty(B, H, W, cp)
-        sb, sc, sh, sw = t.stride()
-        cabi.check(self.lib.ld_dn_pack_nhwc(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st), "pack_nhwc")
-        return out
-
-    def conv(self, src, weight, shift, cin, cout, k, residual=None):
-        out = self.empty(self.B, self.H, self.W, cout)
-        a = cabi.PcConvArgs()
-        a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
-        a.residual, a.out = cabi.ptr(residual), out.data_ptr()
-        a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, self.H, self.W, cin, self.H, self.W, \
-            cout, k, 1, 0
-        cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
-        return out
-
     def gn_work(self):
-        return self.empty(int(self.lib.ld_dn_gn_work_bytes(self.B, self.H, self.W, self.blk.dim_out)) // 8, dtype=torch.float64)
+        return self.work(self.lib.ld_dn_gn_work_bytes(self.B, self.H, self.W, self.mod.dim_out))
 
     def gn_forward(self, y, gamma, beta, film, residual, out=None):
-        blk = self.blk
+        blk = self.mod
         stat = self.empty(self.B, blk.groups, 2)
         out = self.empty(self.B, self.H, self.W, blk.cop) if out is None else out
         cabi.check(self.lib.ld_dn_gn_forward(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), cabi.ptr(film), cabi.ptr(residual),
@@ -153,7 +72,7 @@ class _Run:
         return out, stat
 
     def gn_backward(self, dout, y, stat, gamma, beta, film, dy):
-        blk = self.blk
+        blk = self.mod
         dg, db = self.empty(blk.dim_out), self.empty(blk.dim_out)
         dfilm = None if film is None else self.empty(self.B, 2 * blk.dim_out)
         cabi.check(self.lib.ld_dn_gn_backward(dout.data_ptr(), y.data_ptr(), stat.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
@@ -162,24 +81,9 @@ class _Run:
                                               blk.groups, self.st), "dn_gn_backward")
         return dg, db, dfilm
 
-    def wgrad(self, dy, a, cin, cinp, k):
-        """The weight gradient in the parameter's OIHW and the bias gradient of a convolution with output gradient dy."""
-        blk, B, H, W = self.blk, self.B, self.H, self.W
-        co, cop, kk = blk.dim_out, blk.cop, k * k
-        splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cinp, cop, k))
-        work, dwp = self.empty(splits * cop * kk * cinp), self.empty(cop * kk * cinp)
-        cabi.check(self.lib.ld_seg_wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cinp, cop, k,
-                                         splits, self.st), "seg_wgrad")
-        dw = self.empty(co, cin, k, k)
-        cabi.check(self.lib.ld_dn_gather3(dwp.data_ptr(), dw.data_ptr(), co, cin, kk, 0, kk * cinp, 1, cinp, self.st), "gather3")
-        db = self.empty(co)
-        cabi.check(self.lib.ld_dn_colsum(dy.data_ptr(), self.gn_work().data_ptr(), db.data_ptr(), B, H, W, co, cop, self.st),
-                   "dn_colsum")
-        return dw, db
-
     # ------------------------------------------------------------------------------------------------ the two halves
-    def forward(self, x, temb):
-        blk, p, lib = self.blk, self.p, self.lib
+    def forward(self, x, temb, keep=True):              # (keep: the GroupNorm kernels always write their statistics)
+        blk, p, lib = self.mod, self.p, self.lib
         ci, co, cip, cop = blk.dim, blk.dim_out, blk.cip, blk.cop
         xp = self.nhwc(x, ci, cip)
         film = None
@@ -197,19 +101,19 @@ class _Run:
         return out, (xp, y1, y2, stat1, stat2, h1, film, temb)
 
     def backward(self, dout, saved):
-        blk, p, lib = self.blk, self.p, self.lib
+        blk, p, lib = self.mod, self.p, self.lib
         ci, co, cip, cop = blk.dim, blk.dim_out, blk.cip, blk.cop
         xp, y1, y2, stat1, stat2, h1, film, temb = saved
         g = {}
         dop = self.nhwc(dout, co, cop)
         dy2 = self.empty(self.B, self.H, self.W, cop)
         g["block2.norm.weight"], g["block2.norm.bias"], _ = self.gn_backward(dop, y2, stat2, p.g2, p.be2, None, dy2)
-        g["block2.proj.weight"], g["block2.proj.bias"] = self.wgrad(dy2, h1, co, cop, 3)
+        g["block2.proj.weight"], g["block2.proj.bias"] = self.wgrad(dy2, h1, co, cop, co, cop, 3), self.bias_grad(dy2, co, cop)
         dy1 = self.conv(dy2, p.w2d, p.zeros, cop, cop, 3)                 # = d h1, then d y1 in place
         g["block1.norm.weight"], g["block1.norm.bias"], dfilm = self.gn_backward(dy1, y1, stat1, p.g1, p.be1, film, dy1)
-        g["block1.proj.weight"], g["block1.proj.bias"] = self.wgrad(dy1, xp, ci, cip, 3)
+        g["block1.proj.weight"], g["block1.proj.bias"] = self.wgrad(dy1, xp, co, cop, ci, cip, 3), self.bias_grad(dy1, co, cop)
         if blk.has_res_conv:
-            g["res_conv.weight"], g["res_conv.bias"] = self.wgrad(dop, xp, ci, cip, 1)
+            g["res_conv.weight"], g["res_conv.bias"] = self.wgrad(dop, xp, co, cop, ci, cip, 1), self.bias_grad(dop, co, cop)
             dskip = self.conv(dop, p.wrd, p.zeros, cop, cip, 1)
         else:
             dskip = dop
@@ -222,33 +126,10 @@ class _Run:
             cabi.check(lib.ld_dn_time_proj_backward(dfilm.data_ptr(), temb.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                                     dtemb.data_ptr(), self.B, T, 2 * co, self.st), "dn_time_proj_backward")
             g["mlp.1.weight"], g["mlp.1.bias"] = dw, db
-        return dxp[..., :ci].permute(0, 3, 1, 2), dtemb, g
+        return dxp[..., :ci].permute(0, 3, 1, 2), (dtemb,), g
 
 
-class _ResnetBlockFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, blk, names, x, temb, *params):
-        with torch.cuda.device(x.device):
-            run = _Run(blk, blk._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])
-            out, saved = run.forward(x, temb)
-        ctx.run, ctx.names, ctx.has_temb = run, names, temb is not None
-        ctx.save_for_backward(*[t for t in saved if t is not None])
-        ctx.present = [t is not None for t in saved]
-        return out[..., :blk.dim_out].permute(0, 3, 1, 2)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout):
-        it = iter(ctx.saved_tensors)
-        saved = tuple(next(it) if have else None for have in ctx.present)
-        run = ctx.run
-        with torch.cuda.device(run.dev):
-            run.st = _st(run.dev)
-            dx, dtemb, g = run.backward(dout, saved)
-        return (None, None, dx, dtemb) + tuple(g.get(n) for n in ctx.names)
-
-
-class ResnetBlock(_PackedWeights, nn.Module):
+class ResnetBlock(TrainableModule):
     """``ResnetBlock(dim, dim_out, time_emb_dim=None, groups=8)`` of ddpm.py:188-212, forward and backward in HIP (fp32).
 
     ``forward(x, time_emb=None)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is
@@ -256,7 +137,7 @@ class ResnetBlock(_PackedWeights, nn.Module):
     kernels' NHWC output).  ``dim`` and ``dim_out`` are multiples of 32, ``groups`` divides ``dim_out`` with ``dim_out /
     groups`` a multiple of 4; any H, W >= 1."""
 
-    debug_fill = None       # a float: every buffer the module allocates is filled with it first (tests: NaN)
+    Run = _Run
 
     def __init__(self, dim, dim_out, *, time_emb_dim=None, groups=8):
         super().__init__()
@@ -265,7 +146,7 @@ class ResnetBlock(_PackedWeights, nn.Module):
         if groups <= 0 or dim_out % groups or (dim_out // groups) % 4:
             raise ValueError(f"ResnetBlock: groups {groups} must divide dim_out {dim_out} with dim_out / groups a multiple of 4")
         self.dim, self.dim_out, self.groups, self.time_emb_dim = dim, dim_out, groups, time_emb_dim
-        self.cip, self.cop = _pad64(dim), _pad64(dim_out)
+        self.cip, self.cop = pad64(dim), pad64(dim_out)
         self.mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_emb_dim, dim_out * 2)) if time_emb_dim is not None else None
         self.block1 = _Block(dim, dim_out, groups)
         self.block2 = _Block(dim_out, dim_out, groups)
@@ -275,32 +156,13 @@ class ResnetBlock(_PackedWeights, nn.Module):
     def _pack(self, dev):
         return _Packed(self, dev)
 
-    # ------------------------------------------------------------------------------------------------ forward
-    def _check(self, x, time_emb):
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != self.dim or x.numel() == 0:
-            raise ValueError(f"ResnetBlock: x must be a non-empty [B, {self.dim}, H, W] tensor")
-        if x.dtype != torch.float32:
-            raise ValueError(f"ResnetBlock: x is {x.dtype}; only float32 is supported (no 16-bit storage in training)")
-        if not x.is_cuda:
-            raise ValueError("ResnetBlock: x is a CPU tensor; the block runs on HIP kernels only (there is no CPU path)")
+    def _check_extra(self, x, time_emb):
         if time_emb is not None:
             if self.mlp is None:
                 raise ValueError("ResnetBlock: time_emb given to a block built without time_emb_dim")
             if time_emb.dtype != torch.float32 or time_emb.device != x.device or \
                     tuple(time_emb.shape) != (x.shape[0], self.time_emb_dim):
                 raise ValueError(f"ResnetBlock: time_emb must be float32 [{x.shape[0]}, {self.time_emb_dim}] on {x.device}")
-        for n, p in self.named_parameters():
-            if p.device != x.device or p.dtype != torch.float32:
-                raise ValueError(f"ResnetBlock: parameter {n} is {p.dtype} on {p.device}, x is float32 on {x.device}")
 
     def forward(self, x, time_emb=None):
-        self._check(x, time_emb)
-        names, params = zip(*self.named_parameters())
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params) or
-                                                  (time_emb is not None and time_emb.requires_grad))
-        if needs_grad:
-            return _ResnetBlockFn.apply(self, names, x, time_emb, *params)
-        with torch.no_grad(), torch.cuda.device(x.device):
-            run = _Run(self, self._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])
-            out, _ = run.forward(x.detach(), None if time_emb is None else time_emb.detach())
-        return out[..., :self.dim_out].permute(0, 3, 1, 2)
+        return super().forward(x, time_emb)

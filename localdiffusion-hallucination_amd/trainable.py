@@ -1,0 +1,200 @@
+"""What the trainable pieces of the denoiser share: ``ResnetBlock`` (``resblock.py``), ``LinearAttention``
+(``linattn_grad.py``) and ``Attention`` (``attention_grad.py``) are each a ``TrainableModule`` with a ``Run`` of their own.
+
+The common layout: activations are fp32 NHWC with a pixel stride of ``pad64(channels)`` floats, the upper part zero; the
+kernel-layout copies of the weights (``pack_conv``, ``pack_vec``) are zero there too and are cached per device, keyed on every
+parameter's ``data_ptr`` and ``_version`` (``PackedWeights``).  A module's forward and backward are the two halves of one
+``autograd.Function``; each half is a sequence of launches that the module's ``Run`` subclass writes down, out of the launches
+every module uses (``Run``: buffers, the NHWC repack, ``ld_pc_conv``, the weight and bias gradients) and its own.
+"""
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import _cabi as cabi
+
+
+def pad64(c):
+    return (c + 63) // 64 * 64
+
+
+def stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class PackedWeights:
+    """Mixin of a trainable module: the cache of the kernel-layout copies of its weights (``_pack(dev)`` builds them)."""
+
+    _packed = None
+
+    def invalidate(self):
+        """Drop the kernel-layout copies of the weights; they are rebuilt on next use.  ``.to()``, ``load_state_dict`` and any
+        in-place change of a parameter (an optimiser step: its ``_version`` moves) do this by themselves."""
+        self._packed = None
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate()
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        self.invalidate()
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    def _packed_for(self, dev):
+        key = (dev,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._packed is None or self._packed[0] != key:
+            with torch.no_grad():
+                self._packed = (key, self._pack(dev))
+        return self._packed[1]
+
+
+# ---------------------------------------------------------------------------------------------------- packing
+def pack_conv(lib, st, w, co, cop, ci, cip, k):
+    """OIHW [co, ci, k, k] -> forward layout [cop][k*k][cip] and data-gradient layout [cip][flipped k*k][cop], zero in the
+    padded channels."""
+    w = w.detach().contiguous()
+    kk = k * k
+    fwd, dgr = w.new_zeros(cop * kk * cip), w.new_zeros(cip * kk * cop)
+    cabi.check(lib.ld_seg_permute3(w.data_ptr(), fwd.data_ptr(), co, ci, kk, 0, kk * cip, 1, cip, st), "permute3")
+    cabi.check(lib.ld_seg_permute3(w.data_ptr(), dgr.data_ptr(), co, ci, kk, (kk - 1) * cop, 1, kk * cop, -cop, st), "permute3")
+    return fwd, dgr
+
+
+def pack_vec(v, n):
+    """A bias or gain as n floats, zero behind its own."""
+    out = v.new_zeros(n)
+    out[:v.numel()].copy_(v.detach())
+    return out
+
+
+def ones_zeros(n, dev):
+    """``ld_pc_conv``'s unit scale and the shift of a convolution without bias."""
+    return torch.ones(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------- launches
+class Run:
+    """The launches of one forward / backward of a module on one device: here the ones every module uses.  A subclass adds
+    its own and the two halves: ``forward(x, *extra, keep=True)`` returns the padded NHWC output and the tensors (or
+    ``None``) to save, ``keep=False`` leaves out what only the backward reads; ``backward(dout, saved)`` returns dx, the
+    gradients of the extra inputs and ``{parameter name: gradient}``.  ``packed`` has ``ones`` and ``zeros``."""
+
+    def __init__(self, mod, packed, dev, B, H, W):
+        self.mod, self.p, self.dev, self.B, self.H, self.W = mod, packed, dev, B, H, W
+        self.lib, self.st = cabi.lib(), stream(dev)
+        self.fill = mod.debug_fill
+
+    def empty(self, *shape, dtype=torch.float32):
+        t = torch.empty(*shape, dtype=dtype, device=self.dev)
+        if self.fill is not None:
+            t.fill_(self.fill)                  # (debug hook: nothing may depend on what a fresh buffer holds)
+        return t
+
+    def work(self, nbytes):
+        return self.empty(max(int(nbytes), 8) // 8, dtype=torch.float64)
+
+    def nhwc(self, t, c, cp):
+        """[B, c, H, W] of any strides -> NHWC with pixel stride cp; no copy when it already is that."""
+        B, H, W = self.B, self.H, self.W
+        if c == cp and t.stride() == (H * W * c, 1, W * c, c) and t.data_ptr() % 16 == 0:
+            return t
+        out = self.empty(B, H, W, cp)
+        sb, sc, sh, sw = t.stride()
+        cabi.check(self.lib.ld_dn_pack_nhwc(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st), "pack_nhwc")
+        return out
+
+    def conv(self, src, weight, shift, cin, cout, k, residual=None):
+        out = self.empty(self.B, self.H, self.W, cout)
+        a = cabi.PcConvArgs()
+        a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
+        a.residual, a.out = cabi.ptr(residual), out.data_ptr()
+        a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, self.H, self.W, cin, self.H, self.W, \
+            cout, k, 1, 0
+        cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
+        return out
+
+    def wgrad(self, dy, a, co, cop, ci, cip, k):
+        """The weight gradient, in the parameter's OIHW [co, ci, k, k], of a convolution from its output gradient dy [.., cop]
+        and its input a [.., cip]."""
+        B, H, W = self.B, self.H, self.W
+        kk = k * k
+        splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cip, cop, k))
+        work, dwp = self.empty(splits * cop * kk * cip), self.empty(cop * kk * cip)
+        cabi.check(self.lib.ld_seg_wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cip, cop, k,
+                                         splits, self.st), "seg_wgrad")
+        dw = self.empty(co, ci, k, k)
+        cabi.check(self.lib.ld_dn_gather3(dwp.data_ptr(), dw.data_ptr(), co, ci, kk, 0, kk * cip, 1, cip, self.st), "gather3")
+        return dw
+
+    def bias_grad(self, dy, c, cp):
+        """The bias gradient [c] of a convolution from its output gradient dy [.., cp]."""
+        B, H, W = self.B, self.H, self.W
+        db = self.empty(c)
+        work = self.work(self.lib.ld_dn_gn_work_bytes(B, H, W, c))
+        cabi.check(self.lib.ld_dn_colsum(dy.data_ptr(), work.data_ptr(), db.data_ptr(), B, H, W, c, cp, self.st), "dn_colsum")
+        return db
+
+
+class _Fn(torch.autograd.Function):
+    """A module's ``Run.forward`` and ``Run.backward`` as one node: ``apply(mod, names, x, *extra, *params)`` with one
+    parameter per name; ``extra`` are the further differentiable inputs (or ``None``)."""
+
+    @staticmethod
+    def forward(ctx, mod, names, x, *rest):
+        with torch.cuda.device(x.device):
+            run = mod._run(x)
+            out, saved = run.forward(x, *rest[:len(rest) - len(names)])
+        ctx.run, ctx.names = run, names
+        ctx.save_for_backward(*[t for t in saved if t is not None])
+        ctx.present = [t is not None for t in saved]
+        return out[..., :mod.dim_out].permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        it = iter(ctx.saved_tensors)
+        saved = tuple(next(it) if have else None for have in ctx.present)
+        run = ctx.run
+        with torch.cuda.device(run.dev):
+            run.st = stream(run.dev)
+            dx, d_extra, g = run.backward(dout, saved)
+        return (None, None, dx, *d_extra) + tuple(g.get(n) for n in ctx.names)
+
+
+class TrainableModule(PackedWeights, nn.Module):
+    """A module whose forward and backward are HIP launches (fp32).  A subclass sets ``dim`` and ``dim_out`` (the channels of
+    ``x`` and of the result) and ``Run`` (its ``Run`` subclass), and defines ``_pack(dev)``; ``forward(x, *extra)`` takes
+    ``x`` [B, dim, H, W] on the GPU and returns [B, dim_out, H, W], a ``channels_last``-strided view of the kernels' NHWC
+    output."""
+
+    debug_fill = None       # a float: every buffer the module allocates is filled with it first (tests: NaN)
+    Run = None
+
+    def _run(self, x):
+        return self.Run(self, self._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])
+
+    def _check_extra(self, x, *extra):
+        """A subclass with further inputs checks them here, against an ``x`` of the right shape and type."""
+
+    def _check(self, x, *extra):
+        name = type(self).__name__
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != self.dim or x.numel() == 0:
+            raise ValueError(f"{name}: x must be a non-empty [B, {self.dim}, H, W] tensor")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{name}: x is {x.dtype}; only float32 is supported (no 16-bit storage in training)")
+        self._check_extra(x, *extra)
+        if not x.is_cuda:
+            raise ValueError(f"{name}: x is a CPU tensor; the module runs on HIP kernels only (there is no CPU path)")
+        for n, p in self.named_parameters():
+            if p.device != x.device or p.dtype != torch.float32:
+                raise ValueError(f"{name}: parameter {n} is {p.dtype} on {p.device}, x is float32 on {x.device}")
+
+    def forward(self, x, *extra):
+        self._check(x, *extra)
+        names, params = zip(*self.named_parameters())
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *extra, *params)):
+            return _Fn.apply(self, names, x, *extra, *params)
+        with torch.no_grad(), torch.cuda.device(x.device):
+            out, _ = self._run(x).forward(x.detach(), *(None if t is None else t.detach() for t in extra), keep=False)
+        return out[..., :self.dim_out].permute(0, 3, 1, 2)

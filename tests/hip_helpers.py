@@ -9,6 +9,7 @@ from localdiffusion_hallucination_amd import _cabi as cabi
 from localdiffusion_hallucination_amd import rng
 
 DEV = "cuda"
+NAN = float("nan")
 TDT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 # max-abs tolerance relative to the reference tensor's max-abs, per storage dtype
 RTOL = {"fp32": 2e-5, "bf16": 3e-2, "fp16": 4e-3}      # 16-bit: ~8 half-ulps (2^-8 / 2^-11) of the largest value
@@ -16,6 +17,26 @@ RTOL = {"fp32": 2e-5, "bf16": 3e-2, "fp16": 4e-3}      # 16-bit: ~8 half-ulps (2
 
 def st():
     return torch.cuda.current_stream().cuda_stream
+
+
+def pad64(c):
+    return (c + 63) // 64 * 64
+
+
+def nans(*shape, dtype=torch.float32):
+    return torch.full(shape, NAN, dtype=dtype, device=DEV)
+
+
+def padded(x, ldc, fill=NAN):
+    """NCHW cpu -> NHWC device with pixel stride ldc; the padding holds ``fill`` (NaN: a kernel that reads it shows)."""
+    B, Cc, H, W = x.shape
+    out = torch.full((B, H, W, ldc), fill, dtype=torch.float32)
+    out[..., :Cc] = x.permute(0, 2, 3, 1)
+    return out.to(DEV)
+
+
+def unpadded(t, Cc):
+    return t[..., :Cc].permute(0, 3, 1, 2).contiguous().cpu()
 
 
 def rand(shape, key, lo=-1.0, hi=1.0):

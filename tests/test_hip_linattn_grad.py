@@ -16,34 +16,13 @@ import torch.nn.functional as F
 import localdiffusion_hallucination_amd as ldh
 from localdiffusion_hallucination_amd import _cabi as cabi
 
-from hip_helpers import DEV, RTOL, st
+from hip_helpers import DEV, NAN, RTOL, nans, pad64, padded, st, unpadded
 import linattn_ref as R
 import resblock_ref
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = torch.float32, torch.float64
-NAN = float("nan")
-
-
-def pad64(c):
-    return (c + 63) // 64 * 64
-
-
-def nans(*shape, dtype=F32):
-    return torch.full(shape, NAN, dtype=dtype, device=DEV)
-
-
-def padded(x, ldc):
-    """NCHW cpu -> NHWC device with pixel stride ldc; the padding holds NaN (a kernel that reads it shows)."""
-    B, Cc, H, W = x.shape
-    out = torch.full((B, H, W, ldc), NAN, dtype=F32)
-    out[..., :Cc] = x.permute(0, 2, 3, 1)
-    return out.to(DEV)
-
-
-def unpadded(t, Cc):
-    return t[..., :Cc].permute(0, 3, 1, 2).contiguous().cpu()
 
 
 def work(nbytes):

@@ -13,28 +13,15 @@ import localdiffusion_hallucination_amd as ldh
 from localdiffusion_hallucination_amd import _cabi as cabi
 from localdiffusion_hallucination_amd import weights
 
-from hip_helpers import DEV, RTOL, st
+from hip_helpers import DEV, NAN, RTOL, padded, st, unpadded
 import resblock_ref as R
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = torch.float32, torch.float64
-NAN = float("nan")
 
 
 # ------------------------------------------------------------------------------------------------ kernel wrappers
-def padded(x, ldc, fill=NAN):
-    """NCHW cpu -> NHWC device with pixel stride ldc; the padding holds ``fill`` (NaN: a kernel that reads it shows)."""
-    B, Cc, H, W = x.shape
-    out = torch.full((B, H, W, ldc), fill, dtype=F32)
-    out[..., :Cc] = x.permute(0, 2, 3, 1)
-    return out.to(DEV)
-
-
-def unpadded(t, Cc):
-    return t[..., :Cc].permute(0, 3, 1, 2).contiguous().cpu()
-
-
 def gn_work(B, H, W, Cc):
     n = int(cabi.lib().ld_dn_gn_work_bytes(B, H, W, Cc))
     assert n > 0

@@ -1,0 +1,150 @@
+"""What tools/bench_resblock_grad.py, bench_linattn_grad.py and bench_attention_grad.py share: the event timing, the
+per-launch split of one forward + backward over the library's entry points, the eager timing in both memory formats, and
+the runner that gives every case a child process of its own under a time limit."""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from localdiffusion_hallucination_amd import _cabi as cabi       # noqa: E402
+
+HBM_PEAK_GBS = 8000.0
+
+
+def time_ms(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    times = []
+    for _ in range(iters):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        times.append(ev[0].elapsed_time(ev[1]))
+    return float(np.median(times))
+
+
+class TimedLib:
+    """The library with the launches of every entry point attributed to a label; forward and backward are told apart by
+    ``phase``."""
+
+    def __init__(self, lib):
+        self._lib, self.calls, self.phase = lib, [], "forward"
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith(("ld_dn_", "ld_seg_", "ld_pc_conv")) or name.endswith(("_work_bytes", "_splits")):
+            return fn
+
+        def wrapped(*args):
+            label = name[3:]
+            if name == "ld_pc_conv":
+                label = "pc_conv (forward)" if self.phase == "forward" else "pc_conv (data gradient)"
+            if name == "ld_dn_pack_nhwc":
+                label = f"dn_pack_nhwc ({self.phase})"
+            n0 = self._lib.ld_timing_count()
+            rc = fn(*args)
+            self.calls.append((label, n0, self._lib.ld_timing_count()))
+            return rc
+        return wrapped
+
+
+def kernel_split(run):
+    """run(set_phase) does one forward + backward under the library's timing session; returns {label: [ms, launches]} and,
+    call by call in order, (label, [ms of each of its launches])."""
+    lib = cabi.lib()
+    timed = TimedLib(lib)
+    real = cabi.lib
+    cabi.check(lib.ld_timing_begin(4096), "timing_begin")
+    try:
+        cabi.lib = lambda: timed
+        run(lambda phase: setattr(timed, "phase", phase))
+        torch.cuda.synchronize()
+    finally:
+        cabi.lib = real
+        n = max(1, lib.ld_timing_count())
+        ms, cnt = (C.c_float * n)(), C.c_int()
+        rc = lib.ld_timing_end(ms, n, C.byref(cnt))
+    cabi.check(rc, "timing_end")
+    split, calls = {}, []
+    for label, a, b in timed.calls:
+        e = split.setdefault(label, [0.0, 0])
+        e[0] += float(sum(ms[a:b]))
+        e[1] += b - a
+        calls.append((label, [float(v) for v in ms[a:b]]))
+    return split, calls
+
+
+def eager_ms(mod, fn, x, extra, dout, iters, warmup):
+    """{"nchw": ms, "nhwc": ms} of forward + backward of ``fn(params, x, *extra)``, the module restated in eager PyTorch on
+    clones of its parameters, with x and dout in either memory format."""
+    p = {k: v.detach().clone().requires_grad_(True) for k, v in mod.state_dict().items()}
+    res = {}
+    for fmt, name in ((torch.contiguous_format, "nchw"), (torch.channels_last, "nhwc")):
+        ins = [x.detach().contiguous(memory_format=fmt)] + [e.detach().clone() for e in extra]
+        for t in ins:
+            t.requires_grad_(True)
+        de = dout.contiguous(memory_format=fmt)
+        leaves = list(p.values()) + ins
+
+        def step():
+            for v in leaves:
+                v.grad = None
+            fn(p, *ins).backward(de)
+
+        res[name] = time_ms(step, iters, warmup)
+    return res
+
+
+def print_split(split, kernels_ms):
+    for k, v in sorted(split.items(), key=lambda kv: -kv[1]["ms"]):
+        print(f"      {k:28s} {v['ms']:9.3f} ms  {100 * v['ms'] / kernels_ms:5.1f} %  ({v['launches']} launches)")
+
+
+def main(tool, cases, run_case, report, heads=False):
+    """The tool's command line.  ``run_case(dim, H, args)`` returns the case's JSON row and ``report(row)`` prints it.  Every
+    case runs in a child process (``tool --child``) under ``--timeout``; the first one that fails or runs out of time ends the
+    run, so that nothing more is started on the GPU after it."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    if heads:
+        ap.add_argument("--heads", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--cases", default=cases)
+    ap.add_argument("--timeout", type=float, default=300.0, help="seconds each case's process may take")
+    ap.add_argument("--no-eager", action="store_true")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    todo = [tuple(int(v) for v in c.split(":")) for c in a.cases.split(",")]
+    if a.child:
+        (dim, H), = todo
+        print("ROW " + json.dumps(run_case(dim, H, a)))
+        return 0
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup") if hasattr(a, k) for w in ("--" + k, str(getattr(a, k)))]
+    rows = []
+    for dim, H in todo:
+        cmd = [sys.executable, os.path.abspath(tool), "--child", "--cases", f"{dim}:{H}"] + passed_on + \
+            (["--no-eager"] if a.no_eager else [])
+        try:
+            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            print(f"dim {dim} @{H}^2: no result within {a.timeout:.0f} s; stopping here", file=sys.stderr)
+            break
+        row = [ln[4:] for ln in res.stdout.splitlines() if ln.startswith("ROW ")]
+        if res.returncode != 0 or not row:
+            print(f"dim {dim} @{H}^2: the case's process ended with status {res.returncode}; stopping here", file=sys.stderr)
+            break
+        rows.append(json.loads(row[0]))
+        report(rows[-1])
+        sys.stdout.flush()
+    print(json.dumps(rows))
+    return 0 if len(rows) == len(todo) else 1
