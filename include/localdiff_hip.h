@@ -836,6 +836,42 @@ int64_t ld_dn_fa_work_bytes(int B, int heads, int H, int W);
 int ld_dn_fa_backward(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
                       int H, int W, int heads, int ld3, int ldo, void* stream);
 
+/* ---- training the denoiser, fourth slice: csrc/resample_grad.hip -------------------------------------------------------------
+ * What the layers between the blocks need besides ld_pc_conv / ld_seg_wgrad / ld_dn_colsum: Downsample's rearrangement
+ * (ddpm.py:120-124) and Upsample's nearest x 2 (ddpm.py:114-118), each with its backward, the im2col of the 7 x 7 stem and
+ * the head (final_conv).  fp32, the layout above: activations NHWC with a pixel stride ldc >= C, the padding never read and
+ * written as zeros.  The layout kernels move 16 bytes per thread; nothing allocates, there are no atomics, every sum has one
+ * order.  Activation pointers are 16-byte aligned; C and ldc are multiples of 4 (the head: of 32), ldc <= 65,536, H and W
+ * <= 2^20 and B H W <= 2^36.  A refused call returns -1 before anything is launched. */
+/* out [B, H, W, 4 C] (no padding), channel (p1 2 + p2) C + c = x [B, 2 H, 2 W, ldc] at (2 h + p1, 2 w + p2, c): the
+ * reference's 'b c (h p1) (w p2) -> b (c p1 p2) h w' with the channel order (p1 p2 c), which the weight packing absorbs. */
+int ld_dn_space_to_depth(const float* x, float* out, int B, int H, int W, int C, int ldc, void* stream);
+/* Its inverse: dx [B, 2 H, 2 W, ldc] (channels C..ldc-1 zero) from g [B, H, W, 4 C]. */
+int ld_dn_depth_to_space(const float* g, float* dx, int B, int H, int W, int C, int ldc, void* stream);
+/* out [B, 2 H, 2 W, ldc] = x [B, H, W, ldc] at (h / 2, w / 2): F.interpolate(scale_factor=2, mode="nearest"). */
+int ld_dn_upsample2x(const float* x, float* out, int B, int H, int W, int C, int ldc, void* stream);
+/* Its backward: dx [B, H, W, ldc] = ((g[2h][2w] + g[2h][2w+1]) + g[2h+1][2w]) + g[2h+1][2w+1] from g [B, 2 H, 2 W, ldc],
+ * in fp32 and in that order. */
+int ld_dn_upsample2x_backward(const float* g, float* dx, int B, int H, int W, int C, int ldc, void* stream);
+/* out [B, H, W, ldk], column (ci 7 + ky) 7 + kx = x[b][ci][y + ky - 3][x + kx - 3], zero outside the image and in the
+ * columns from 49 Cin on: the 7 x 7 (padding 3) stem as a 1 x 1 convolution whose weight is the OIHW parameter as it lies
+ * in memory.  x is [B, Cin, H, W] with strides (sb, sc, sh, sw) in floats, Cin 1..4; ldk >= 49 Cin a multiple of 4. */
+int ld_dn_im2col(const float* x, float* out, int B, int Cin, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                 int ldk, void* stream);
+/* The head, Conv2d(C, O, 1) with O 1..8 and C <= 2048: out NCHW [B, O, H, W] = sum_c x [B, H, W, ldc] w [O][C] + bias [O] (fp32 sums:
+ * a lane's four channels per 32-channel chunk in chunk order, then the eight lanes of a pixel pairwise). */
+int ld_dn_head_forward(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int ldc,
+                       int O, void* stream);
+/* Parts the pixels are cut into by ld_dn_head_backward (0 for a refused shape; it depends on B H W alone), and the bytes
+ * of its `work`. */
+int ld_dn_head_splits(int B, int H, int W);
+int64_t ld_dn_head_work_bytes(int B, int H, int W, int C, int O);
+/* Its backward from dout NCHW [B, O, H, W]: dx [B, H, W, ldc] = sum_o dout w (o order; channels C..ldc-1 zero), dw [O][C] =
+ * sum over pixels of dout x and db [O] = sum of dout: fp64 sums per part, the parts added in index order by a second
+ * launch. */
+int ld_dn_head_backward(const float* dout, const float* x, const float* w, double* work, float* dw, float* db, float* dx,
+                        int B, int H, int W, int C, int ldc, int O, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

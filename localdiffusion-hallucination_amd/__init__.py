@@ -32,7 +32,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "LinearAttention", "Attention", "coreset", "configure_runtime"]
+           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "coreset", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -72,4 +72,7 @@ def __getattr__(name):
     if name == "Attention":
         from .attention_grad import Attention
         return Attention
+    if name in ("Downsample", "Upsample", "Conv2d"):
+        from . import resample
+        return getattr(resample, name)
     raise AttributeError(name)

@@ -227,6 +227,15 @@ _SIGS = {
     "ld_dn_fa_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_fa_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ld_dn_fa_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_space_to_depth": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_depth_to_space": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_upsample2x": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_upsample2x_backward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_im2col": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, C.c_int, vp]),
+    "ld_dn_head_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_head_splits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "ld_dn_head_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ld_dn_head_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -1,5 +1,6 @@
 """What the trainable pieces of the denoiser share: ``ResnetBlock`` (``resblock.py``), ``LinearAttention``
-(``linattn_grad.py``) and ``Attention`` (``attention_grad.py``) are each a ``TrainableModule`` with a ``Run`` of their own.
+(``linattn_grad.py``), ``Attention`` (``attention_grad.py``) and ``Downsample`` / ``Upsample`` / ``Conv2d`` (``resample.py``)
+are each a ``TrainableModule`` with a ``Run`` of their own.
 
 The common layout: activations are fp32 NHWC with a pixel stride of ``pad64(channels)`` floats, the upper part zero; the
 kernel-layout copies of the weights (``pack_conv``, ``pack_vec``) are zero there too and are cached per device, keyed on every
@@ -77,8 +78,9 @@ def ones_zeros(n, dev):
 class Run:
     """The launches of one forward / backward of a module on one device: here the ones every module uses.  A subclass adds
     its own and the two halves: ``forward(x, *extra, keep=True)`` returns the padded NHWC output and the tensors (or
-    ``None``) to save, ``keep=False`` leaves out what only the backward reads; ``backward(dout, saved)`` returns dx, the
-    gradients of the extra inputs and ``{parameter name: gradient}``.  ``packed`` has ``ones`` and ``zeros``."""
+    ``None``) to save, ``keep=False`` leaves out what only the backward reads; ``backward(dout, saved)`` returns dx (``None``:
+    the input has no gradient), the gradients of the extra inputs and ``{parameter name: gradient}``.  The launches take the
+    map size ``hw`` they work at, by default the run's own (H, W), which is x's.  ``packed`` has ``ones`` and ``zeros``."""
 
     def __init__(self, mod, packed, dev, B, H, W):
         self.mod, self.p, self.dev, self.B, self.H, self.W = mod, packed, dev, B, H, W
@@ -94,9 +96,13 @@ class Run:
     def work(self, nbytes):
         return self.empty(max(int(nbytes), 8) // 8, dtype=torch.float64)
 
-    def nhwc(self, t, c, cp):
+    def hw(self, hw):
+        """The map size of a launch: the run's own unless the caller names another (``hw = (H, W)``)."""
+        return (self.H, self.W) if hw is None else hw
+
+    def nhwc(self, t, c, cp, hw=None):
         """[B, c, H, W] of any strides -> NHWC with pixel stride cp; no copy when it already is that."""
-        B, H, W = self.B, self.H, self.W
+        B, (H, W) = self.B, self.hw(hw)
         if c == cp and t.stride() == (H * W * c, 1, W * c, c) and t.data_ptr() % 16 == 0:
             return t
         out = self.empty(B, H, W, cp)
@@ -104,32 +110,39 @@ class Run:
         cabi.check(self.lib.ld_dn_pack_nhwc(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st), "pack_nhwc")
         return out
 
-    def conv(self, src, weight, shift, cin, cout, k, residual=None):
-        out = self.empty(self.B, self.H, self.W, cout)
+    def conv(self, src, weight, shift, cin, cout, k, residual=None, hw=None):
+        H, W = self.hw(hw)
+        out = self.empty(self.B, H, W, cout)
         a = cabi.PcConvArgs()
         a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
         a.residual, a.out = cabi.ptr(residual), out.data_ptr()
-        a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, self.H, self.W, cin, self.H, self.W, \
-            cout, k, 1, 0
+        a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, H, W, cin, H, W, cout, k, 1, 0
         cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
         return out
 
-    def wgrad(self, dy, a, co, cop, ci, cip, k):
-        """The weight gradient, in the parameter's OIHW [co, ci, k, k], of a convolution from its output gradient dy [.., cop]
-        and its input a [.., cip]."""
-        B, H, W = self.B, self.H, self.W
+    def wgrad_packed(self, dy, a, cop, cip, k, hw=None):
+        """The weight gradient in the forward kernel layout [cop][k*k][cip] of a convolution from its output gradient dy
+        [.., cop] and its input a [.., cip]."""
+        B, (H, W) = self.B, self.hw(hw)
         kk = k * k
         splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cip, cop, k))
         work, dwp = self.empty(splits * cop * kk * cip), self.empty(cop * kk * cip)
         cabi.check(self.lib.ld_seg_wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cip, cop, k,
                                          splits, self.st), "seg_wgrad")
+        return dwp
+
+    def wgrad(self, dy, a, co, cop, ci, cip, k, hw=None):
+        """The weight gradient, in the parameter's OIHW [co, ci, k, k], of a convolution from its output gradient dy [.., cop]
+        and its input a [.., cip]."""
+        kk = k * k
+        dwp = self.wgrad_packed(dy, a, cop, cip, k, hw)
         dw = self.empty(co, ci, k, k)
         cabi.check(self.lib.ld_dn_gather3(dwp.data_ptr(), dw.data_ptr(), co, ci, kk, 0, kk * cip, 1, cip, self.st), "gather3")
         return dw
 
-    def bias_grad(self, dy, c, cp):
+    def bias_grad(self, dy, c, cp, hw=None):
         """The bias gradient [c] of a convolution from its output gradient dy [.., cp]."""
-        B, H, W = self.B, self.H, self.W
+        B, (H, W) = self.B, self.hw(hw)
         db = self.empty(c)
         work = self.work(self.lib.ld_dn_gn_work_bytes(B, H, W, c))
         cabi.check(self.lib.ld_dn_colsum(dy.data_ptr(), work.data_ptr(), db.data_ptr(), B, H, W, c, cp, self.st), "dn_colsum")
@@ -148,7 +161,7 @@ class _Fn(torch.autograd.Function):
         ctx.run, ctx.names = run, names
         ctx.save_for_backward(*[t for t in saved if t is not None])
         ctx.present = [t is not None for t in saved]
-        return out[..., :mod.dim_out].permute(0, 3, 1, 2)
+        return mod._view(out)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -174,6 +187,11 @@ class TrainableModule(PackedWeights, nn.Module):
     def _run(self, x):
         return self.Run(self, self._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])
 
+    def _view(self, out):
+        """What the module returns of its ``Run.forward``'s output: by default the real channels of the padded NHWC tensor
+        as [B, dim_out, H, W]; a module whose kernels write another layout (the head: NCHW) says so here."""
+        return out[..., :self.dim_out].permute(0, 3, 1, 2)
+
     def _check_extra(self, x, *extra):
         """A subclass with further inputs checks them here, against an ``x`` of the right shape and type."""
 
@@ -197,4 +215,4 @@ class TrainableModule(PackedWeights, nn.Module):
             return _Fn.apply(self, names, x, *extra, *params)
         with torch.no_grad(), torch.cuda.device(x.device):
             out, _ = self._run(x).forward(x.detach(), *(None if t is None else t.detach() for t in extra), keep=False)
-        return out[..., :self.dim_out].permute(0, 3, 1, 2)
+        return self._view(out)

@@ -110,9 +110,10 @@ def print_split(split, kernels_ms):
 
 
 def main(tool, cases, run_case, report, heads=False):
-    """The tool's command line.  ``run_case(dim, H, args)`` returns the case's JSON row and ``report(row)`` prints it.  Every
-    case runs in a child process (``tool --child``) under ``--timeout``; the first one that fails or runs out of time ends the
-    run, so that nothing more is started on the GPU after it."""
+    """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
+    returns the case's JSON row and ``report(row)`` prints it.  Every case runs in a child process (``tool --child``) under
+    ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is started on the GPU after
+    it."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     if heads:
@@ -124,24 +125,25 @@ def main(tool, cases, run_case, report, heads=False):
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    todo = [tuple(int(v) for v in c.split(":")) for c in a.cases.split(",")]
+    todo = [tuple(int(v) if v.isdigit() else v for v in c.split(":")) for c in a.cases.split(",")]
     if a.child:
-        (dim, H), = todo
-        print("ROW " + json.dumps(run_case(dim, H, a)))
+        (case,) = todo
+        print("ROW " + json.dumps(run_case(*case, a)))
         return 0
     passed_on = [w for k in ("batch", "heads", "iters", "warmup") if hasattr(a, k) for w in ("--" + k, str(getattr(a, k)))]
     rows = []
-    for dim, H in todo:
-        cmd = [sys.executable, os.path.abspath(tool), "--child", "--cases", f"{dim}:{H}"] + passed_on + \
+    for case in todo:
+        name = ":".join(str(v) for v in case)
+        cmd = [sys.executable, os.path.abspath(tool), "--child", "--cases", name] + passed_on + \
             (["--no-eager"] if a.no_eager else [])
         try:
             res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.timeout)
         except subprocess.TimeoutExpired:
-            print(f"dim {dim} @{H}^2: no result within {a.timeout:.0f} s; stopping here", file=sys.stderr)
+            print(f"case {name}: no result within {a.timeout:.0f} s; stopping here", file=sys.stderr)
             break
         row = [ln[4:] for ln in res.stdout.splitlines() if ln.startswith("ROW ")]
         if res.returncode != 0 or not row:
-            print(f"dim {dim} @{H}^2: the case's process ended with status {res.returncode}; stopping here", file=sys.stderr)
+            print(f"case {name}: the case's process ended with status {res.returncode}; stopping here", file=sys.stderr)
             break
         rows.append(json.loads(row[0]))
         report(rows[-1])
