@@ -872,6 +872,38 @@ int64_t ld_dn_head_work_bytes(int B, int H, int W, int C, int O);
 int ld_dn_head_backward(const float* dout, const float* x, const float* w, double* work, float* dw, float* db, float* dx,
                         int B, int H, int W, int C, int ldc, int O, void* stream);
 
+/* ---- training the denoiser, fifth slice: csrc/condenc_grad.hip ----------------------------------------------------------------
+ * What a trainable BasicBlock of the ResUnet condition encoder (unet_model.py:8-51) needs besides ld_pc_conv / ld_seg_wgrad /
+ * ld_dn_colsum / ld_seg_pool: GroupNorm in training mode at an even number of channels per group (16 groups of 2 at 32
+ * channels: a thread's four channels are two pairs, each in one group) followed by ReLU or nothing, of one tensor or of the
+ * sum of two normalised tensors, with its backward; and the im2col of a 3 x 3 convolution on an image.  fp32, the layout
+ * above: activations NHWC with a pixel stride ldc >= C, the padding never read into a statistic or a gradient and written as
+ * zeros (every output is a whole padded tensor).  Sums are fp64 per run of pixels, merged in index order; no atomics, nothing
+ * allocates.  Activation, gamma and beta pointers are 16-byte aligned, work 8-byte; C is a multiple of 4 and of 2 groups, C <=
+ * 2048, ldc <= 4096 a multiple of 4, B <= 32,767, H and W <= 2^20, B H W <= 2^36.  A refused call returns -1 before anything
+ * is launched. */
+/* Bytes of the `work` scratch of the two entry points below, either form (0 for a shape they refuse). */
+int64_t ld_dn_gnr_work_bytes(int B, int H, int W, int C, int groups);
+/* out [B, H, W, ldc] = act(GN(y; gamma, beta) + GN(y2; gamma2, beta2)), act = ReLU when relu != 0 and nothing otherwise, GN
+ * with the statistics of this batch: stat (stat2) [B][groups][2] = (mean, 1 / sqrt(biased var + 1e-5)) of y (y2).  y2,
+ * gamma2, beta2 and stat2 are all NULL (the one-operand form, convblock.1) or all given (the block's tail). */
+int ld_dn_gnr_forward(const float* y, const float* gamma, const float* beta, const float* y2, const float* gamma2,
+                      const float* beta2, double* work, float* stat, float* stat2, float* out, int B, int H, int W, int C, int ldc,
+                      int groups, int relu, void* stream);
+/* Its backward from dout, the saved result act (relu != 0: g = dout where act > 0, else 0 -- ld_seg_bn_backward's rule; relu
+ * == 0: g = dout and act may be NULL), the saved y and stat (y2 and stat2): dbeta [C] = sum g, dgamma [C] = sum g y^, dy = rstd
+ * (gamma g - mean_group(gamma g) - y^ mean_group(gamma g y^)), and the same for the second operand from the same g (dbeta2 =
+ * dbeta).  One reduction pass, a finalisation, one element-wise pass.  dy may be dout; dy2 is a buffer of its own. */
+int ld_dn_gnr_backward(const float* dout, const float* act, const float* y, const float* stat, const float* gamma,
+                       const float* y2, const float* stat2, const float* gamma2, double* work, float* dgamma, float* dbeta,
+                       float* dy, float* dgamma2, float* dbeta2, float* dy2, int B, int H, int W, int C, int ldc, int groups,
+                       int relu, void* stream);
+/* out [B, H, W, ldk], column (ci 3 + ky) 3 + kx = x[b][ci][y + ky - 1][x + kx - 1], zero outside the image and in the columns
+ * from 9 Cin on: a 3 x 3 (padding 1) convolution on an image as a 1 x 1 convolution whose weight is the OIHW parameter as it
+ * lies in memory.  x is [B, Cin, H, W] with strides (sb, sc, sh, sw) in floats, Cin 1..4; ldk >= 9 Cin a multiple of 4. */
+int ld_dn_im2col3(const float* x, float* out, int B, int Cin, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int ldk,
+                  void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

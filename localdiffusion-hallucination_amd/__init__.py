@@ -32,7 +32,8 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "coreset", "configure_runtime"]
+           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "coreset",
+           "configure_runtime"]
 
 
 def __getattr__(name):
@@ -75,4 +76,7 @@ def __getattr__(name):
     if name in ("Downsample", "Upsample", "Conv2d"):
         from . import resample
         return getattr(resample, name)
+    if name in ("BasicBlock", "ResUnet"):
+        from . import condenc
+        return getattr(condenc, name)
     raise AttributeError(name)
