@@ -904,6 +904,33 @@ int ld_dn_gnr_backward(const float* dout, const float* act, const float* y, cons
 int ld_dn_im2col3(const float* x, float* out, int B, int Cin, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int ldk,
                   void* stream);
 
+/* ---- training the denoiser, sixth slice: csrc/unet_grad.hip --------------------------------------------------------------------
+ * What a trainable Unet (ddpm.py:286-451) needs besides its blocks: the time MLP (sinusoidal embedding -> Linear(dim, T) ->
+ * GELU -> Linear(T, T), ddpm.py:136-149 and :339-344) in training form with its backward, and the glue of Unet.forward in the
+ * padded NHWC layout.  fp32 data; the time MLP's sums are fp64 in a fixed order (a wave's lanes over the input features, then
+ * the shuffle tree; the batch in index order), no atomics, nothing allocates.  A refused call returns -1 before anything is
+ * launched. */
+/* emb [B, dim] = (sin(times[b] freqs[k]), cos(..)) with times [B] as fp32 and the dim / 2 frequencies made on the host (the
+ * reference multiplies a long t by an fp32 table: float(t) * freq); h1 [B, T] = emb w1^T + b1, the pre-GELU value the backward
+ * reads; temb [B, T] = gelu(h1) w3^T + b3, the exact (erf) GELU.  w1 [T, dim], w3 [T, T] as nn.Linear keeps them.  dim even and
+ * >= 4, T a multiple of 4, dim + T <= 12288; any B >= 1 (a workgroup per sample). */
+int ld_dn_time_mlp_forward(const float* times, const float* freqs, const float* w1, const float* b1, const float* w3,
+                           const float* b3, float* emb, float* h1, float* temb, int B, int dim, int T, void* stream);
+/* Bytes of the `work` scratch of the backward (0 for a shape it refuses): gelu(h1) and dh1, [B, T] floats each. */
+int64_t ld_dn_time_mlp_work_bytes(int B, int dim, int T);
+/* Its backward from dtemb [B, T] and the saved emb and h1: dw3 [T, T] = dtemb^T gelu(h1), db3 [T] = sum_b dtemb, dh1 = (dtemb
+ * w3) gelu'(h1), dw1 [T, dim] = dh1^T emb, db1 [T] = sum_b dh1; `times` has no gradient.  Two launches: an element of dh1 per
+ * thread, then an element of a parameter gradient per thread that walks the batch in index order (any B >= 1). */
+int ld_dn_time_mlp_backward(const float* dtemb, const float* emb, const float* h1, const float* w3, float* work, float* dw1,
+                            float* db1, float* dw3, float* db3, int B, int dim, int T, void* stream);
+/* out [B, H, W, ldo]: channels 0..ca-1 = a [B, H, W, lda] (+ a2 of the same stride when given), channels ca..ca+cb-1 = b [B, H,
+ * W, ldb] when given (b == NULL goes with cb == 0), the columns from ca + cb to ldo zero.  With b == NULL it is attn(x) + x,
+ * with a2 == NULL torch.cat((a, b), dim = channels); one of the two must be given.  ca and cb are multiples of 32, every
+ * stride a multiple of 4 floats, every pointer 16-byte aligned: 16-byte loads and stores, and the sources' padding is never
+ * read.  Its gradients are views of dout, so there is no backward kernel. */
+int ld_dn_join(const float* a, const float* a2, const float* b, float* out, int B, int H, int W, int ca, int lda, int cb, int ldb,
+               int ldo, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

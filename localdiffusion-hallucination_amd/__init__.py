@@ -32,7 +32,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "coreset",
+           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "TimeMLP", "TrainableUnet", "coreset",
            "configure_runtime"]
 
 
@@ -79,4 +79,7 @@ def __getattr__(name):
     if name in ("BasicBlock", "ResUnet"):
         from . import condenc
         return getattr(condenc, name)
+    if name in ("TimeMLP", "TrainableUnet"):
+        from . import unet_grad
+        return getattr(unet_grad, name)
     raise AttributeError(name)

@@ -242,6 +242,10 @@ _SIGS = {
     "ld_dn_gnr_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_im2col3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, C.c_int, vp]),
+    "ld_dn_time_mlp_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_time_mlp_work_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
+    "ld_dn_time_mlp_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_join": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -23,6 +23,9 @@ is zero and stays zero); what is new is in ``csrc/condenc_grad.hip``:
 
 The two data gradients of a non-image block (through ``convblock.0`` and through ``identity.0``) are summed by passing one as
 the other convolution's ``residual``.
+
+``TrainableUnet`` (``unet_grad.py``) puts ``ResUnet`` in ``Unet.cond_model``'s place.  Not covered yet: a fused optimiser /
+EMA step, a ``Trainer``, and 16-bit storage.
 """
 import torch
 from torch import nn

@@ -700,8 +700,8 @@ class GaussianDiffusion(nn.Module):
         ``loss_weight[t]``, the batch mean.  ``noise`` None: draws from the run's noise stream in the reference's order
         (noise, then the [B,C] offset noise when its strength is positive, :1165-1167).  Returns the scalar loss
         (and the per-sample losses with ``per_sample=True``).  No backward pass runs here: ``p_losses_grad`` gives the gradient
-        of this loss with respect to the denoiser's output, ``ResnetBlock`` is the first trainable piece of the denoiser;
-        the backward of the whole ``Unet`` and the optimiser are not built yet."""
+        of this loss with respect to the denoiser's output, and ``TrainableUnet`` (``unet_grad.py``) takes it in
+        ``out.backward``; a fused optimiser step and a ``Trainer`` are not built yet."""
         assert not self.self_condition
         lib, st, dev = cabi.lib(), self._st(), self.device
         x0 = x_start.to(dev, torch.float32).contiguous()

@@ -20,8 +20,8 @@ the input checks are ``trainable.py``'s, shared with the two attention modules.
 
 NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``, full
 attention is in ``attention_grad.py``, Down/Upsample, the 7x7 stem, the head and the plain 3x3 are in ``resample.py``, the
-ResUnet condition encoder is in ``condenc.py``): the time MLP in front of the blocks, any optimiser / EMA / ``Trainer``,
-16-bit storage, and ``Unet`` assembling the backward of its blocks.
+ResUnet condition encoder is in ``condenc.py``, the time MLP in front of the blocks and ``TrainableUnet`` assembling the
+backward of its blocks are in ``unet_grad.py``): a fused optimiser / EMA step, a ``Trainer``, and 16-bit storage.
 """
 import torch
 from torch import nn
