@@ -931,6 +931,47 @@ int ld_dn_time_mlp_backward(const float* dtemb, const float* emb, const float* h
 int ld_dn_join(const float* a, const float* a2, const float* b, float* out, int B, int H, int W, int ca, int lda, int cb, int ldb,
                int ldo, void* stream);
 
+/* ---- training the denoiser, seventh slice: csrc/denoiser_opt.hip ----------------------------------------------------------------
+ * The optimiser step of the reference's Trainer.train (ddpm.py:1558-1571) over every parameter tensor of the Unet at once:
+ * clip_grad_norm_, Adam, zero_grad and the EMA update in two launches.  The tensors are described by a table in DEVICE memory
+ * (a few hundred entries do not fit in kernel arguments), built once per trainer: fill param, count and flags of a HOST array,
+ * let ld_dn_opt_layout assign the segments and workgroups, copy the array to the device.  Every tensor owns a 16-byte aligned
+ * segment [offset, offset + count) of four flat buffers of flat_floats floats -- grad, exp_avg, exp_avg_sq, ema -- and the
+ * workgroups first_wg .. of LD_DN_OPT_CHUNK elements each, so no workgroup straddles two tensors; counts need not be multiples
+ * of 4.  An entry without LD_DN_OPT_ADAM has no gradient and no moments (the reference's conv_fusion.mlp.1.*: it is not in the
+ * norm and Adam leaves it alone) but is in the EMA.  fp32 storage, fp64 sums in an order that depends on the sizes alone, no
+ * atomics, nothing allocates; a refused call returns -1 before anything is launched.  The kernels keep every access to the
+ * flat buffers inside flat_floats whatever the table holds; the parameter pointers are the table's. */
+#define LD_DN_OPT_CHUNK 4096
+#define LD_DN_OPT_MAX_TENSORS 65536
+#define LD_DN_OPT_ADAM 1
+typedef struct ld_dn_opt_tensor {
+  float* param;     /* the parameter's own memory: 4-byte aligned; a 16-byte aligned one takes the 16-byte loads and stores */
+  int64_t count;    /* elements, >= 1 */
+  int64_t offset;   /* (out) first float of its segment in the flat buffers, a multiple of 4 */
+  int32_t first_wg; /* (out) its first workgroup */
+  int32_t flags;    /* LD_DN_OPT_ADAM or 0 */
+} ld_dn_opt_tensor;
+/* Host only: checks param / count / flags of the n_tensors entries and fills offset and first_wg in index order; *flat_floats
+ * is the length of each flat buffer, *workgroups the grid of the two entry points below.  Nothing is written when it refuses. */
+int ld_dn_opt_layout(ld_dn_opt_tensor* tensors, int n_tensors, int64_t* flat_floats, int64_t* workgroups);
+/* *sumsq (device) = the sum of the squares of every gradient segment of an LD_DN_OPT_ADAM entry, in fp64: one partial per
+ * workgroup into work (ld_dn_opt_sqnorm_work_bytes(n_wg) bytes), added by a second launch of one workgroup in a fixed order
+ * (thread t takes partials t, t + 256, .. in index order; then the wave's shuffle tree and the four waves in order).
+ * grad 16-byte aligned, table / work / sumsq 8-byte aligned. */
+int64_t ld_dn_opt_sqnorm_work_bytes(int n_wg);
+int ld_dn_opt_sqnorm(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, const float* grad, int64_t flat_floats, double* work,
+                     double* sumsq, void* stream);
+/* One launch over the table.  coef = min(1, max_norm / (sqrt(*sumsq) + 1e-6)) (clip_grad_norm_; *sumsq is read on the device,
+ * and a NaN norm gives a NaN coef as torch's clamp does); per element of an LD_DN_OPT_ADAM entry ld_seg_adam's update from
+ * g coef (step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) from the host in double, 1 - beta rounded to fp32
+ * once) and grad = 0; then per element of every entry, with p the updated parameter: ema_mode 0 leaves ema alone, 1 sets
+ * ema = p, 2 sets ema = lerp(ema, p, ema_w) as ATen evaluates it (ema + ema_w (p - ema) below ema_w = 0.5, p - (p - ema)
+ * (1 - ema_w) from there on).  max_norm >= 0 (infinity: no clipping); 0 <= ema_w <= 1. */
+int ld_dn_opt_step(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, float* grad, float* exp_avg, float* exp_avg_sq,
+                   float* ema, int64_t flat_floats, const double* sumsq, double max_norm, double beta1, double beta2, double eps,
+                   double step_size, double bc2_sqrt, int ema_mode, float ema_w, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

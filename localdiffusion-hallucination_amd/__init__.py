@@ -32,7 +32,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
-           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "TimeMLP", "TrainableUnet", "coreset",
+           "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "TimeMLP", "TrainableUnet", "DenoiserTrainer", "coreset",
            "configure_runtime"]
 
 
@@ -82,4 +82,7 @@ def __getattr__(name):
     if name in ("TimeMLP", "TrainableUnet"):
         from . import unet_grad
         return getattr(unet_grad, name)
+    if name == "DenoiserTrainer":
+        from .denoiser_train import DenoiserTrainer
+        return DenoiserTrainer
     raise AttributeError(name)

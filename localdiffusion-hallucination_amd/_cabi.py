@@ -81,6 +81,12 @@ class McAdamTensor(C.Structure):
                 ("mirror1", vp), ("m1_off", i64), ("m1_s0", i64), ("m1_s1", i64), ("m1_s2", i64)]
 
 
+class DnOptTensor(C.Structure):
+    _fields_ = [("param", vp), ("count", i64), ("offset", i64), ("first_wg", i32), ("flags", i32)]
+
+
+DN_OPT_CHUNK, DN_OPT_ADAM = 4096, 1     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM
+
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
 _SIGS = {
     "ld_last_error": (C.c_char_p, []),
@@ -246,6 +252,11 @@ _SIGS = {
     "ld_dn_time_mlp_work_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
     "ld_dn_time_mlp_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_join": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_opt_layout": (C.c_int, [C.POINTER(DnOptTensor), C.c_int, C.POINTER(i64), C.POINTER(i64)]),
+    "ld_dn_opt_sqnorm_work_bytes": (i64, [C.c_int]),
+    "ld_dn_opt_sqnorm": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, vp, vp, vp]),
+    "ld_dn_opt_step": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, C.c_double, C.c_int, f32, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -77,6 +77,14 @@ def load_reference_checkpoint(path_or_dict, diffusion, use_ema=True, strict=True
             "unexpected": unexpected}
 
 
+def adam_param_groups(n_params, lr=1e-4, betas=(0.9, 0.99), eps=1e-8):
+    """The ``param_groups`` of ``torch.optim.Adam(params, lr=lr, betas=betas, eps=eps).state_dict()`` over ``n_params``
+    parameters (the defaults are the reference trainer's, ddpm.py:1261,1265,1444)."""
+    return [{"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "weight_decay": 0, "amsgrad": False,
+             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+             "params": list(range(n_params))}]
+
+
 def save_reference_checkpoint(diffusion, path, step=0):
     """Write ``diffusion`` in the reference's Trainer.save layout (model == ema copy; no optimizer state)."""
     sd = {k: v.detach().cpu() for k, v in diffusion.state_dict().items()}
@@ -87,9 +95,7 @@ def save_reference_checkpoint(diffusion, path, step=0):
     # 'opt': a fresh Adam state in torch's state_dict layout (no moments yet) over the model's parameters, with the
     # reference trainer's defaults (ddpm.py:1261,1265,1444): Trainer.load hands it to opt.load_state_dict (:1521)
     n_params = sum(1 for _ in diffusion.parameters())
-    opt = {"state": {}, "param_groups": [{"lr": 1e-4, "betas": (0.9, 0.99), "eps": 1e-8, "weight_decay": 0,
-                                          "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
-                                          "differentiable": False, "fused": None, "params": list(range(n_params))}]}
+    opt = {"state": {}, "param_groups": adam_param_groups(n_params)}
     torch.save({"step": int(step), "model": sd, "opt": opt, "ema": ema, "scaler": None}, path)
 
 

@@ -1,0 +1,381 @@
+"""``DenoiserTrainer``: the reference's training step for the denoiser (``Trainer.train``, ddpm.py:1532-1606) on HIP kernels --
+the seventh slice of the denoiser's backward pass.
+
+A step is: for every batch of the loader the loss divided by the number of batches, its gradients accumulated
+(``accumulate``: ``normalize`` -> ``q_sample`` -> ``TrainableUnet`` -> ``ld_p_losses`` -> ``p_losses_grad`` -> ``out.backward``);
+then ``apply``: ``clip_grad_norm_(max_grad_norm)``, ``Adam(lr, betas)``, ``zero_grad`` and ``ema.update()`` as two launches of
+``csrc/denoiser_opt.hip`` over every parameter tensor at once.  ``ld_dn_opt_sqnorm`` leaves the squared norm of all gradients
+in device memory, ``ld_dn_opt_step`` reads it there, so nothing in a step waits for the GPU: the host decides what the EMA
+does from integer counters alone (``ema_action``).
+
+Where things live.  ``diffusion`` (an ``ldh.GaussianDiffusion`` on the GPU) gives the schedule, the objective, ``normalize``,
+the noise stream and the offset noise; its ``.model``, the inference ``Unet``, plays the reference's ``ema.ema_model`` (``sample``
+runs on it; ``sync_ema`` loads the EMA weights into it).  The online model is a ``TrainableUnet`` built from
+``diffusion.model``'s configuration and weights.  Gradients, both Adam moments and the EMA weights are four flat fp32 buffers in
+which every parameter owns a 16-byte aligned segment (``ld_dn_opt_layout``); each ``.grad`` is a view of its segment, which
+autograd accumulates into in place and the step's launch zeroes, so the ``.grad`` tensors keep their addresses.
+``conv_fusion.mlp.1.weight`` / ``.bias`` get no gradient (the reference calls ``conv_fusion`` without a time embedding): they
+have no moments, are not in the norm, and are in the EMA.
+
+The EMA rule is ``ema_pytorch.EMA.update`` restated from its source (``ema_action``); the package is not available where
+this was built, so the rule could not be checked against it.
+
+NOT covered: 16-bit storage, more than one GPU, ``amp``, FID, writing the kernel-layout weight copies from the optimiser launch
+(the modules repack after a step, as they do under ``torch.optim.Adam``), handing padded tensors between modules.
+"""
+import ctypes as C
+import math
+import os
+
+import torch
+
+from . import _cabi as cabi
+from . import checkpoint
+from .trainable import stream
+from .unet_grad import TrainableUnet
+
+# the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
+NO_GRAD_PARAMS = ("conv_fusion.mlp.1.weight", "conv_fusion.mlp.1.bias")
+EMA_KEEP, EMA_COPY, EMA_LERP = 0, 1, 2
+
+
+def ema_action(s, *, beta=0.995, update_every=10, update_after_step=100, inv_gamma=1.0, power=2 / 3, min_value=0.0,
+               initted=True):
+    """What ``ema_pytorch.EMA.update()`` does at its call number ``s`` (the number of calls made before this one):
+    ``(mode, decay)`` with mode ``EMA_KEEP`` (nothing), ``EMA_COPY`` (ema = online) or ``EMA_LERP`` (ema.lerp_(online,
+    1 - decay)).  ``s % update_every != 0``: nothing.  Else ``s <= update_after_step``: copy.  Else lerp with
+    ``decay = clamp(1 - (1 + e / inv_gamma) ** -power, min_value, beta)``, ``e = max(s + 1 - update_after_step - 1, 0)``, and
+    ``decay = 0`` for ``e <= 0``; an EMA that was never initialised (``initted`` False) copies first, and a lerp from the copy
+    towards the same weights is the copy, so that case is ``EMA_COPY`` (the caller sets ``initted``).  Needs no GPU."""
+    if s % update_every != 0:
+        return EMA_KEEP, 0.0
+    if s <= update_after_step:
+        return EMA_COPY, 0.0
+    e = max(s + 1 - update_after_step - 1, 0)
+    decay = 0.0 if e <= 0 else min(max(1.0 - (1.0 + e / inv_gamma) ** -power, min_value), beta)
+    return (EMA_LERP if initted else EMA_COPY), decay
+
+
+def online_kwargs(model):
+    """The ``TrainableUnet`` constructor arguments that rebuild ``model`` (an ``ldh.Unet``)."""
+    cfg = model.cfg
+    return dict(dim=cfg.dim, init_dim=cfg.init_dim, out_dim=cfg.out_dim, dim_mults=tuple(cfg.dim_mults), channels=cfg.channels,
+                self_condition=bool(model.self_condition), cond_img=model.cond_img, resnet_block_groups=cfg.resnet_block_groups,
+                learned_sinusoidal_cond=bool(model.random_or_learned_sinusoidal_cond), learned_sinusoidal_dim=cfg.learned_sinusoidal_dim,
+                sinusoidal_pos_emb_theta=model.theta, attn_dim_head=cfg.attn_dim_head, attn_heads=cfg.attn_heads,
+                full_attn=tuple(cfg.full_attn), mode=cfg.mode)
+
+
+def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr, betas, eps, ema_step, initted):
+    """The dictionary ``Trainer.save`` writes (ddpm.py:1495-1507), from CPU tensors.  ``diffusion_sd``: the
+    ``GaussianDiffusion.state_dict()`` (its ``model.*`` entries give the key order and are replaced); ``online_sd`` / ``ema_sd``:
+    the online and the EMA weights by the Unet's names, in the order of ``parameters()``; ``moments``: {name: (exp_avg,
+    exp_avg_sq)} of the parameters that have them.  ``model`` = the buffers + ``model.<online>``; ``ema`` = the same under
+    ``online_model.``, the buffers + ``model.<ema>`` under ``ema_model.``, ``initted`` and ``step``; ``opt`` = a
+    ``torch.optim.Adam.state_dict()`` whose ``state[i]`` exists for the parameters with moments."""
+    def with_weights(w):
+        return {k: (w[k[6:]] if k.startswith("model.") else v).detach().cpu().clone() for k, v in diffusion_sd.items()}
+    missing = [k for k in diffusion_sd if k.startswith("model.") and k[6:] not in online_sd]
+    if missing or len(online_sd) != sum(k.startswith("model.") for k in diffusion_sd) or list(online_sd) != list(ema_sd):
+        raise ValueError(f"checkpoint_dict: the online / EMA weights do not match the diffusion's model (e.g. {missing[:3]})")
+    model = with_weights(online_sd)
+    ema = {"online_model." + k: v for k, v in model.items()}
+    ema.update({"ema_model." + k: v for k, v in with_weights(ema_sd).items()})
+    ema["initted"] = torch.tensor(bool(initted))
+    ema["step"] = torch.tensor(int(ema_step))
+    state = {}
+    for i, name in enumerate(online_sd):
+        if name in moments:
+            m, v = moments[name]
+            state[i] = {"step": torch.tensor(float(opt_step)), "exp_avg": m.detach().cpu().clone(),
+                        "exp_avg_sq": v.detach().cpu().clone()}
+    opt = {"state": state, "param_groups": checkpoint.adam_param_groups(len(online_sd), lr, betas, eps)}
+    return {"step": int(step), "model": model, "opt": opt, "ema": ema, "scaler": None}
+
+
+def _positive(name, v, zero_ok=False):
+    if not isinstance(v, (int, float)) or isinstance(v, bool) or math.isnan(v) or v < 0 or (v == 0 and not zero_ok):
+        raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be a {'non-negative' if zero_ok else 'positive'} number")
+
+
+class DenoiserTrainer:
+    """``DenoiserTrainer(diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
+    ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2/3, ema_min_value=0.0)``: the defaults are
+    the reference's (ddpm.py:1261-1265, 1444, 1449 and ``ema_pytorch``'s).  Refused with ``ValueError`` before any GPU call:
+    what ``TrainableUnet`` refuses, ``self_condition``, hyper-parameters out of range, a ``diffusion`` that is not on a GPU.
+
+    ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
+    ``ema_initted`` are ``ema_pytorch``'s two buffers."""
+
+    def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
+                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0):
+        model = getattr(diffusion, "model", None)
+        if model is None or not hasattr(model, "cfg") or not hasattr(diffusion, "p_losses_grad"):
+            raise ValueError("DenoiserTrainer: diffusion must be an ldh.GaussianDiffusion around an ldh.Unet")
+        if getattr(diffusion, "self_condition", False) or getattr(model, "self_condition", False):
+            raise ValueError("DenoiserTrainer: self_condition is not built for training (no shipped caller of the reference sets it)")
+        _positive("train_lr", train_lr)
+        _positive("eps", eps, zero_ok=True)
+        _positive("max_grad_norm", max_grad_norm, zero_ok=True)
+        _positive("ema_inv_gamma", ema_inv_gamma)
+        _positive("ema_power", ema_power, zero_ok=True)
+        betas = tuple(adam_betas)
+        if len(betas) != 2 or not all(isinstance(b, float) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"DenoiserTrainer: adam_betas {adam_betas!r} must be two floats in [0, 1)")
+        if not (0.0 <= ema_min_value <= ema_decay <= 1.0):
+            raise ValueError(f"DenoiserTrainer: 0 <= ema_min_value {ema_min_value} <= ema_decay {ema_decay} <= 1 does not hold")
+        for name, v, lo in (("ema_update_every", ema_update_every, 1), ("ema_update_after_step", ema_update_after_step, 0)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < lo:
+                raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
+        online = TrainableUnet(**online_kwargs(model))                  # (raises ValueError for what it cannot train)
+        dev = diffusion.device
+        if dev.type != "cuda":
+            raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")
+        self.diffusion, self.device = diffusion, dev
+        self.lr, self.betas, self.eps, self.max_grad_norm = float(train_lr), betas, float(eps), float(max_grad_norm)
+        self.ema_kw = dict(beta=float(ema_decay), update_every=ema_update_every, update_after_step=ema_update_after_step,
+                           inv_gamma=float(ema_inv_gamma), power=float(ema_power), min_value=float(ema_min_value))
+        self.step, self.ema_step, self.ema_initted, self.last_ema = 0, 0, False, None
+        online.load_state_dict(model.state_dict())
+        self.online_model = online.to(dev)
+        self._build_table()
+
+    # ------------------------------------------------------------------ the table and the flat buffers
+    def _build_table(self):
+        dev, lib = self.device, cabi.lib()
+        named = list(self.online_model.named_parameters())
+        self.names = [k for k, _ in named]
+        n = len(named)
+        host = (cabi.DnOptTensor * n)()
+        for e, (k, p) in zip(host, named):
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"DenoiserTrainer: parameter {k} is {p.dtype}, contiguous {p.is_contiguous()}; fp32 contiguous only")
+            e.param, e.count, e.flags = p.data_ptr(), p.numel(), (0 if k in NO_GRAD_PARAMS else cabi.DN_OPT_ADAM)
+        flat, wgs = cabi.i64(), cabi.i64()
+        cabi.check(lib.ld_dn_opt_layout(host, n, C.byref(flat), C.byref(wgs)), "dn_opt_layout")
+        self._n, self._n_wg, self._flat = n, int(wgs.value), int(flat.value)
+        self._segments = {k: (int(e.offset), int(e.count), bool(e.flags & cabi.DN_OPT_ADAM)) for e, (k, _) in zip(host, named)}
+        self._ptrs = [int(e.param) for e in host]
+        self._views = self._params = None
+        with torch.cuda.device(dev):
+            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+            self._grad, self._m, self._v, self._ema = (torch.zeros(self._flat, dtype=torch.float32, device=dev) for _ in range(4))
+            self._work = torch.zeros(1 + int(lib.ld_dn_opt_sqnorm_work_bytes(self._n_wg)) // 8, dtype=torch.float64, device=dev)
+        with torch.no_grad():                               # ema_pytorch: the EMA model starts as a copy of the online one
+            for k, p in named:
+                self._segment(self._ema, k).copy_(p.reshape(-1))
+        self._attach_grads()
+
+    def _segment(self, flat, name):
+        off, count, _ = self._segments[name]
+        return flat[off:off + count]
+
+    def _attach_grads(self):
+        """Every trained parameter's ``.grad`` is the view of its segment of the flat gradient (a ``.grad`` the caller put
+        there instead is added to the segment first); the parameters must still be where the table says.  The views are
+        made once: a step only checks identities."""
+        if self._views is None:
+            named = list(self.online_model.named_parameters())
+            self._params = [p for _, p in named]
+            self._views = [(k, p, ptr, self._segment(self._grad, k).view(p.shape) if self._segments[k][2] else None)
+                           for (k, p), ptr in zip(named, self._ptrs)]
+        for k, p, ptr, view in self._views:
+            if p.data_ptr() != ptr:
+                raise RuntimeError(f"DenoiserTrainer: parameter {k} was moved (.to(), assign); build a new trainer")
+            if view is None or p.grad is view:
+                continue
+            if p.grad is not None and p.grad.data_ptr() != view.data_ptr():
+                view.add_(p.grad)
+            p.grad = view
+
+    # ------------------------------------------------------------------ one batch, one step
+    def accumulate(self, hr, lr, scale=1.0, t=None, noise=None):
+        """One batch of ddpm.py:1544-1553: adds the gradients of ``scale`` times the training loss of (``hr``, the image,
+        ``lr``, the condition image) to the ``.grad``s and returns ``scale * loss`` as a 0-d device tensor.  ``t`` None: drawn
+        as ``GaussianDiffusion.forward(train=True)`` draws it (torch's host generator); ``noise`` None: drawn as ``p_losses``
+        draws it (the run's noise stream, the offset noise included).  No host synchronisation."""
+        gd, dev, lib = self.diffusion, self.device, cabi.lib()
+        if not isinstance(hr, torch.Tensor) or hr.dim() != 4:
+            raise ValueError("DenoiserTrainer: hr must be a [B, C, H, W] tensor")
+        B = hr.shape[0]
+        if t is None:
+            t = torch.randint(0, gd.num_timesteps, (B,)).long()
+        if not t.is_cuda:
+            t = t.pin_memory()                              # (a pageable copy would wait for the stream)
+        self._attach_grads()
+        with torch.cuda.device(dev):
+            t = t.to(dev, torch.long, non_blocking=True)
+            with torch.no_grad():
+                x0 = gd.normalize(hr.to(dev, torch.float32)).contiguous()
+                cond = lr.to(dev, torch.float32).contiguous()
+                noise = gd.training_noise(x0, noise)
+                t32 = t.to(torch.int32)
+                x = torch.empty_like(x0)
+                cabi.check(lib.ld_q_sample_t(x0.data_ptr(), noise.data_ptr(), x.data_ptr(), t32.data_ptr(),
+                                             gd.sqrt_alphas_cumprod.data_ptr(), gd.sqrt_one_minus_alphas_cumprod.data_ptr(), B,
+                                             x0[0].numel(), stream(dev)), "q_sample_t")
+            out = self.online_model(x, cond, t)
+            with torch.no_grad():
+                per_sample = torch.empty(B, dtype=torch.float32, device=dev)
+                cabi.check(lib.ld_p_losses(out.data_ptr(), x0.data_ptr(), noise.data_ptr(), t32.data_ptr(),
+                                           gd.sqrt_alphas_cumprod.data_ptr(), gd.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                                           gd.loss_weight.data_ptr(), per_sample.data_ptr(), B, x0[0].numel(),
+                                           cabi.OBJ[gd.objective], stream(dev)), "p_losses")
+                value = per_sample.mean() * float(scale)
+            out.backward(gd.p_losses_grad(out, x0, noise, t, grad_output=float(scale)))
+        return value
+
+    def apply(self):
+        """ddpm.py:1558-1571: clip the accumulated gradients to ``max_grad_norm``, Adam, zero the gradients, ``ema.update()``
+        -- two launches -- and move every parameter's version so that the modules repack their weights.  Nothing waits."""
+        dev, lib = self.device, cabi.lib()
+        self._attach_grads()
+        t = self.step + 1
+        b1, b2 = self.betas
+        step_size = self.lr / (1.0 - b1 ** t)               # bias corrections in double on the host
+        bc2_sqrt = math.sqrt(1.0 - b2 ** t)
+        mode, decay = ema_action(self.ema_step, initted=self.ema_initted, **self.ema_kw)
+        if self.ema_step % self.ema_kw["update_every"] == 0 and self.ema_step > self.ema_kw["update_after_step"]:
+            self.ema_initted = True
+        with torch.cuda.device(dev):
+            st = stream(dev)
+            sumsq = self._work.data_ptr()
+            cabi.check(lib.ld_dn_opt_sqnorm(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._flat,
+                                            sumsq + 8, sumsq, st), "dn_opt_sqnorm")
+            cabi.check(lib.ld_dn_opt_step(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._m.data_ptr(),
+                                          self._v.data_ptr(), self._ema.data_ptr(), self._flat, sumsq, self.max_grad_norm, b1, b2,
+                                          self.eps, step_size, bc2_sqrt, mode, 1.0 - decay, st), "dn_opt_step")
+        # the packed-weight caches are keyed on _version, which a raw kernel write does not move
+        torch.autograd.graph.increment_version(self._params)
+        self.last_ema = (mode, decay)                       # what the launch was told: (EMA_KEEP / EMA_COPY / EMA_LERP, decay)
+        self.step += 1
+        self.ema_step += 1
+
+    def train_step(self, batches):
+        """The reference's step: ``accumulate(hr, lr, scale=1 / len(batches))`` over all ``(hr, lr)`` batches, ``apply()``;
+        returns the summed loss (the reference's ``total_loss``) on the device."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("DenoiserTrainer: no batches")
+        total = None
+        for hr, lr in batches:
+            value = self.accumulate(hr, lr, scale=1.0 / len(batches))
+            total = value if total is None else total + value
+        self.apply()
+        return total
+
+    def check_finite(self):
+        """Read the last step's gradient norm back (the one place that does) and raise on a non-finite value; returns it."""
+        norm = math.sqrt(float(self._work[0].item())) if self.step else 0.0
+        if not math.isfinite(norm):
+            raise FloatingPointError(f"DenoiserTrainer: the gradient norm of step {self.step} is {norm}; the weights and moments "
+                                     "took the step as torch would have (they hold NaN now)")
+        return norm
+
+    # ------------------------------------------------------------------ state
+    def _named(self, flat):
+        return {k: self._segment(flat, k).view(p.shape).clone() for k, p in self.online_model.named_parameters()}
+
+    def ema_state_dict(self):
+        """The EMA weights by the Unet's names (copies, on the device)."""
+        return self._named(self._ema)
+
+    def moments(self):
+        """{name: (exp_avg, exp_avg_sq)} of the parameters that have them (copies, on the device)."""
+        m, v = self._named(self._m), self._named(self._v)
+        return {k: (m[k], v[k]) for k in self.names if self._segments[k][2]}
+
+    def sync_ema(self):
+        """Load the EMA weights into ``diffusion.model`` (the reference's ``ema.ema_model``) for sampling and evaluation."""
+        self.diffusion.model.load_state_dict(self.ema_state_dict())          # (``Unet.load_state_dict`` invalidates its plans)
+
+    @torch.no_grad()
+    def evaluate(self, batches, min_max_val):
+        """ddpm.py:1574-1587: sample every ``(hr, lr)`` test batch from ``lr`` with the EMA weights and return the mean over
+        the batches of the mean squared error to ``hr``."""
+        self.sync_ema()
+        losses = []
+        for hr, lr in batches:
+            lr = lr.to(self.device, torch.float32)
+            out = self.diffusion.sample(lr, None, batch_size=lr.shape[0], mask=None, min_max_val=min_max_val)
+            losses.append(float(torch.nn.functional.mse_loss(out, hr.to(self.device, torch.float32))))
+        if not losses:
+            raise ValueError("DenoiserTrainer: no test batches")
+        return sum(losses) / len(losses)
+
+    def state(self):
+        """``checkpoint_dict``'s result for this trainer (CPU tensors)."""
+        cpu = lambda d: {k: v.detach().cpu() for k, v in d.items()}                        # noqa: E731
+        moments = {k: (m.cpu(), v.cpu()) for k, (m, v) in self.moments().items()}
+        online = {k: p for k, p in self.online_model.named_parameters()}
+        return checkpoint_dict(self.step, cpu(self.diffusion.state_dict()), cpu(online), cpu(self.ema_state_dict()), moments,
+                               self.step, self.lr, self.betas, self.eps, self.ema_step, self.ema_initted)
+
+    def save(self, path):
+        """Write the reference's ``Trainer.save`` file (``checkpoint.load_reference_checkpoint`` and the reference's own
+        ``Trainer.load`` read it)."""
+        torch.save(self.state(), path)
+
+    def load(self, path, trust_pickle=False):
+        """Restore what ``save`` wrote (or the reference's ``Trainer.save``): the EMA weights into ``diffusion`` and the EMA
+        buffer, the online weights, both moments, Adam's step count and the counters."""
+        data = checkpoint._read(path, trust_pickle)
+        info = checkpoint.load_reference_checkpoint(data, self.diffusion, use_ema=True)
+        if info["source"] != "ema":
+            raise RuntimeError(f"DenoiserTrainer.load: the file has no EMA weights (found {info['source']!r})")
+        online = {k[6:]: v for k, v in data["model"].items() if k.startswith("model.")}
+        self.online_model.load_state_dict(online)                     # (in place: the table's pointers stay good)
+        ema = {k[len("ema_model.model."):]: v for k, v in data["ema"].items() if k.startswith("ema_model.model.")}
+        state = data["opt"]["state"]
+        with torch.no_grad():
+            self._m.zero_()
+            self._v.zero_()
+            self._grad.zero_()
+            for i, k in enumerate(self.names):
+                self._segment(self._ema, k).copy_(ema[k].reshape(-1))
+                if i in state:
+                    if not self._segments[k][2]:
+                        raise RuntimeError(f"DenoiserTrainer.load: the file has Adam moments for {k}, which gets no gradient")
+                    self._segment(self._m, k).copy_(state[i]["exp_avg"].reshape(-1))
+                    self._segment(self._v, k).copy_(state[i]["exp_avg_sq"].reshape(-1))
+        steps = {int(float(s["step"])) for s in state.values()}
+        if len(steps) > 1:
+            raise RuntimeError(f"DenoiserTrainer.load: the parameters' Adam step counts differ ({sorted(steps)[:4]})")
+        self.step = int(data["step"])
+        if steps and steps != {self.step}:
+            raise RuntimeError(f"DenoiserTrainer.load: Adam's step count {steps} is not the trainer's step {self.step}")
+        self.ema_step, self.ema_initted = int(data["ema"]["step"]), bool(data["ema"]["initted"])
+        self._attach_grads()
+        return info
+
+    # ------------------------------------------------------------------ the loop
+    def fit(self, batches, test_batches, num_steps, save_and_sample_every, out_dir, min_max_val=None):
+        """``Trainer.train`` (ddpm.py:1532-1606) until ``step == num_steps``: ``train_step(batches)``; every
+        ``save_and_sample_every`` steps ``evaluate(test_batches)`` and, at a new best, ``save`` to
+        ``<out_dir>/model-best<step rounded up to 100 (mnist) or 500>.pt``.  ``train_loss.csv`` and ``loss.csv`` have the
+        layout pandas gives the reference's frames (an index column, ``epoch``, ``loss``); ``train_loss.csv`` holds every
+        step (the reference appends each step's row to the evaluation frame, so its file keeps only the last one).
+        ``min_max_val`` defaults to the reference's per data set (ddpm.py:1474-1489).  Returns the best evaluation loss."""
+        data = str(self.diffusion.config.get("data", ""))
+        if min_max_val is None:
+            min_max_val = (0.0, 1.0) if data == "mnist" else (-1.0, 1.0) if data == "mri" else (0.0, 2.0)
+        os.makedirs(out_dir, exist_ok=True)
+        batches, test_batches = list(batches), list(test_batches)
+        train_rows, eval_rows, best = [], [], 1e10
+
+        def write(name, rows):
+            with open(os.path.join(out_dir, name), "w") as f:
+                f.write(",epoch,loss\n" + "".join(f"{i},{e},{v}\n" for i, (e, v) in enumerate(rows)))
+        while self.step < num_steps:
+            at = self.step
+            train_rows.append((at, float(self.train_step(batches))))
+            write("train_loss.csv", train_rows)
+            if self.step % save_and_sample_every == 0:
+                ls = self.evaluate(test_batches, min_max_val)
+                if best > ls:
+                    best = ls
+                    num = 100 if data == "mnist" else 500
+                    self.save(os.path.join(out_dir, f"model-best{int(math.ceil(self.step / num)) * num}.pt"))
+                eval_rows.append((self.step, ls))
+                write("loss.csv", eval_rows)
+        return best

@@ -693,19 +693,12 @@ class GaussianDiffusion(nn.Module):
                                             x0.shape[0], x0[0].numel(), self._st()), "q_sample_t")
         return out
 
-    @torch.inference_mode()
-    def p_losses(self, x_start, cond_img, t, noise=None, offset_noise_strength=None, per_sample=False):
-        """The training loss of one batch WITHOUT a backward pass (ddpm.py:1156-1201): q_sample at the per-sample
-        timesteps ``t``, one denoiser evaluation, the objective's target, the per-sample mean squared error times
-        ``loss_weight[t]``, the batch mean.  ``noise`` None: draws from the run's noise stream in the reference's order
-        (noise, then the [B,C] offset noise when its strength is positive, :1165-1167).  Returns the scalar loss
-        (and the per-sample losses with ``per_sample=True``).  No backward pass runs here: ``p_losses_grad`` gives the gradient
-        of this loss with respect to the denoiser's output, and ``TrainableUnet`` (``unet_grad.py``) takes it in
-        ``out.backward``; a fused optimiser step and a ``Trainer`` are not built yet."""
-        assert not self.self_condition
-        lib, st, dev = cabi.lib(), self._st(), self.device
-        x0 = x_start.to(dev, torch.float32).contiguous()
-        B = x0.shape[0]
+    def training_noise(self, x0, noise=None, offset_noise_strength=None):
+        """The noise of one training batch as ddpm.py:1165-1167 makes it, for ``x0`` [B, C, H, W] fp32 on the device:
+        ``noise`` (None: the next draw of the run's noise stream) plus, when the strength is positive, that strength times a
+        [B, C] draw -- the next one of the stream -- broadcast over the image.  Shared by ``p_losses`` and
+        ``DenoiserTrainer.accumulate``, so that both draw the same values in the same order."""
+        dev = self.device
         if noise is None:
             noise = torch.empty_like(x0)
             self._train_draw = getattr(self, "_train_draw", -1) + 1
@@ -713,10 +706,27 @@ class GaussianDiffusion(nn.Module):
         noise = noise.to(dev, torch.float32).contiguous()
         strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
         if strength > 0.0:
-            off = torch.empty(B, x0.shape[1], dtype=torch.float32, device=dev)
+            off = torch.empty(x0.shape[0], x0.shape[1], dtype=torch.float32, device=dev)
             self._train_draw = getattr(self, "_train_draw", -1) + 1
             self._noise(off, self._train_draw)
             noise = (noise + strength * off[:, :, None, None]).contiguous()
+        return noise
+
+    @torch.inference_mode()
+    def p_losses(self, x_start, cond_img, t, noise=None, offset_noise_strength=None, per_sample=False):
+        """The training loss of one batch WITHOUT a backward pass (ddpm.py:1156-1201): q_sample at the per-sample
+        timesteps ``t``, one denoiser evaluation, the objective's target, the per-sample mean squared error times
+        ``loss_weight[t]``, the batch mean.  ``noise`` None: draws from the run's noise stream in the reference's order
+        (noise, then the [B,C] offset noise when its strength is positive, :1165-1167).  Returns the scalar loss
+        (and the per-sample losses with ``per_sample=True``).  No backward pass runs here: ``p_losses_grad`` gives the gradient
+        of this loss with respect to the denoiser's output, ``TrainableUnet`` (``unet_grad.py``) takes it in
+        ``out.backward``, and ``DenoiserTrainer`` (``denoiser_train.py``) is the reference's training step around the two:
+        this loss, its backward, and one fused clip / Adam / EMA launch pair."""
+        assert not self.self_condition
+        lib, st, dev = cabi.lib(), self._st(), self.device
+        x0 = x_start.to(dev, torch.float32).contiguous()
+        B = x0.shape[0]
+        noise = self.training_noise(x0, noise, offset_noise_strength)
         x = self.q_sample(x0, t, noise)
         model_out = self.model(x, cond_img.to(dev, torch.float32), t.to(dev, torch.long)).contiguous()
         t32 = t.to(dev, torch.int32).contiguous()

@@ -19,8 +19,8 @@ synchronisation in either direction, no atomics, the same bits on every call.
 The modules still exchange [B, C, H, W] views (``Run.nhwc``'s contract): where a view's channel count is not a multiple of 64
 (32 and 96 channels) the next module repacks it (``ld_dn_pack_nhwc``).
 
-NOT covered (follow-ups): the fused clipped-Adam / EMA step and a ``Trainer`` (``torch.optim.Adam`` trains this module as it
-is), and 16-bit storage.
+The fused clipped-Adam / EMA step and the trainer around this module are ``denoiser_train.py`` (``torch.optim.Adam`` trains
+it as it is, too).  NOT covered: 16-bit storage.
 """
 import math
 
