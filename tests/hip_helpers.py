@@ -59,7 +59,7 @@ def rel_err(got, ref):
 
 def pack(w, dtype, ksize, scale_in=None, unshuffle=0):
     w = w.to(DEV, torch.float32).contiguous()
-    out = torch.empty(w.numel(), dtype=TDT[dtype], device=DEV)
+    out = nans(w.numel(), dtype=TDT[dtype])
     si = None if scale_in is None else scale_in.to(DEV, torch.float32).contiguous()
     cabi.check(cabi.lib().ld_pack_conv_weight(w.data_ptr(), cabi.ptr(si), out.data_ptr(), w.shape[0], w.shape[1],
                                               ksize, unshuffle, cabi.dtype_code(dtype), st()), "pack")
@@ -86,7 +86,7 @@ def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_p
         a.src[i] = s
     a.nsrc = len(srcs)
     a.weight, a.bias = wpacked.data_ptr(), bias.data_ptr()
-    out = torch.empty(B, H, W, cout, dtype=TDT[dtype], device=DEV)
+    out = nans(B, H, W, cout, dtype=TDT[dtype])
     a.out = out.data_ptr()
     if stats is not None:
         a.out_stats, a.out_groups = stats.data_ptr(), groups
@@ -94,7 +94,7 @@ def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_p
     a.t_ptr = cabi.ptr(t_ptr)
     side_out = None
     if side is not None:
-        side_out = torch.empty(B, H, W, cout, dtype=TDT[dtype], device=DEV)
+        side_out = nans(B, H, W, cout, dtype=TDT[dtype])
         a.side_weight, a.side_bias, a.side_out = side[0].data_ptr(), side[1].data_ptr(), side_out.data_ptr()
     cabi.check(cabi.lib().ld_conv3x3(C.byref(a), st()), "conv3x3")
     return out if side is None else (out, side_out)
@@ -112,7 +112,7 @@ def conv1x1(srcs, wpacked, B, H, W, cout, dtype, bias=None, epi=0, unshuffle=0, 
     a.kmax_out = cabi.ptr(kmax_out)
     if gn_tail is not None:
         a.gn_tail = gn_tail
-    out = torch.empty(B, H, W, cout, dtype=TDT[dtype], device=DEV)
+    out = nans(B, H, W, cout, dtype=TDT[dtype])
     a.out = out.data_ptr()
     a.B, a.H, a.W, a.Cout, a.dtype = B, H, W, cout, cabi.dtype_code(dtype)
     cabi.check(cabi.lib().ld_conv1x1(C.byref(a), st()), "conv1x1")

@@ -1,0 +1,132 @@
+"""The exact-arithmetic probes of tests/exact_probes.py, proved on the CPU: every builder at every shape that
+tests/test_hip_exact.py uses asserts its own preconditions (fp32 torch == fp64 torch bit for bit, results inside the
+range all three storage types hold exactly, integer statistics, logit gaps, ...) when it is called, so calling it IS
+the test.  And the case that motivates them: a 3x3 convolution that mis-reads one channel at one tap passes the
+norm-wise rule of tests/test_hip_ops.py in bf16 and fails torch.equal on the integer probe."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from localdiffusion_hallucination_amd import rng
+from oracle import unet_ref
+import exact_probes as P
+
+RTOL_BF16 = 3e-2            # hip_helpers.RTOL["bf16"], the rule of tests/test_hip_ops.py (no device import here)
+
+
+@pytest.mark.parametrize("shape", P.CONV3_SHAPES + P.CONV3_SK_SHAPES + [P.BIG64_SHAPE, P.C32_SHAPE])
+@pytest.mark.parametrize("frac", [False, True])
+def test_conv3x3_probes(shape, frac):
+    p = P.conv3x3(*shape, frac=frac)
+    assert float(p.ref.abs().max()) > 8            # a probe, not a field of zeros
+    if frac:          # the fraction survives: every output is an integer + odd/1024
+        assert bool((((p.ref.double() * 1024).round() % 2) == 1).all())
+
+
+@pytest.mark.parametrize("H,W", P.S32_SIZES)
+@pytest.mark.parametrize("case", sorted(P.S32_CASES))
+def test_lean_kernel_probes(case, H, W):
+    P.conv3x3(2, P.S32_CASES[case], 32, H, W)
+    P.conv3x3(2, P.S32_CASES[case], 32, H, W, frac=True)
+
+
+def test_two_source_and_side_output_probes():
+    P.conv3x3_concat_upsample()
+    p = P.conv3x3_side()
+    assert p.ref.shape == p.ref_side.shape == (2, 64, 17, 23)
+
+
+@pytest.mark.parametrize("shape", P.CONV1_SHAPES)
+def test_conv1x1_probes(shape):
+    P.conv1x1(*shape)
+    P.conv1x1(*shape, frac=True)
+
+
+def test_conv1x1_variant_probes():
+    P.conv1x1_concat()
+    P.conv1x1(2, 128, 64, 9, 11, residual=True)
+    P.conv1x1(2, 128, 64, 9, 11, residual=True, per_batch=True)
+    for nch in (2, 3, 5, 13):
+        P.conv1x1(2, 32 * nch, 64, 16, 16, key=2300 + nch)
+    p = P.conv1x1_unshuffle()
+    sd = {"d.1.weight": p.w, "d.1.bias": p.b}
+    assert torch.equal(unet_ref.pixel_unshuffle_conv(sd, "d", p.x), p.ref)      # the oracle's rearrangement
+
+
+@pytest.mark.parametrize("cin,ks,H,W", P.IMAGE_CASES)
+def test_conv_image_probes(cin, ks, H, W):
+    P.conv_image(cin, ks, H, W)
+
+
+@pytest.mark.parametrize("cin,H,W", P.STEM_SHAPES)
+@pytest.mark.parametrize("variant", ["int", "frac", "split", "mirror"])
+def test_stem_probes(cin, H, W, variant):
+    p = P.stem(cin, H, W, variant)
+    if variant != "int":
+        assert not torch.equal(P.stored(p.ref, "bf16"), p.ref)
+
+
+@pytest.mark.parametrize("cin,cout", P.FINAL_CASES)
+def test_final_conv_probes(cin, cout):
+    P.final_conv(cin, cout)
+    P.final_conv(cin, cout, frac=True)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("kind", ["3x3", "1x1"])
+def test_two_term_weight_probes(kind, dtype):
+    P.two_term(kind, dtype)
+
+
+@pytest.mark.parametrize("n", P.ATTN_SIZES)
+def test_attention_probes(n):
+    p = P.attention_onehot(n)
+    print(f"one-hot n={n}: smallest logit gap {p.gap:.0f}")
+    u = P.attention_uniform(n)
+    print(f"uniform n={n}: fp32 torch distance even {u.d_even:.2e} (of 8), odd {u.d_odd:.2e}")
+    # what the probe is for: ONE key skipped or counted twice moves an even channel by at least 4 / (n + 1)
+    assert 4.0 / (n + 1) / 8.0 > 10 * max(1e-5, 4 * u.d_even)
+
+
+@pytest.mark.parametrize("C,H,W", P.LINATTN_SHAPES)
+def test_linattn_probes(C, H, W):
+    p = P.linattn_uniform(C, H, W)
+    n = H * W
+    print(f"linattn C={C} n={n}: fp32 torch distance {p.d:.2e}")
+    assert 1.0 / (n + 1) > 10 * max(1e-5, 4 * p.d)         # a pixel lost or doubled: 1.6e-4 at n = 6144
+    # the oracle's RMSNorm with g = scale / sqrt(C) is the normalisation the builder used
+    g = (p.scale / C ** 0.5).reshape(1, C, 1, 1)
+    kv = F.conv2d(unet_ref.rms_norm(p.x, g), p.w)
+    assert float(kv[:, 128:256].abs().max()) == 0.0
+    assert float((kv[:, 256:].abs() - 1).abs().max()) < 1e-6 or C == 32
+    assert float((kv[:, 256:].abs().round() - kv[:, 256:].abs()).abs().max()) < 1e-6
+
+
+def _emulated_bf16(conv, x, w, b):
+    """A clean bf16 kernel: fp32 arithmetic on bf16-rounded operands, the output rounded once."""
+    q = lambda t: t.to(torch.bfloat16).float()
+    return q(conv(q(x), q(w), b))
+
+
+def test_a_misread_channel_passes_the_normwise_rule_and_fails_the_exact_probe():
+    """256 -> 256 at 8 x 8 on the inputs of test_hip_ops.test_conv3x3_plain_and_stats: the last input channel of the
+    centre tap reads its neighbour.  max-abs error / max-abs reference stays under the bf16 bound of 3e-2 (a clean
+    kernel sits at 2-3e-3); on the integer probe of the same shape the same mutation changes output bits."""
+    B, cin, cout, H, W = 1, 256, 256, 8, 8
+    r = lambda shape, key, lo=-1.0, hi=1.0: torch.from_numpy(rng.uniform(shape, 1234, key, lo, hi))
+    x, w, b = r((B, cin, H, W), 1), r((cout, cin, 3, 3), 2, -0.1, 0.1), r((cout,), 3)
+    q = lambda t: t.to(torch.bfloat16).float()
+    ref = F.conv2d(q(x), q(w), b, padding=1)
+    rel = lambda got: float((got - ref).abs().max()) / float(ref.abs().max())
+    clean = rel(_emulated_bf16(lambda x, w, b: F.conv2d(x, w, b, padding=1), x, w, b))
+    broken = rel(_emulated_bf16(P.misread_last_channel, x, w, b))
+    print(f"old rule: clean {clean:.2e}, one mis-read channel {broken:.2e}, bound {RTOL_BF16:.0e}")
+    assert clean < RTOL_BF16 / 8
+    assert broken < RTOL_BF16 and broken > 2 * clean       # wrong, visibly worse than clean, and let through
+    p = P.conv3x3(B, cin, cout, H, W)
+    good = _emulated_bf16(lambda x, w, b: F.conv2d(x, w, b, padding=1), p.x, p.w, p.b)
+    bad = _emulated_bf16(P.misread_last_channel, p.x, p.w, p.b)
+    assert torch.equal(good, p.ref)
+    assert not torch.equal(bad, p.ref)
+    print(f"integer probe: {int((bad != p.ref).sum())} of {bad.numel()} outputs differ")

@@ -287,7 +287,7 @@ def test_conv_image(dtype, cin, ks, H, W):
     B = 2
     x, w, b = hh.rand((B, cin, H, W), 40), hh.rand((32, cin, ks, ks), 41, -0.2, 0.2), hh.rand((32,), 42)
     ref = F.conv2d(x, w, b, padding=ks // 2)
-    out = torch.empty(B, H, W, 32, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H, W, 32, dtype=hh.TDT[dtype])
     stats = hh.stats_buffer(B, 16)
     xd, wd, bd = x.to(hh.DEV), w.to(hh.DEV), b.to(hh.DEV)
     cabi.check(cabi.lib().ld_conv_image(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), out.data_ptr(), stats.data_ptr(),
@@ -309,7 +309,7 @@ def test_conv_stem_mfma_16bit(dtype, cin, H, W):
     xd, wd, bd = x.to(hh.DEV), w.to(hh.DEV).contiguous(), b.to(hh.DEV)
     wp = torch.empty(int(lib.ld_stem_packed_bytes()), dtype=torch.uint8, device=hh.DEV)
     cabi.check(lib.ld_pack_stem_weight(wd.data_ptr(), wp.data_ptr(), cin, hh.st()), "pack_stem")
-    out = torch.empty(B, H, W, 32, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H, W, 32, dtype=hh.TDT[dtype])
     cabi.check(lib.ld_conv_stem(xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), out.data_ptr(), B, cin, H, W,
                                 cabi.dtype_code(dtype), hh.st()), "conv_stem")
     got = hh.nchw(out)
@@ -317,7 +317,7 @@ def test_conv_stem_mfma_16bit(dtype, cin, H, W):
     # the split products keep ~2^-16 relative accuracy: what is left is the final rounding of the stored value
     # (half an ulp) plus, for fp16, that 2^-16 of the largest product
     assert float(((got - ref).abs() / ref.abs().clamp_min(0.25)).max()) < ulp * 1.02 + (0 if dtype == "bf16" else 2.0 ** -13)
-    out2 = torch.empty_like(out)
+    out2 = torch.full_like(out, hh.NAN)
     cabi.check(lib.ld_conv_image(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), out2.data_ptr(), None, 0, B, cin, H, W, 7,
                                  cabi.dtype_code(dtype), hh.st()), "conv_image")
     assert float((got - hh.nchw(out2)).abs().max()) <= 2 * ulp * float(ref.abs().max())
@@ -336,7 +336,7 @@ def test_gn_apply_resblock_tail_and_basicblock_tail(dtype):
     gad, bad = ga.to(hh.DEV), ba.to(hh.DEV)
     A.a = hh.make_src(ad, c, gn=(sa, gad, bad, 8), act=cabi.ACT_SILU)
     A.b = hh.make_src(rd, c)
-    out = torch.empty(B, H, W, c, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H, W, c, dtype=hh.TDT[dtype])
     A.out, A.B, A.H, A.W, A.dtype = out.data_ptr(), B, H, W, cabi.dtype_code(dtype)
     cabi.check(cabi.lib().ld_gn_apply(C.byref(A), hh.st()), "gn_apply")
     assert hh.rel_err(hh.nchw(out), ref) < hh.RTOL[dtype]
@@ -349,7 +349,7 @@ def test_gn_apply_resblock_tail_and_basicblock_tail(dtype):
     A.a = hh.make_src(ad, c, gn=(sa, gad, bad, 16))
     A.b = hh.make_src(rd, c, gn=(sr, grd, brd, 16))
     A.final_act, A.pool = cabi.ACT_RELU, 1
-    out = torch.empty(B, H // 2, W // 2, c, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H // 2, W // 2, c, dtype=hh.TDT[dtype])
     A.out, A.B, A.H, A.W, A.dtype = out.data_ptr(), B, H, W, cabi.dtype_code(dtype)
     cabi.check(cabi.lib().ld_gn_apply(C.byref(A), hh.st()), "gn_apply")
     assert hh.rel_err(hh.nchw(out), ref) < hh.RTOL[dtype]
@@ -366,7 +366,7 @@ def test_full_attention(dtype, n_hw):
     q, k, v = [t.reshape(B, 4, 32, n).transpose(-1, -2) for t in qkv.chunk(3, dim=1)]
     att = (q @ k.transpose(-1, -2)).softmax(dim=-1) @ v            # q is taken as pre-scaled
     ref = att.transpose(-1, -2).reshape(B, hid, H, W)
-    out = torch.empty(B, H, W, hid, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H, W, hid, dtype=hh.TDT[dtype])
     qd = hh.nhwc(qkv, dtype)
     cabi.check(cabi.lib().ld_attention(qd.data_ptr(), out.data_ptr(), B, n, 4, 32, cabi.dtype_code(dtype), hh.st()), "attention")
     assert hh.rel_err(hh.nchw(out), ref) < hh.RTOL[dtype]
@@ -393,7 +393,7 @@ def test_full_attention_two_key_groups(dtype, B, n_hw):
         cabi.check(lib.ld_tuning_set(b"attn_split_min_n", 256), "tuning_set")
         for name, wgs in (("split", 1 << 30), ("one", 0)):
             cabi.check(lib.ld_tuning_set(b"attn_split_max_wgs", wgs), "tuning_set")
-            out = torch.empty(B, H, W, hid, dtype=hh.TDT[dtype], device=hh.DEV)
+            out = hh.nans(B, H, W, hid, dtype=hh.TDT[dtype])
             cabi.check(lib.ld_attention(qd.data_ptr(), out.data_ptr(), B, n, 4, 32, cabi.dtype_code(dtype), hh.st()), "attention")
             outs[name] = hh.nchw(out)
             assert hh.rel_err(outs[name], ref) < hh.RTOL[dtype], name
@@ -422,7 +422,7 @@ def test_full_attention_split_thresholds_never_leave_a_key_group_empty(dtype, n_
     try:
         cabi.check(lib.ld_tuning_set(b"attn_split_min_n", 0), "tuning_set")
         cabi.check(lib.ld_tuning_set(b"attn_split_max_wgs", 1 << 30), "tuning_set")
-        out = torch.empty(B, H, W, hid, dtype=hh.TDT[dtype], device=hh.DEV)
+        out = hh.nans(B, H, W, hid, dtype=hh.TDT[dtype])
         cabi.check(lib.ld_attention(qd.data_ptr(), out.data_ptr(), B, n, 4, 32, cabi.dtype_code(dtype), hh.st()), "attention")
         got = hh.nchw(out)
     finally:
@@ -452,9 +452,9 @@ def test_linear_attention_block(dtype, c, H, W):
     kmax2 = torch.zeros(B, cabi.STAT_STRIPES, hid, dtype=torch.int32, device=hh.DEV)  # stand-alone kernel, same result
     cabi.check(lib.ld_linattn_kmax(qkv.data_ptr(), kmax2.data_ptr(), B, n, 4, 32, dt, hh.st()), "kmax")
     nchunks = max(1, min(32, n // 256))
-    ctxn = torch.empty(B, 4, 32, 32, device=hh.DEV)
-    ctx = torch.empty(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)), device=hh.DEV)
-    wfold = torch.empty(B, c * hid, dtype=hh.TDT[dtype], device=hh.DEV)
+    ctxn = hh.nans(B, 4, 32, 32)
+    ctx = hh.nans(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)))
+    wfold = hh.nans(B, c * hid, dtype=hh.TDT[dtype])
     wout = sd["a.to_out.0.weight"].reshape(c, hid).contiguous().to(hh.DEV)
     cabi.check(lib.ld_linattn_ctx(qkv.data_ptr(), kmax.data_ptr(), ctx.data_ptr(), B, n, 4, 32, nchunks, dt, hh.st()), "ctx")
     cabi.check(lib.ld_linattn_ctx_reduce(ctx.data_ptr(), nchunks, ctxn.data_ptr(), B, 4, 32, hh.st()), "reduce")
@@ -487,7 +487,7 @@ def test_time_mlp_and_film():
     half = dim // 2
     freqs = torch.exp(torch.arange(half) * -(math.log(10000.0) / (half - 1))).to(hh.DEV)
     td_ = {k: v.to(hh.DEV) for k, v in sd.items()}
-    temb = torch.empty(n, td, device=hh.DEV)
+    temb = hh.nans(n, td)
     tdev = times.to(hh.DEV, torch.int32)
     lib = cabi.lib()
     cabi.check(lib.ld_time_mlp(tdev.data_ptr(), n, freqs.data_ptr(), dim, td_["time_mlp.1.weight"].data_ptr(),
@@ -496,7 +496,7 @@ def test_time_mlp_and_film():
     assert hh.rel_err(temb.cpu(), ref) < 2e-5
     w, b = hh.rand((two_c, td), 84, -0.1, 0.1), hh.rand((two_c,), 85)
     fref = F.linear(F.silu(ref), w, b)
-    film = torch.empty(n, two_c, device=hh.DEV)
+    film = hh.nans(n, two_c)
     wd, bd = w.to(hh.DEV), b.to(hh.DEV)
     cabi.check(lib.ld_film(temb.data_ptr(), n, td, wd.data_ptr(), bd.data_ptr(), two_c, film.data_ptr(), hh.st()), "film")
     assert hh.rel_err(film.cpu(), fref) < 2e-5
@@ -505,7 +505,7 @@ def test_time_mlp_and_film():
 # ------------------------------------------------------------------------------ pointwise / sampler kernels
 def test_randn_matches_host_stream():
     n = 1 << 16
-    out = torch.empty(n, device=hh.DEV)
+    out = hh.nans(n)
     tdev = torch.tensor([7], dtype=torch.int32, device=hh.DEV)
     cabi.check(cabi.lib().ld_randn(out.data_ptr(), n, 10, 3, 0, None, hh.st()), "randn")
     ref = torch.from_numpy(rng.randn((n,), 10, 3))
@@ -517,7 +517,7 @@ def test_randn_matches_host_stream():
 def test_randn_at_is_a_slice_of_the_draw():
     """ld_randn_at(first, n) == ld_randn[first : first + n] bit for bit (sub-batches draw their part of a batch's noise)."""
     n, first, m = 1 << 14, 5000, 3000
-    full, part = torch.empty(n, device=hh.DEV), torch.empty(m, device=hh.DEV)
+    full, part = hh.nans(n), hh.nans(m)
     tdev = torch.tensor([7], dtype=torch.int32, device=hh.DEV)
     cabi.check(cabi.lib().ld_randn(full.data_ptr(), n, 10, 100, -1, tdev.data_ptr(), hh.st()), "randn")
     cabi.check(cabi.lib().ld_randn_at(part.data_ptr(), m, first, 10, 100, -1, tdev.data_ptr(), hh.st()), "randn_at")
@@ -536,11 +536,11 @@ def test_final_step_at_matches_the_batch_call(dtype):
     xt = hh.rand((B, cout, H, W), 114, -1, 1).to(hh.DEV)
     for t, base in ((7, 13 + 7), (0, 20)):
         tdev = torch.tensor([t], dtype=torch.int32, device=hh.DEV)
-        mo1, x1, x01 = torch.empty_like(xt), xt.clone(), torch.empty_like(xt)
+        mo1, x1, x01 = torch.full_like(xt, hh.NAN), xt.clone(), torch.full_like(xt, hh.NAN)
         cabi.check(lib.ld_final_step(x.data_ptr(), w.data_ptr(), b.data_ptr(), mo1.data_ptr(), x1.data_ptr(), x01.data_ptr(),
                                      sched.data_ptr(), tdev.data_ptr(), 0.0, 2.0, 0, 10, base - t if t > 0 else 0,
                                      B, H, W, cin, cout, cabi.dtype_code(dtype), hh.st()), "final_step")
-        mo2, x2, x02 = torch.empty_like(xt), xt.clone(), torch.empty_like(xt)
+        mo2, x2, x02 = torch.full_like(xt, hh.NAN), xt.clone(), torch.full_like(xt, hh.NAN)
         h = B // 2
         for i in range(2):
             cabi.check(lib.ld_final_step_at(x[i * h:].data_ptr(), w.data_ptr(), b.data_ptr(), mo2[i * h:].data_ptr(),
@@ -572,7 +572,7 @@ def test_ddpm_step(objective):
         if t > 0:
             ref = ref + (0.5 * buf["posterior_log_variance_clipped"][t]).exp() * z
         xd, md, zd = x.to(hh.DEV), mo.to(hh.DEV), z.to(hh.DEV)
-        out, x0o = torch.empty_like(xd), torch.empty_like(xd)
+        out, x0o = torch.full_like(xd, hh.NAN), torch.full_like(xd, hh.NAN)
         tdev = torch.tensor([t], dtype=torch.int32, device=hh.DEV)
         cabi.check(cabi.lib().ld_ddpm_step(xd.data_ptr(), md.data_ptr(), zd.data_ptr(), out.data_ptr(), x0o.data_ptr(),
                                            table.data_ptr(), tdev.data_ptr(), 0.0, 2.0, cabi.OBJ[objective], xd.numel(),
@@ -590,7 +590,7 @@ def test_branch_and_fusion_kernels():
     mask[:, :, 0, 5] = 0.7
     binary = (mask >= 1).float()
     cd, md = cond.to(hh.DEV), mask.to(hh.DEV)
-    co, ci = torch.empty_like(cd), torch.empty_like(cd)
+    co, ci = torch.full_like(cd, hh.NAN), torch.full_like(cd, hh.NAN)
     cabi.check(lib.ld_branch_conditions(cd.data_ptr(), md.data_ptr(), co.data_ptr(), ci.data_ptr(), 0.95, B, Cc, HW, hh.st()), "bc")
     assert torch.equal(co.cpu(), cond * binary) and torch.equal(ci.cpu(), cond * torch.clip(1 - binary, 0.95, 1.0))
     mo = hh.rand((B, Cc, H, H), 94, -1, 3)
@@ -602,7 +602,7 @@ def test_branch_and_fusion_kernels():
     a, b_ = xo * binary, xi * (1 - binary)
     xref = torch.where(a == 0, b_, a)
     d = [t.to(hh.DEV) for t in (xo, xi, p0o, p0i)]
-    xd, x0d = torch.empty_like(d[0]), torch.empty_like(d[0])
+    xd, x0d = torch.full_like(d[0], hh.NAN), torch.full_like(d[0], hh.NAN)
     cabi.check(lib.ld_fuse_ddpm(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), md.data_ptr(),
                                 xd.data_ptr(), x0d.data_ptr(), 0.0, 2.0, B, Cc, HW, hh.st()), "fuse")
     assert torch.equal(xd.cpu(), xref) and float((x0d.cpu() - x0).abs().max()) < 1e-6
@@ -613,7 +613,7 @@ def test_branch_and_fusion_kernels():
         masks[k].view(H, H)[:, 2 * k:2 * k + 2] = 1.0
     patches = hh.rand((B, K, Cc, HW), 99)
     ref = (patches * masks[None, :, None, :]).sum(1).reshape(B, Cc, H, H)
-    pd, mk, od = patches.to(hh.DEV), masks.to(hh.DEV), torch.empty(B, Cc, H, H, device=hh.DEV)
+    pd, mk, od = patches.to(hh.DEV), masks.to(hh.DEV), hh.nans(B, Cc, H, H)
     cabi.check(lib.ld_recompose(pd.data_ptr(), mk.data_ptr(), od.data_ptr(), B, K, Cc, HW, hh.st()), "recompose")
     assert float((od.cpu() - ref).abs().max()) < 1e-6
 
@@ -623,7 +623,7 @@ def test_final_conv(dtype):
     B, cin, cout, H, W = 2, 32, 3, 9, 13
     x, w, b = _q(hh.rand((B, cin, H, W), 100), dtype), hh.rand((cout, cin, 1, 1), 101, -0.3, 0.3), hh.rand((cout,), 102)
     ref = F.conv2d(x, w, b)
-    out = torch.empty(B, cout, H, W, device=hh.DEV)
+    out = hh.nans(B, cout, H, W)
     xd, wd, bd = hh.nhwc(x, dtype), w.reshape(cout, cin).contiguous().to(hh.DEV), b.to(hh.DEV)
     cabi.check(cabi.lib().ld_final_conv(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), out.data_ptr(), B, H, W, cin, cout,
                                         cabi.dtype_code(dtype), hh.st()), "final_conv")
@@ -653,15 +653,15 @@ def test_linear_attention_fused_16bit(dtype, c, H, W, single_sweep):
     wkv = torch.cat([hh.pack(torch.cat([w[hid + 32 * h: hid + 32 * h + 32], w[2 * hid + 32 * h: 2 * hid + 32 * h + 32]], 0).contiguous(),
                              dtype, 1, scale_in=scale) for h in range(4)]).contiguous()
     nchunks = max(1, min(32, n // 256))
-    ctx = torch.empty(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)), device=hh.DEV)
-    ctxn = torch.empty(B, 4, 32, 32, device=hh.DEV)
-    wfold = torch.empty(B, c * hid, dtype=hh.TDT[dtype], device=hh.DEV)
+    ctx = hh.nans(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)))
+    ctxn = hh.nans(B, 4, 32, 32)
+    wfold = hh.nans(B, c * hid, dtype=hh.TDT[dtype])
     wout = sd["a.to_out.0.weight"].reshape(c, hid).contiguous().to(hh.DEV)
     kshift = None
     if single_sweep:   # |k_d| <= ||W_k[d] * g * sqrt(C)||_2 because the RMS-normalised pixel has unit 2-norm
         kshift = (w[hid:2 * hid, :, 0, 0] * scale[None, :]).norm(dim=1).contiguous().to(hh.DEV)
         nchunks = max(1, min(128, n // 512))
-        ctx = torch.empty(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)), device=hh.DEV)
+        ctx = hh.nans(int(lib.ld_linattn_ctx_part_floats(B, 4, 32, nchunks)))
     cabi.check(lib.ld_linattn_kvctx(xd.data_ptr(), wkv.data_ptr(), None if kshift is None else kshift.data_ptr(), ctx.data_ptr(),
                                     B, n, c, 4, 32, nchunks, dt, hh.st()), "kvctx")
     cabi.check(lib.ld_linattn_ctx_reduce(ctx.data_ptr(), nchunks, ctxn.data_ptr(), B, 4, 32, hh.st()), "reduce")
@@ -676,7 +676,7 @@ def test_linear_attention_fused_16bit(dtype, c, H, W, single_sweep):
         cabi.check(lib.ld_linattn_ctxfold(ctx.data_ptr(), nchunks, wout.data_ptr(), wfold2.data_ptr(), B, c, 4, 32, 1, dt, hh.st()), "ctxfold")
         assert hh.rel_err(wfold2.float().cpu(), wfold.float().cpu()) < 1e-2 * f
         wfold = wfold2
-    out = torch.empty(B, H, W, c, dtype=hh.TDT[dtype], device=hh.DEV)
+    out = hh.nans(B, H, W, c, dtype=hh.TDT[dtype])
     bias, g2 = sd["a.to_out.0.bias"].to(hh.DEV), (sd["a.to_out.1.g"].flatten() * math.sqrt(c)).to(hh.DEV)
     qshift = None
     if single_sweep:
@@ -894,7 +894,7 @@ def test_two_term_weights_remove_the_weight_rounding(dtype):
 
     def packed(w, k, terms):
         w = w.to(hh.DEV, torch.float32).contiguous()
-        out = torch.empty(terms * w.numel(), dtype=hh.TDT[dtype], device=hh.DEV)
+        out = hh.nans(terms * w.numel(), dtype=hh.TDT[dtype])
         cabi.check(lib.ld_pack_conv_weight_terms(w.data_ptr(), None, out.data_ptr(), w.shape[0], w.shape[1], k, 0,
                                                  cabi.dtype_code(dtype), terms, hh.st()), "pack")
         return out
@@ -907,7 +907,7 @@ def test_two_term_weights_remove_the_weight_rounding(dtype):
         s1, s2 = hh.make_src(hh.nhwc(x1, dtype), c1, ups=1), hh.make_src(hh.nhwc(x2, dtype), c2)
         a.src[0], a.src[1], a.nsrc = s1, s2, 2
         wp, bd = packed(w, 3, terms), b.to(hh.DEV)
-        out = torch.empty(B, H, W, cout, dtype=hh.TDT[dtype], device=hh.DEV)
+        out = hh.nans(B, H, W, cout, dtype=hh.TDT[dtype])
         a.weight, a.bias, a.out, a.weight_terms = wp.data_ptr(), bd.data_ptr(), out.data_ptr(), terms
         a.B, a.H, a.W, a.Cout, a.dtype = B, H, W, cout, cabi.dtype_code(dtype)
         cabi.check(lib.ld_conv3x3(C.byref(a), hh.st()), "conv3x3")
@@ -929,7 +929,7 @@ def test_two_term_weights_remove_the_weight_rounding(dtype):
         s1, s2 = hh.make_src(hh.nhwc(y1, dtype), c1), hh.make_src(hh.nhwc(y2, dtype), c2)
         a.src[0], a.src[1], a.nsrc = s1, s2, 2
         wp, bd = packed(w1, 1, terms), b1.to(hh.DEV)
-        out = torch.empty(B, H, W, cout, dtype=hh.TDT[dtype], device=hh.DEV)
+        out = hh.nans(B, H, W, cout, dtype=hh.TDT[dtype])
         a.weight, a.bias, a.out, a.weight_terms = wp.data_ptr(), bd.data_ptr(), out.data_ptr(), terms
         a.epilogue, a.hidden, a.q_scale, a.gn_tail = cabi.EPI_GN_TAIL, 128, 32 ** -0.5, tail
         a.B, a.H, a.W, a.Cout, a.dtype = B, H, W, cout, cabi.dtype_code(dtype)
