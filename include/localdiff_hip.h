@@ -962,6 +962,22 @@ int ld_dn_opt_layout(ld_dn_opt_tensor* tensors, int n_tensors, int64_t* flat_flo
 int64_t ld_dn_opt_sqnorm_work_bytes(int n_wg);
 int ld_dn_opt_sqnorm(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, const float* grad, int64_t flat_floats, double* work,
                      double* sumsq, void* stream);
+/* Data-parallel training: ld_dn_opt_reduce in the place of ld_dn_opt_sqnorm.  gathered (device) holds `world` copies of the
+ * flat gradient, rank r's at gathered + r * rank_stride (what an all-gather of the ranks' buffers leaves).  Per element i of
+ * every LD_DN_OPT_ADAM entry: g = gathered[i], then g += gathered[r * rank_stride + i] for r = 1 .. world - 1 -- plain fp32
+ * additions in that order, whatever the world size -- and grad[i] = g; the squares of g go into the per-workgroup fp64
+ * partials in ld_dn_opt_sqnorm's order, and the same second launch adds them: *sumsq and work hold the bits that
+ * ld_dn_opt_sqnorm gives on the reduced buffer.  Entries without LD_DN_OPT_ADAM and the padding between segments are neither
+ * read in gathered nor written in grad.  grad is a buffer of its own or one rank's copy (gathered + r * rank_stride): a thread
+ * stores only elements it has loaded from every copy.  Refused with -1 before anything is launched: world outside 1 ..
+ * LD_DN_OPT_MAX_WORLD, rank_stride below flat_floats or no multiple of 4, gathered or grad off the 16-byte grid (table, work,
+ * sumsq: 8 bytes), a grad that overlaps gathered in any other way. */
+#define LD_DN_OPT_MAX_WORLD 64
+int ld_dn_opt_reduce(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, const float* gathered, int world, int64_t rank_stride,
+                     float* grad, int64_t flat_floats, double* work, double* sumsq, void* stream);
+/* The loss tail of the same exchange: *out (device) = gathered[at], then += gathered[r * rank_stride + at] for r = 1 ..
+ * world - 1, by one thread; 0 <= at < rank_stride.  Nothing else of gathered is read. */
+int ld_dn_opt_reduce_tail(const float* gathered, int world, int64_t rank_stride, int64_t at, float* out, void* stream);
 /* One launch over the table.  coef = min(1, max_norm / (sqrt(*sumsq) + 1e-6)) (clip_grad_norm_; *sumsq is read on the device,
  * and a NaN norm gives a NaN coef as torch's clamp does); per element of an LD_DN_OPT_ADAM entry ld_seg_adam's update from
  * g coef (step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) from the host in double, 1 - beta rounded to fp32

@@ -85,7 +85,7 @@ class DnOptTensor(C.Structure):
     _fields_ = [("param", vp), ("count", i64), ("offset", i64), ("first_wg", i32), ("flags", i32)]
 
 
-DN_OPT_CHUNK, DN_OPT_ADAM = 4096, 1     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM
+DN_OPT_CHUNK, DN_OPT_ADAM, DN_OPT_MAX_WORLD = 4096, 1, 64     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM, LD_DN_OPT_MAX_WORLD
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
 _SIGS = {
@@ -255,6 +255,8 @@ _SIGS = {
     "ld_dn_opt_layout": (C.c_int, [C.POINTER(DnOptTensor), C.c_int, C.POINTER(i64), C.POINTER(i64)]),
     "ld_dn_opt_sqnorm_work_bytes": (i64, [C.c_int]),
     "ld_dn_opt_sqnorm": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, vp, vp, vp]),
+    "ld_dn_opt_reduce": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, i64, vp, i64, vp, vp, vp]),
+    "ld_dn_opt_reduce_tail": (C.c_int, [vp, C.c_int, i64, i64, vp, vp]),
     "ld_dn_opt_step": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_int, f32, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),

@@ -13,6 +13,10 @@
 // takes partials t, t + 256, .. in index order, then the tree and the waves): an order that depends on the sizes alone.  No
 // atomics, nothing allocates, the norm never leaves the device: the step reads it from memory.  Adam's arithmetic is
 // seg_adam_kernel's (segtrain.hip), applied to g * coef.
+//
+// Data-parallel training puts ld_dn_opt_reduce in the place of ld_dn_opt_sqnorm: the ranks all-gather their flat gradients,
+// and one launch adds the copies in rank order (plain fp32, left to right) while it gathers the norm's partials, so every
+// rank steps on the same bits and a W-rank step equals a one-rank step that accumulated the W shards in order.
 #include "common.hip.h"
 #include "dn_common.hip.h"
 
@@ -173,6 +177,97 @@ __global__ __launch_bounds__(OPT_BS) void opt_step_kernel(const ld_dn_opt_tensor
   }
 }
 
+// ---------------------------------------------------------------- data-parallel: the rank-ordered sum of the gathered gradients
+// gathered holds `world` copies of the flat gradient, rank r's at r * stride.  Per element g = copy 0, then += copy 1, 2, ..
+// in plain fp32; grad = g, and the workgroup's fp64 partial of g * g is gathered exactly as opt_sqnorm_kernel gathers it (the
+// same chunk, the same per-thread order, the same block sum), so the second launch gives the bits ld_dn_opt_sqnorm gives on
+// the reduced buffer.  W > 0: world is W, every copy's 16-byte load is issued before the first add; W == 0: any world, the
+// copies in batches of RB loads.  grad may be a rank's own slice of gathered: a thread stores only the elements it has
+// loaded from every copy, so neither pointer is __restrict__.
+constexpr int OPT_RB = 8;
+
+template <int W>
+__device__ __forceinline__ float4 opt_sum4(const float* src, int world, long stride) {
+  if constexpr (W > 0) {
+    float4 q[W];
+#pragma unroll
+    for (int r = 0; r < W; ++r) q[r] = ld4(src + (long)r * stride);
+    float4 g = q[0];
+#pragma unroll
+    for (int r = 1; r < W; ++r) {
+      g.x += q[r].x;
+      g.y += q[r].y;
+      g.z += q[r].z;
+      g.w += q[r].w;
+    }
+    return g;
+  } else {
+    float4 g = ld4(src);
+    for (int r0 = 1; r0 < world; r0 += OPT_RB) {
+      float4 q[OPT_RB];
+#pragma unroll
+      for (int j = 0; j < OPT_RB; ++j) {
+        const int r = r0 + j < world ? r0 + j : world - 1;           // (a repeated load of the last copy, not added)
+        q[j] = ld4(src + (long)r * stride);
+      }
+#pragma unroll
+      for (int j = 0; j < OPT_RB; ++j) {
+        if (r0 + j < world) {
+          g.x += q[j].x;
+          g.y += q[j].y;
+          g.z += q[j].z;
+          g.w += q[j].w;
+        }
+      }
+    }
+    return g;
+  }
+}
+
+template <int W>
+__global__ __launch_bounds__(OPT_BS) void opt_reduce_kernel(const ld_dn_opt_tensor* __restrict__ tab, int n, const float* gathered,
+                                                            int world_rt, long stride, float* grad, long flat,
+                                                            double* __restrict__ partial) {
+  __shared__ double red[OPT_BS / 64];
+  const int world = W > 0 ? W : world_rt;
+  OptChunk c;
+  double acc = 0.0;
+  if (opt_chunk(tab, n, flat, c) && (c.e.flags & LD_DN_OPT_ADAM)) {
+    const float* src = gathered + c.e.offset;
+    float* g = grad + c.e.offset;
+#pragma unroll
+    for (int k = 0; k < OPT_LANES; ++k) {
+      const long i = c.lo + 4L * (k * OPT_BS + (int)threadIdx.x);
+      if (i >= c.hi) continue;
+      if (i + 4 <= c.hi) {
+        const float4 q = opt_sum4<W>(src + i, world, stride);
+        opt_store4(g + i, q);
+        acc += (double)q.x * (double)q.x;
+        acc += (double)q.y * (double)q.y;
+        acc += (double)q.z * (double)q.z;
+        acc += (double)q.w * (double)q.w;
+      } else {
+        for (long j = i; j < c.hi; ++j) {
+          float v = src[j];
+          for (int r = 1; r < world; ++r) v += src[(long)r * stride + j];
+          g[j] = v;
+          acc += (double)v * (double)v;
+        }
+      }
+    }
+  }
+  const double s = opt_block_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// the loss tail: *out = slot `at` of copy 0, then += copy 1, 2, .. (one thread)
+__global__ void opt_reduce_tail_kernel(const float* __restrict__ gathered, int world, long stride, long at, float* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float v = gathered[at];
+  for (int r = 1; r < world; ++r) v += gathered[(long)r * stride + at];
+  *out = v;
+}
+
 inline bool opt_sizes_ok(int n_tensors, int n_wg, int64_t flat) {
   return n_tensors > 0 && n_tensors <= LD_DN_OPT_MAX_TENSORS && n_wg >= n_tensors && flat >= 4 && flat % 4 == 0 &&
          flat < (1LL << 40);
@@ -220,6 +315,47 @@ extern "C" int ld_dn_opt_sqnorm(const ld_dn_opt_tensor* table, int n_tensors, in
   LD_LAUNCH(opt_sqnorm_kernel, dim3((unsigned)n_wg), dim3(OPT_BS), 0, st, table, n_tensors, grad, (long)flat_floats, work);
   LD_LAUNCH(opt_sqnorm_final_kernel, dim3(1), dim3(OPT_BS), 0, st, (const double*)work, n_wg, sumsq);
   LD_LAUNCH_CHECK("dn_opt_sqnorm");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_opt_reduce(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, const float* gathered, int world,
+                                int64_t rank_stride, float* grad, int64_t flat_floats, double* work, double* sumsq, void* stream) {
+  LD_REQUIRE(opt_sizes_ok(n_tensors, n_wg, flat_floats), "ld_dn_opt_reduce: %d tensors, %d workgroups, %lld floats (at least one "
+             "tensor, a workgroup per tensor, a multiple of 4 floats)", n_tensors, n_wg, (long long)flat_floats);
+  LD_REQUIRE(world >= 1 && world <= LD_DN_OPT_MAX_WORLD, "ld_dn_opt_reduce: world %d (1..%d)", world, LD_DN_OPT_MAX_WORLD);
+  LD_REQUIRE(rank_stride >= flat_floats && rank_stride % 4 == 0 && rank_stride < (1LL << 40),
+             "ld_dn_opt_reduce: rank_stride %lld (a multiple of 4 floats, at least flat_floats = %lld)", (long long)rank_stride,
+             (long long)flat_floats);
+  LD_REQUIRE(table && gathered && grad && work && sumsq, "ld_dn_opt_reduce: null pointer");
+  LD_REQUIRE(dn_aligned16(gathered) && dn_aligned16(grad) && ((uintptr_t)table | (uintptr_t)work | (uintptr_t)sumsq) % 8 == 0,
+             "ld_dn_opt_reduce: a pointer is not aligned (gathered and grad 16 bytes; the table, work and sumsq 8)");
+  const uintptr_t g0 = (uintptr_t)gathered, g1 = g0 + (uintptr_t)world * (uintptr_t)rank_stride * 4, d0 = (uintptr_t)grad;
+  const bool apart = d0 + (uintptr_t)flat_floats * 4 <= g0 || d0 >= g1;
+  LD_REQUIRE(apart || (d0 >= g0 && (d0 - g0) % ((uintptr_t)rank_stride * 4) == 0),
+             "ld_dn_opt_reduce: grad overlaps gathered without being one rank's copy");
+  hipStream_t st = dn_st(stream);
+  const dim3 grid((unsigned)n_wg), block(OPT_BS);
+  const long stride = (long)rank_stride, flat = (long)flat_floats;
+  switch (world) {
+    case 1: LD_LAUNCH(opt_reduce_kernel<1>, grid, block, 0, st, table, n_tensors, gathered, world, stride, grad, flat, work); break;
+    case 2: LD_LAUNCH(opt_reduce_kernel<2>, grid, block, 0, st, table, n_tensors, gathered, world, stride, grad, flat, work); break;
+    case 4: LD_LAUNCH(opt_reduce_kernel<4>, grid, block, 0, st, table, n_tensors, gathered, world, stride, grad, flat, work); break;
+    case 8: LD_LAUNCH(opt_reduce_kernel<8>, grid, block, 0, st, table, n_tensors, gathered, world, stride, grad, flat, work); break;
+    default: LD_LAUNCH(opt_reduce_kernel<0>, grid, block, 0, st, table, n_tensors, gathered, world, stride, grad, flat, work); break;
+  }
+  LD_LAUNCH(opt_sqnorm_final_kernel, dim3(1), dim3(OPT_BS), 0, st, (const double*)work, n_wg, sumsq);
+  LD_LAUNCH_CHECK("dn_opt_reduce");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_opt_reduce_tail(const float* gathered, int world, int64_t rank_stride, int64_t at, float* out, void* stream) {
+  LD_REQUIRE(world >= 1 && world <= LD_DN_OPT_MAX_WORLD, "ld_dn_opt_reduce_tail: world %d (1..%d)", world, LD_DN_OPT_MAX_WORLD);
+  LD_REQUIRE(rank_stride > 0 && rank_stride < (1LL << 40) && at >= 0 && at < rank_stride,
+             "ld_dn_opt_reduce_tail: slot %lld of a rank_stride of %lld floats", (long long)at, (long long)rank_stride);
+  LD_REQUIRE(gathered && out, "ld_dn_opt_reduce_tail: null pointer");
+  LD_REQUIRE(((uintptr_t)gathered | (uintptr_t)out) % 4 == 0, "ld_dn_opt_reduce_tail: a pointer is not aligned (4 bytes)");
+  LD_LAUNCH(opt_reduce_tail_kernel, dim3(1), dim3(64), 0, dn_st(stream), gathered, world, (long)rank_stride, (long)at, out);
+  LD_LAUNCH_CHECK("dn_opt_reduce_tail");
   return LD_OK;
 }
 

@@ -20,7 +20,18 @@ have no moments, are not in the norm, and are in the EMA.
 The EMA rule is ``ema_pytorch.EMA.update`` restated from its source (``ema_action``); the package is not available where
 this was built, so the rule could not be checked against it.
 
-NOT covered: 16-bit storage, more than one GPU, ``amp``, FID, writing the kernel-layout weight copies from the optimiser launch
+More than one GPU (``group=`` a torch process group, or ``comm=`` an ``LdComm``): the reference's
+``Accelerator(split_batches=True)``.  Every rank is handed the same global batches and takes its rows of each
+(``dist.shard_bounds``); a micro-batch is scaled by ``1 / (world * len(batches))``.  ``apply`` then all-gathers the ranks' flat
+gradients -- one collective of ``flat + 4`` floats per rank, whose extra slot carries the rank's summed loss -- and
+``ld_dn_opt_reduce`` adds the ``world`` copies IN RANK ORDER (plain fp32, left to right) while it gathers the squared norm in
+``ld_dn_opt_sqnorm``'s order; ``ld_dn_opt_step`` follows unchanged on identical inputs.  So the replicas hold the same bits
+after every step (``replica_digest`` checks it), and a W-rank step equals a one-rank step that accumulated the same W
+micro-batches in order.  Drawn ``t`` and noise are the rank's rows of what one rank would draw for the global batch (seed all
+ranks alike).  The gather is not overlapped with the backward pass.
+
+NOT covered: 16-bit storage, more than one node, ragged shards (a batch size that is no multiple of the world size), a sharded
+evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, ``amp``, FID, writing the kernel-layout weight copies from the optimiser launch
 (the modules repack after a step, as they do under ``torch.optim.Adam``), handing padded tensors between modules.
 """
 import ctypes as C
@@ -93,6 +104,29 @@ def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr
     return {"step": int(step), "model": model, "opt": opt, "ema": ema, "scaler": None}
 
 
+def shard_rows(n_rows, world, rank):
+    """The rows ``[lo, hi)`` of a global batch of ``n_rows`` that ``rank`` of ``world`` trains on (``dist.shard_bounds``).
+    ``ValueError`` when the shards would be ragged: their losses would need per-rank weights.  Needs no GPU."""
+    from .dist import shard_bounds
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"DenoiserTrainer: rank {rank} of a world of {world}")
+    if n_rows < world or n_rows % world:
+        raise ValueError(f"DenoiserTrainer: a batch of {n_rows} does not split evenly over {world} ranks (ragged shards are "
+                         "not built)")
+    return shard_bounds(n_rows, world, rank)
+
+
+class EmulatedRank:
+    """``comm=EmulatedRank(world, rank)``: a rank whose peers live in the same process -- it has no collective, so its
+    trainer's ``apply`` needs ``gathered=`` (tests; comparing world sizes on one GPU)."""
+
+    def __init__(self, world, rank):
+        self.world, self.rank = int(world), int(rank)
+
+    def all_gather(self, send, recv):
+        raise RuntimeError("EmulatedRank has no collective: pass apply(gathered=...)")
+
+
 def _positive(name, v, zero_ok=False):
     if not isinstance(v, (int, float)) or isinstance(v, bool) or math.isnan(v) or v < 0 or (v == 0 and not zero_ok):
         raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be a {'non-negative' if zero_ok else 'positive'} number")
@@ -104,11 +138,18 @@ class DenoiserTrainer:
     the reference's (ddpm.py:1261-1265, 1444, 1449 and ``ema_pytorch``'s).  Refused with ``ValueError`` before any GPU call:
     what ``TrainableUnet`` refuses, ``self_condition``, hyper-parameters out of range, a ``diffusion`` that is not on a GPU.
 
+    ``group`` (a torch process group, or ``"default"`` for the default one) or ``comm`` (an ``LdComm``) makes it one rank of
+    a data-parallel run (the module docstring); giving both is refused.  ``world`` and ``rank`` say which; with neither
+    (``world`` 1, ``data_parallel`` False) the trainer issues the launches it always did; a group or communicator of one rank
+    runs the data-parallel launches on its one copy, to the same bits.
+
     ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
     ``ema_initted`` are ``ema_pytorch``'s two buffers."""
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
-                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0):
+                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None):
+        if group is not None and comm is not None:
+            raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
         model = getattr(diffusion, "model", None)
         if model is None or not hasattr(model, "cfg") or not hasattr(diffusion, "p_losses_grad"):
             raise ValueError("DenoiserTrainer: diffusion must be an ldh.GaussianDiffusion around an ldh.Unet")
@@ -136,6 +177,21 @@ class DenoiserTrainer:
         self.ema_kw = dict(beta=float(ema_decay), update_every=ema_update_every, update_after_step=ema_update_after_step,
                            inv_gamma=float(ema_inv_gamma), power=float(ema_power), min_value=float(ema_min_value))
         self.step, self.ema_step, self.ema_initted, self.last_ema = 0, 0, False, None
+        self.group, self.comm, self.world, self.rank, self.staged_gather = None, comm, 1, 0, False
+        if comm is not None:
+            self.world, self.rank = int(comm.world), int(comm.rank)
+        elif group is not None:
+            import torch.distributed as tdist
+            if not (tdist.is_available() and tdist.is_initialized()):
+                raise ValueError("DenoiserTrainer: group given but torch.distributed is not initialised")
+            self.group = tdist.group.WORLD if isinstance(group, str) and group == "default" else group
+            self.world, self.rank = tdist.get_world_size(self.group), tdist.get_rank(self.group)
+            # gloo (the test-only mode of several ranks on one GPU) gathers host tensors: the exchange is staged through
+            # pinned host memory and waits for the GPU -- a functional path, never a measurement
+            self.staged_gather = tdist.get_backend(self.group) == "gloo"
+        self.data_parallel = comm is not None or group is not None       # (also at world 1: the same launches, one copy)
+        if not 1 <= self.world <= cabi.DN_OPT_MAX_WORLD or not 0 <= self.rank < self.world:
+            raise ValueError(f"DenoiserTrainer: rank {self.rank} of a world of {self.world} (1..{cabi.DN_OPT_MAX_WORLD})")
         online.load_state_dict(model.state_dict())
         self.online_model = online.to(dev)
         self._build_table()
@@ -159,7 +215,18 @@ class DenoiserTrainer:
         self._views = self._params = None
         with torch.cuda.device(dev):
             self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
-            self._grad, self._m, self._v, self._ema = (torch.zeros(self._flat, dtype=torch.float32, device=dev) for _ in range(4))
+            self._m, self._v, self._ema = (torch.zeros(self._flat, dtype=torch.float32, device=dev) for _ in range(3))
+            # what a rank sends: the flat gradient and four more floats, the first of which is its summed loss
+            self._send = torch.zeros(self._flat + 4, dtype=torch.float32, device=dev)
+            self._grad, self._loss_slot = self._send[:self._flat], self._send[self._flat:]
+            self._gathered = self._loss = None
+            if self.data_parallel:
+                self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
+                if not isinstance(self.comm, EmulatedRank):
+                    self._gathered = torch.empty(self.world, self._flat + 4, dtype=torch.float32, device=dev)
+                if self.staged_gather:
+                    self._host_send = torch.empty(self._flat + 4, dtype=torch.float32).pin_memory()
+                    self._host_recv = torch.empty(self.world, self._flat + 4, dtype=torch.float32).pin_memory()
             self._work = torch.zeros(1 + int(lib.ld_dn_opt_sqnorm_work_bytes(self._n_wg)) // 8, dtype=torch.float64, device=dev)
         with torch.no_grad():                               # ema_pytorch: the EMA model starts as a copy of the online one
             for k, p in named:
@@ -193,13 +260,17 @@ class DenoiserTrainer:
         """One batch of ddpm.py:1544-1553: adds the gradients of ``scale`` times the training loss of (``hr``, the image,
         ``lr``, the condition image) to the ``.grad``s and returns ``scale * loss`` as a 0-d device tensor.  ``t`` None: drawn
         as ``GaussianDiffusion.forward(train=True)`` draws it (torch's host generator); ``noise`` None: drawn as ``p_losses``
-        draws it (the run's noise stream, the offset noise included).  No host synchronisation."""
+        draws it (the run's noise stream, the offset noise included).  No host synchronisation.  On a rank of a
+        data-parallel run this is the local half: ``hr`` / ``lr`` are the rank's rows, given ``t`` / ``noise`` are taken as they
+        are, drawn ones are the rank's rows of the draw for the global batch of ``world`` times as many rows, and the value
+        is also added to the loss slot that travels with the gradients."""
         gd, dev, lib = self.diffusion, self.device, cabi.lib()
         if not isinstance(hr, torch.Tensor) or hr.dim() != 4:
             raise ValueError("DenoiserTrainer: hr must be a [B, C, H, W] tensor")
         B = hr.shape[0]
+        first_row = self.rank * B                           # of the global batch (equal shards)
         if t is None:
-            t = torch.randint(0, gd.num_timesteps, (B,)).long()
+            t = torch.randint(0, gd.num_timesteps, (B * self.world,)).long()[first_row:first_row + B]
         if not t.is_cuda:
             t = t.pin_memory()                              # (a pageable copy would wait for the stream)
         self._attach_grads()
@@ -208,7 +279,7 @@ class DenoiserTrainer:
             with torch.no_grad():
                 x0 = gd.normalize(hr.to(dev, torch.float32)).contiguous()
                 cond = lr.to(dev, torch.float32).contiguous()
-                noise = gd.training_noise(x0, noise)
+                noise = gd.training_noise(x0, noise, first_row=first_row)
                 t32 = t.to(torch.int32)
                 x = torch.empty_like(x0)
                 cabi.check(lib.ld_q_sample_t(x0.data_ptr(), noise.data_ptr(), x.data_ptr(), t32.data_ptr(),
@@ -223,11 +294,18 @@ class DenoiserTrainer:
                                            cabi.OBJ[gd.objective], stream(dev)), "p_losses")
                 value = per_sample.mean() * float(scale)
             out.backward(gd.p_losses_grad(out, x0, noise, t, grad_output=float(scale)))
+            if self.data_parallel:
+                self._loss_slot[0].add_(value)
         return value
 
-    def apply(self):
+    def apply(self, gathered=None):
         """ddpm.py:1558-1571: clip the accumulated gradients to ``max_grad_norm``, Adam, zero the gradients, ``ema.update()``
-        -- two launches -- and move every parameter's version so that the modules repack their weights.  Nothing waits."""
+        -- two launches -- and move every parameter's version so that the modules repack their weights.  Nothing waits.
+
+        ``data_parallel``: one all-gather of the rank's ``flat + 4`` floats, then ``ld_dn_opt_reduce`` (the rank-ordered sum into
+        the rank's own gradient and the squared norm; ``ld_dn_opt_sqnorm`` is not launched), the loss tail, and
+        ``ld_dn_opt_step`` as ever; returns the step's loss summed over the ranks (a 0-d device tensor, the same bits on every
+        rank).  ``gathered``: a ready ``[world, flat + 4]`` fp32 device tensor to use in place of the collective (tests)."""
         dev, lib = self.device, cabi.lib()
         self._attach_grads()
         t = self.step + 1
@@ -237,11 +315,29 @@ class DenoiserTrainer:
         mode, decay = ema_action(self.ema_step, initted=self.ema_initted, **self.ema_kw)
         if self.ema_step % self.ema_kw["update_every"] == 0 and self.ema_step > self.ema_kw["update_after_step"]:
             self.ema_initted = True
+        loss = None
         with torch.cuda.device(dev):
             st = stream(dev)
             sumsq = self._work.data_ptr()
-            cabi.check(lib.ld_dn_opt_sqnorm(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._flat,
-                                            sumsq + 8, sumsq, st), "dn_opt_sqnorm")
+            if not self.data_parallel and gathered is None:
+                cabi.check(lib.ld_dn_opt_sqnorm(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._flat,
+                                                sumsq + 8, sumsq, st), "dn_opt_sqnorm")
+            else:
+                stride = self._flat + 4
+                if gathered is None:
+                    gathered = self._exchange()
+                elif not (isinstance(gathered, torch.Tensor) and gathered.dtype == torch.float32 and gathered.is_contiguous()
+                          and gathered.device == self._send.device and tuple(gathered.shape) == (self.world, stride)):
+                    raise ValueError(f"DenoiserTrainer: gathered must be a contiguous [{self.world}, {stride}] fp32 tensor on "
+                                     f"{self._send.device}")
+                if self._loss is None:
+                    self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
+                cabi.check(lib.ld_dn_opt_reduce(self._table.data_ptr(), self._n, self._n_wg, gathered.data_ptr(), self.world,
+                                                stride, self._grad.data_ptr(), self._flat, sumsq + 8, sumsq, st), "dn_opt_reduce")
+                cabi.check(lib.ld_dn_opt_reduce_tail(gathered.data_ptr(), self.world, stride, self._flat,
+                                                     self._loss.data_ptr(), st), "dn_opt_reduce_tail")
+                self._loss_slot.zero_()
+                loss = self._loss[0].clone()
             cabi.check(lib.ld_dn_opt_step(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._m.data_ptr(),
                                           self._v.data_ptr(), self._ema.data_ptr(), self._flat, sumsq, self.max_grad_norm, b1, b2,
                                           self.eps, step_size, bc2_sqrt, mode, 1.0 - decay, st), "dn_opt_step")
@@ -250,19 +346,74 @@ class DenoiserTrainer:
         self.last_ema = (mode, decay)                       # what the launch was told: (EMA_KEEP / EMA_COPY / EMA_LERP, decay)
         self.step += 1
         self.ema_step += 1
+        return loss
+
+    def send_buffer(self):
+        """What this rank contributes to the exchange: ``flat + 4`` floats, the flat gradient and the loss slot (a view)."""
+        return self._send
+
+    def _exchange(self):
+        """The one collective of a step: every rank's send buffer into ``[world, flat + 4]``."""
+        with cabi.prof_range("exchange"):
+            if self.comm is not None:
+                self.comm.all_gather(self._send, self._gathered)
+            elif self.staged_gather:                       # gloo: through pinned host memory (waits for the GPU; test-only)
+                import torch.distributed as tdist
+                self._host_send.copy_(self._send)
+                tdist.all_gather_into_tensor(self._host_recv.view(-1), self._host_send, group=self.group)
+                self._gathered.copy_(self._host_recv)
+            else:
+                import torch.distributed as tdist
+                tdist.all_gather_into_tensor(self._gathered.view(-1), self._send, group=self.group)
+        return self._gathered
 
     def train_step(self, batches):
         """The reference's step: ``accumulate(hr, lr, scale=1 / len(batches))`` over all ``(hr, lr)`` batches, ``apply()``;
-        returns the summed loss (the reference's ``total_loss``) on the device."""
+        returns the summed loss (the reference's ``total_loss``) on the device.  ``data_parallel`` (``split_batches=True``):
+        every rank is handed the same global batches and takes its rows of each, the scale is ``1 / (world * len(batches))``
+        and the loss is the sum over the ranks; a batch size that is no multiple of ``world`` is a ``ValueError``."""
         batches = list(batches)
         if not batches:
             raise ValueError("DenoiserTrainer: no batches")
+        if self.data_parallel:
+            rows = [shard_rows(int(hr.shape[0]), self.world, self.rank) for hr, _ in batches]      # (before any GPU call)
+            for (hr, lr), (lo, hi) in zip(batches, rows):
+                self.accumulate(hr[lo:hi], lr[lo:hi], scale=1.0 / (self.world * len(batches)))
+            return self.apply()
         total = None
         for hr, lr in batches:
             value = self.accumulate(hr, lr, scale=1.0 / len(batches))
             total = value if total is None else total + value
         self.apply()
         return total
+
+    def replica_digest(self):
+        """A debugging call that waits for the GPU: ``(sumsq, weight sum, weight xor)`` -- the last step's squared gradient
+        norm, the fp64 sum of the online weights and the xor of their bit patterns -- gathered from every rank;
+        ``RuntimeError`` naming the first rank whose numbers are not rank 0's, else the digest."""
+        import numpy as np
+        with torch.no_grad():
+            w = torch.cat([p.detach().reshape(-1) for p in self.online_model.parameters()]).cpu().numpy()
+            mine = np.array([float(self._work[0].item()) if self.step else 0.0, np.sum(w, dtype=np.float64),
+                             float(np.bitwise_xor.reduce(w.view(np.uint32)))], dtype=np.float64)
+            every = torch.from_numpy(mine.view(np.int64).copy())[None]            # bit patterns: a NaN compares like any value
+            if self.world > 1 and not isinstance(self.comm, EmulatedRank):
+                recv = torch.empty(self.world, 3, dtype=torch.int64, device=self.device)
+                if self.comm is not None:
+                    with torch.cuda.device(self.device):
+                        self.comm.all_gather(every[0].to(self.device), recv)
+                else:
+                    import torch.distributed as tdist
+                    if self.staged_gather:
+                        recv = recv.cpu()
+                    tdist.all_gather_into_tensor(recv.view(-1), every[0].to(recv.device), group=self.group)
+                every = recv.cpu()
+        for r in range(every.shape[0]):
+            if not torch.equal(every[r], every[0]):
+                got, want = every[r].numpy().view(np.float64), every[0].numpy().view(np.float64)
+                raise RuntimeError(f"DenoiserTrainer: rank {r} differs from rank 0 after step {self.step}: (sumsq, weight sum, "
+                                   f"weight xor) = {got.tolist()} against {want.tolist()}")
+        return dict(step=self.step, sumsq=float(mine[0]), weight_sum=float(mine[1]), weight_xor=int(mine[2]))
 
     def check_finite(self):
         """Read the last step's gradient norm back (the one place that does) and raise on a non-finite value; returns it."""
@@ -355,7 +506,9 @@ class DenoiserTrainer:
         ``<out_dir>/model-best<step rounded up to 100 (mnist) or 500>.pt``.  ``train_loss.csv`` and ``loss.csv`` have the
         layout pandas gives the reference's frames (an index column, ``epoch``, ``loss``); ``train_loss.csv`` holds every
         step (the reference appends each step's row to the evaluation frame, so its file keeps only the last one).
-        ``min_max_val`` defaults to the reference's per data set (ddpm.py:1474-1489).  Returns the best evaluation loss."""
+        ``min_max_val`` defaults to the reference's per data set (ddpm.py:1474-1489).  Returns the best evaluation loss.
+        Data-parallel: every rank evaluates every test batch (redundant, but no rank sits in a collective for minutes), only
+        rank 0 writes the files, and ``replica_digest()`` runs at every evaluation point."""
         data = str(self.diffusion.config.get("data", ""))
         if min_max_val is None:
             min_max_val = (0.0, 1.0) if data == "mnist" else (-1.0, 1.0) if data == "mri" else (0.0, 2.0)
@@ -364,6 +517,8 @@ class DenoiserTrainer:
         train_rows, eval_rows, best = [], [], 1e10
 
         def write(name, rows):
+            if self.rank:                                     # one writer: rank 0
+                return
             with open(os.path.join(out_dir, name), "w") as f:
                 f.write(",epoch,loss\n" + "".join(f"{i},{e},{v}\n" for i, (e, v) in enumerate(rows)))
         while self.step < num_steps:
@@ -371,11 +526,14 @@ class DenoiserTrainer:
             train_rows.append((at, float(self.train_step(batches))))
             write("train_loss.csv", train_rows)
             if self.step % save_and_sample_every == 0:
+                if self.world > 1:
+                    self.replica_digest()                     # (one wait beside a full sampling run)
                 ls = self.evaluate(test_batches, min_max_val)
                 if best > ls:
                     best = ls
                     num = 100 if data == "mnist" else 500
-                    self.save(os.path.join(out_dir, f"model-best{int(math.ceil(self.step / num)) * num}.pt"))
+                    if self.rank == 0:
+                        self.save(os.path.join(out_dir, f"model-best{int(math.ceil(self.step / num)) * num}.pt"))
                 eval_rows.append((self.step, ls))
                 write("loss.csv", eval_rows)
         return best

@@ -693,22 +693,34 @@ class GaussianDiffusion(nn.Module):
                                             x0.shape[0], x0[0].numel(), self._st()), "q_sample_t")
         return out
 
-    def training_noise(self, x0, noise=None, offset_noise_strength=None):
+    def training_noise(self, x0, noise=None, offset_noise_strength=None, first_row=0):
         """The noise of one training batch as ddpm.py:1165-1167 makes it, for ``x0`` [B, C, H, W] fp32 on the device:
         ``noise`` (None: the next draw of the run's noise stream) plus, when the strength is positive, that strength times a
         [B, C] draw -- the next one of the stream -- broadcast over the image.  Shared by ``p_losses`` and
-        ``DenoiserTrainer.accumulate``, so that both draw the same values in the same order."""
+        ``DenoiserTrainer.accumulate``, so that both draw the same values in the same order.  ``first_row`` > 0 (a
+        data-parallel rank): ``x0`` is rows ``first_row ..`` of a larger batch, and both draws are those rows of what the
+        whole batch would draw -- the stream is read at the rows' element offset, and ``noise_offset`` is as before when
+        this returns."""
         dev = self.device
+        if first_row and callable(self.noise_source):
+            raise ValueError("training_noise: a callable noise_source cannot be read at a row offset")
+
+        def draw(buf):
+            self._train_draw = getattr(self, "_train_draw", -1) + 1
+            keep = self.noise_offset
+            self.noise_offset = keep + int(first_row) * buf[0].numel()
+            try:
+                self._noise(buf, self._train_draw)
+            finally:
+                self.noise_offset = keep
         if noise is None:
             noise = torch.empty_like(x0)
-            self._train_draw = getattr(self, "_train_draw", -1) + 1
-            self._noise(noise, self._train_draw)
+            draw(noise)
         noise = noise.to(dev, torch.float32).contiguous()
         strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
         if strength > 0.0:
             off = torch.empty(x0.shape[0], x0.shape[1], dtype=torch.float32, device=dev)
-            self._train_draw = getattr(self, "_train_draw", -1) + 1
-            self._noise(off, self._train_draw)
+            draw(off)
             noise = (noise + strength * off[:, :, None, None]).contiguous()
         return noise
 

@@ -123,6 +123,12 @@ def rendezvous_run_id() -> Optional[str]:
 RUNTIME_CONFIGURED = False      # set by configure_runtime(), whatever it was asked to apply
 
 
+def process_env() -> Dict[str, str]:
+    """A copy of the process environment: what ``launch.launch_ranks`` hands on to its rank processes and reads the
+    ``*_VISIBLE_DEVICES`` variables from."""
+    return dict(_PROCESS_ENV)
+
+
 def runtime_configured(var: str = "DEBUG_CLR_GRAPH_PACKET_CAPTURE") -> bool:
     """Did the caller decide the runtime settings -- by calling ``configure_runtime`` (with any arguments) or by setting
     the variable in the environment?"""

@@ -10,7 +10,17 @@ The reference's dataset classes and augmentation are not part of this.
 
   python tools/train_denoiser.py --data mnist --hr hr.npy --lr lr.npy [--steps 1000] [--batch-size 32] [--timesteps 250]
          [--objective pred_v] [--train-lr 1e-4] [--save-every 100] [--init model.pt] [--out results/denoiser]
+         [--gpus N] [--rank-timeout 86400] [--grace 30]
 Writes <out>/model-best<step rounded up>.pt (whenever the evaluation loss improves), train_loss.csv, loss.csv.
+
+``--gpus N`` (one node): the tool starts N fresh rank processes of itself (``launch.launch_ranks``; this process makes no GPU
+call), each on its own GPU over RCCL (torch.distributed's "nccl").  ``--batch-size`` stays the GLOBAL batch: rank r trains on
+its rows of every batch (the reference's ``Accelerator(split_batches=True)``), the gradients are summed in rank order, and the
+replicas hold the same bits after every step; every batch size must be a multiple of N.  All ranks are seeded alike, every rank
+evaluates, rank 0 writes the files, and every rank prints its ``replica_digest()`` at the end.  ``--rank-timeout`` bounds the
+whole run, ``--grace`` is what the other ranks get once one has failed.  ``--share-gpu`` is for tests only: the ranks share the
+visible GPUs, which RCCL refuses, so they meet over gloo and the gradient exchange is staged through pinned host memory -- a
+functional path, never a measurement; the log line says so.
 """
 import argparse
 import os
@@ -28,7 +38,7 @@ KWARGS = {"mri": dict(mode="mri"), "mnist": dict(dim_mults=(1, 2, 4), full_attn=
           "mvtec": dict(channels=3, out_dim=3, mode="mvtec")}
 
 
-def main():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True, choices=sorted(KWARGS))
     ap.add_argument("--hr", required=True)
@@ -42,7 +52,16 @@ def main():
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--out", default="results/denoiser")
-    a = ap.parse_args()
+    ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node, one GPU each")
+    ap.add_argument("--rank-timeout", type=float, default=86400.0, help="--gpus > 1: seconds that bound the whole run")
+    ap.add_argument("--grace", type=float, default=30.0, help="--gpus > 1: seconds the other ranks get after one has failed")
+    ap.add_argument("--share-gpu", action="store_true",
+                    help="tests only: the ranks share the visible GPUs over gloo, gradients staged through host memory")
+    return ap.parse_args(argv)
+
+
+def setup(a, **trainer_kw):
+    """The trainer and its (train, validation) batches for the parsed arguments, on the current GPU."""
     hr = torch.from_numpy(np.load(a.hr).astype(np.float32))
     lr = torch.from_numpy(np.load(a.lr).astype(np.float32))
     net = ldh.Unet(dim=32, init_dim=32, **KWARGS[a.data])
@@ -70,11 +89,60 @@ def main():
     gd = ldh.GaussianDiffusion(config, net, image_size=int(hr.shape[2]), timesteps=a.timesteps, objective=a.objective)
     if a.init:
         print("init:", checkpoint.load_reference_checkpoint(a.init, gd))
-    trainer = ldh.DenoiserTrainer(gd.to("cuda"), train_lr=a.train_lr)
-    best = trainer.fit(batches(tr_idx), batches(va_idx), a.steps, a.save_every, a.out)
-    print(f"train images {len(tr_idx)}, validation images {len(va_idx)}, steps {trainer.step}")
-    print(f"last gradient norm: {trainer.check_finite():.4f}")
-    print(f"best evaluation loss: {best:.6f}")
+    trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr, **trainer_kw)
+    return trainer, batches(tr_idx), batches(va_idx)
+
+
+def main(argv=None):
+    a = parse(argv)
+    if a.gpus > 1 and "RANK" not in os.environ:              # the parent: starts the ranks, makes no GPU call itself
+        from localdiffusion_hallucination_amd.launch import launch_ranks
+        log_dir = os.path.join(a.out, "ranks")                # rank<r>.out / rank<r>.err
+        try:
+            rc = launch_ranks([sys.executable, os.path.abspath(__file__)] + list(sys.argv[1:] if argv is None else argv), a.gpus,
+                              timeout_s=a.rank_timeout, grace_s=a.grace, log_dir=log_dir, share_gpu=a.share_gpu)
+        except ValueError as e:
+            raise SystemExit(f"train_denoiser.py: {e}")
+        for r in range(a.gpus):                              # rank 0's output, and every rank's digest line
+            try:
+                for line in open(os.path.join(log_dir, f"rank{r}.out"), errors="replace"):
+                    if r == 0 or line.startswith("replica digest"):
+                        sys.stdout.write(line)
+            except OSError:
+                pass
+        sys.exit(rc)
+    kw, world, rank = {}, int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if a.gpus > 1:
+        import torch.distributed as dist
+        if world != a.gpus:
+            raise SystemExit(f"train_denoiser.py: --gpus {a.gpus} but WORLD_SIZE={world}")
+        ldh.configure_runtime()                              # before the first GPU call
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        if a.share_gpu:
+            # several ranks on one GPU, which RCCL refuses: gloo, and the trainer stages its exchange through pinned host
+            # memory (this torch's gloo is not asked to gather device tensors)
+            local %= max(1, torch.cuda.device_count())
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+            print("[--share-gpu: ranks share a GPU over gloo, gradients staged through host memory -- functional test, "
+                  "not a measurement]")
+        else:
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))   # RCCL
+        torch.cuda.set_device(local)
+        kw = dict(group="default")
+    trainer, train, val = setup(a, **kw)
+    torch.manual_seed(a.seed)                                # every rank alike: t comes from this generator
+    best = trainer.fit(train, val, a.steps, a.save_every, a.out)
+    if rank == 0:
+        print(f"train images {sum(b[0].shape[0] for b in train)}, validation images {sum(b[0].shape[0] for b in val)}, "
+              f"steps {trainer.step}, ranks {trainer.world}")
+        print(f"last gradient norm: {trainer.check_finite():.4f}")
+        print(f"best evaluation loss: {best:.6f}")
+    d = trainer.replica_digest()
+    print(f"replica digest: step {d['step']} sumsq {d['sumsq']!r} weight_sum {d['weight_sum']!r} "
+          f"weight_xor {d['weight_xor']:#010x}", flush=True)
+    if a.gpus > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
