@@ -988,6 +988,25 @@ int ld_dn_opt_step(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, float
                    float* ema, int64_t flat_floats, const double* sumsq, double max_norm, double beta1, double beta2, double eps,
                    double step_size, double bc2_sqrt, int ema_mode, float ema_w, void* stream);
 
+/* ---- training the denoiser, the convolutions in bf16 (conv_precision = "bf16"): csrc/conv16.hip ---------------------------------
+ * ld_pc_conv and ld_seg_wgrad with both operands of every product rounded to bf16 (round-to-nearest-even, NaN kept) and
+ * multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Memory keeps its formats: activations, gradients and the
+ * weight gradient are fp32; only the kernel-layout copy of a weight is bf16.  No floating-point atomics, nothing allocates,
+ * nothing synchronises; a refused call returns -1 before anything is launched. */
+/* ld_pc_conv's contract (args->weight is ignored) at stride 1 with weight_bf16 [Cout][ksize][ksize][Cin] in bf16: out = acc *
+ * scale + shift (+ residual), then the optional ReLU, fp32 NHWC.  Cin a multiple of 32, Cout of 64, ksize 1 or 3; src and
+ * weight_bf16 16-byte aligned.  The data gradient is the same call on the flipped, transposed weight (ld_dn_pack_conv16). */
+int ld_dn_conv16(const ld_pc_conv_args* args, const void* weight_bf16, void* stream);
+/* ld_seg_wgrad's contract: dw [Cout][ksize][ksize][Cin] fp32 from fp32 dy and a, one slab of work [splits][Cout * ksize^2 *
+ * Cin] per split of the pixel axis (a split without pixels writes zeros), added in index order by a second kernel.  Cin, Cout
+ * multiples of 64; 1 <= splits <= ceil(B H W / 32) (ld_seg_wgrad_splits gives the count); dy and a 16-byte aligned. */
+int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout, int ksize,
+                  int splits, void* stream);
+/* An OIHW fp32 parameter [co][ci][k][k] to the two bf16 kernel layouts in one launch: fwd [cop][k * k][cip] and dgr
+ * [cip][k * k, flipped][cop] (dgr[c][k * k - 1 - t][o] = w[o][c][t]), zero in the padded channels.  k 1 or 3; cop >= co and
+ * cip >= ci, both even. */
+int ld_dn_pack_conv16(const float* w_oihw, void* fwd_bf16, void* dgr_bf16, int co, int cop, int ci, int cip, int k, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -259,6 +259,9 @@ _SIGS = {
     "ld_dn_opt_reduce_tail": (C.c_int, [vp, C.c_int, i64, i64, vp, vp]),
     "ld_dn_opt_step": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_int, f32, vp]),
+    "ld_dn_conv16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
+    "ld_dn_wgrad16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_pack_conv16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -1,0 +1,263 @@
+// The denoiser's training convolutions on the bf16 matrix cores (conv_precision = "bf16" of trainable.py): the three
+// launches every trainable module's convolutions go through, with both operands of every product rounded to bf16
+// (round-to-nearest-even, v_cvt_pk_bf16_f32) and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  What
+// sits in memory does not change: activations and gradients are fp32 NHWC, the weight gradient is fp32.
+//
+//   * dn_conv16_kernel: ld_pc_conv's implicit GEMM (M = output pixels, N = output channels, K = taps x input channels;
+//     stride 1) with a bf16 OHWI weight.  The fp32 activation tile is rounded on its way into LDS, the weight tile is
+//     copied as it is; both are K-contiguous, so the LDS image is [row][32 k] bf16 and a lane's fragment (8 consecutive k
+//     of row lane & 31, k offset 8 (lane >> 5)) is one ds_read_b128.  Rows are padded to 80 bytes: the 16 rows a
+//     ds_read_b128 serves at a time start in 16 different 16-byte bank groups.  A 32-channel K-chunk is two MFMAs per
+//     32 x 32 block; the next chunk's global loads sit in registers while the current one is multiplied (pc_gemm's
+//     shape).  The data gradient is the same kernel on the flipped, transposed weight.
+//   * dn_wgrad16_kernel: ld_seg_wgrad's implicit GEMM (rows = output channels, columns = input channels, K = pixels in
+//     chunks of 32).  Both operands are channel-contiguous in memory and K is the pixel axis, so the loader writes the
+//     tiles transposed, [channel][32 pixels] bf16: a thread loads four channels of two neighbouring pixels and stores
+//     the four rounded pairs.  One slab of fp32 partial sums per split, added in index order by a second kernel (no
+//     floating-point atomics: a step is reproducible bit for bit); a split without chunks writes a zero slab.
+//   * dn_pack_conv16_kernel: an OIHW fp32 parameter to the two bf16 layouts in one launch, zero in the padded channels.
+#include "common.hip.h"
+
+namespace {
+constexpr int CV_T = 64;        // tile: 64 rows x 64 columns per workgroup (4 waves, 2 x 2, 32 x 32 each)
+constexpr int CV_KC = 32;       // K per chunk
+constexpr int CV_LD = CV_KC + 8;   // bf16 per LDS row (80 bytes)
+typedef __attribute__((ext_vector_type(16))) float cv_f32x16;
+typedef unsigned short cv_bf16;    // bf16 bits
+
+// the lane's fragment of K-step s (16 k) of a [row][CV_LD] image: 8 consecutive k of row `row`
+__device__ __forceinline__ bf16x8 cv_frag(const cv_bf16 (*img)[CV_LD], int row, int s, int kh) {
+  return *reinterpret_cast<const bf16x8*>(&img[row][s * 16 + 8 * kh]);
+}
+
+// ------------------------------------------------------------------------------------------------ convolution
+__global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const cv_bf16* __restrict__ w) {
+  __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [pixel][k]
+  __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [output channel][k]
+  constexpr int UA = CV_T / 32;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const long M = (long)a.B * a.Ho * a.Wo;
+  const long p0 = (long)blockIdx.x * CV_T;
+  const int n0 = blockIdx.y * CV_T;
+  const int ks = a.ksize, pad = ks == 3 ? 1 : 0, nch = a.Cin / CV_KC, K = ks * ks * a.Cin;
+  const int lr = tid >> 3, lk = (tid & 7) * 4;       // activations: rows lr and lr + 32, 4 floats at k offset lk
+  const int wr = tid >> 2, wk = (tid & 3) * 8;       // weights: row wr, 8 bf16 at k offset wk
+  int pb[UA], py[UA], px[UA];
+  bool pv[UA];
+#pragma unroll
+  for (int u = 0; u < UA; ++u) {
+    const long p = p0 + lr + 32 * u;
+    pv[u] = p < M;
+    const long pc = pv[u] ? p : 0;
+    px[u] = (int)(pc % a.Wo);
+    const long r = pc / a.Wo;
+    py[u] = (int)(r % a.Ho);
+    pb[u] = (int)(r / a.Ho);
+  }
+  auto fa = [&](int q, int u) {
+    const int tap = q / nch, c0 = (q - tap * nch) * CV_KC;
+    const int iy = py[u] - pad + tap / ks, ix = px[u] - pad + tap % ks;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (pv[u] && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi)
+      v = *reinterpret_cast<const float4*>(a.src + (((long)pb[u] * a.Hi + iy) * a.Wi + ix) * a.Cin + c0 + lk);
+    return v;
+  };
+  auto fb = [&](int q) { return *reinterpret_cast<const uint4*>(w + (long)(n0 + wr) * K + q * CV_KC + wk); };
+  cv_f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  float4 ra[UA];
+  uint4 rb;
+#pragma unroll
+  for (int u = 0; u < UA; ++u) ra[u] = fa(0, u);
+  rb = fb(0);
+  const int nq = ks * ks * nch;
+  const int kh = lane >> 5, c = lane & 31;
+  for (int q = 0; q < nq; ++q) {
+    __syncthreads();                                  // the previous chunk's reads of the tiles are done
+#pragma unroll
+    for (int u = 0; u < UA; ++u)
+      *reinterpret_cast<uint2*>(&sa[lr + 32 * u][lk]) = make_uint2(pack_bf16x2(ra[u].x, ra[u].y), pack_bf16x2(ra[u].z, ra[u].w));
+    *reinterpret_cast<uint4*>(&sb[wr][wk]) = rb;
+    __syncthreads();
+    if (q + 1 < nq) {
+#pragma unroll
+      for (int u = 0; u < UA; ++u) ra[u] = fa(q + 1, u);
+      rb = fb(q + 1);
+    }
+#pragma unroll
+    for (int s = 0; s < CV_KC / 16; ++s)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc, 0, 0, 0);
+  }
+  // C/D layout of 32x32x16: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  const int co = n0 + wn * 32 + c;
+  const float sc = a.scale[co], t = a.shift[co];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long p = p0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+    if (p >= M) continue;
+    float v = acc[r] * sc + t;
+    if (a.residual) v += a.residual[p * a.Cout + co];
+    if (a.relu) v = fmaxf(v, 0.0f);
+    a.out[p * a.Cout + co] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ weight gradient
+struct CvWgradDev {
+  const float* dy; const float* a; float* work;
+  long M, nchunks;
+  int H, W, Cin, Cout, ks, chunks_per_split;
+};
+
+__global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
+  __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [output channel][pixel of the chunk]
+  __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [input channel][pixel of the chunk]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int nci = d.Cin / CV_T;
+  const int co0 = ((int)blockIdx.x / nci) * CV_T, ci0 = ((int)blockIdx.x % nci) * CV_T;
+  const int tap = blockIdx.y, taps = d.ks * d.ks;
+  const int oy = d.ks == 3 ? tap / 3 - 1 : 0, ox = d.ks == 3 ? tap % 3 - 1 : 0;
+  const long c0 = (long)blockIdx.z * d.chunks_per_split;
+  const long c1 = c0 + d.chunks_per_split < d.nchunks ? c0 + d.chunks_per_split : d.nchunks;
+  const int lp = (tid >> 4) * 2, lc = (tid & 15) * 4;         // loader: pixels lp and lp + 1 of the chunk, 4 channels
+  float4 ra[2], rb[2];
+  auto fetch = [&](long q) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const long p = q * CV_KC + lp + u;
+      ra[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      rb[u] = ra[u];
+      if (p < d.M) {
+        ra[u] = *reinterpret_cast<const float4*>(d.dy + p * d.Cout + co0 + lc);
+        const int x = (int)(p % d.W), y = (int)((p / d.W) % d.H);
+        const int yy = y + oy, xx = x + ox;
+        if (yy >= 0 && yy < d.H && xx >= 0 && xx < d.W)        // same image: the shifted pixel is p + oy * W + ox
+          rb[u] = *reinterpret_cast<const float4*>(d.a + (p + (long)oy * d.W + ox) * d.Cin + ci0 + lc);
+      }
+    }
+  };
+  cv_f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  if (c0 < c1) fetch(c0);
+  const int kh = lane >> 5, c = lane & 31;
+  for (long q = c0; q < c1; ++q) {
+    __syncthreads();                                          // the previous chunk's reads of the tiles are done
+    *reinterpret_cast<unsigned*>(&sa[lc][lp]) = pack_bf16x2(ra[0].x, ra[1].x);
+    *reinterpret_cast<unsigned*>(&sa[lc + 1][lp]) = pack_bf16x2(ra[0].y, ra[1].y);
+    *reinterpret_cast<unsigned*>(&sa[lc + 2][lp]) = pack_bf16x2(ra[0].z, ra[1].z);
+    *reinterpret_cast<unsigned*>(&sa[lc + 3][lp]) = pack_bf16x2(ra[0].w, ra[1].w);
+    *reinterpret_cast<unsigned*>(&sb[lc][lp]) = pack_bf16x2(rb[0].x, rb[1].x);
+    *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = pack_bf16x2(rb[0].y, rb[1].y);
+    *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = pack_bf16x2(rb[0].z, rb[1].z);
+    *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = pack_bf16x2(rb[0].w, rb[1].w);
+    __syncthreads();
+    if (q + 1 < c1) fetch(q + 1);
+#pragma unroll
+    for (int s = 0; s < CV_KC / 16; ++s)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc, 0, 0, 0);
+  }
+  // C/D layout of 32x32x16: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  float* slab = d.work + (long)blockIdx.z * d.Cout * taps * d.Cin;
+  const int ci = ci0 + wn * 32 + c;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+    slab[((long)co * taps + tap) * d.Cin + ci] = acc[r];
+  }
+}
+
+__global__ void dn_wgrad16_reduce_kernel(const float* __restrict__ work, float* dw, long n, int splits) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float s = work[i];
+  for (int k = 1; k < splits; ++k) s += work[(long)k * n + i];
+  dw[i] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ weight packing
+// One thread per pair of neighbouring elements of fwd [cop][kk][cip] (the first `half` threads) or of dgr [cip][kk][cop]
+// with the taps flipped; w is OIHW [co][ci][kk].
+__global__ void dn_pack_conv16_kernel(const float* __restrict__ w, unsigned* fwd, unsigned* dgr, long half, int co, int cop, int ci,
+                                      int cip, int kk) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * half) return;
+  float v[2];
+  if (i < half) {
+    const long e = 2 * i;
+    const int c = (int)(e % cip), t = (int)((e / cip) % kk), o = (int)(e / ((long)cip * kk));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v[j] = (o < co && c + j < ci) ? w[((long)o * ci + c + j) * kk + t] : 0.0f;
+    fwd[i] = pack_bf16x2(v[0], v[1]);
+  } else {
+    const long e = 2 * (i - half);
+    const int o = (int)(e % cop), t = kk - 1 - (int)((e / cop) % kk), c = (int)(e / ((long)cop * kk));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v[j] = (o + j < co && c < ci) ? w[((long)(o + j) * ci + c) * kk + t] : 0.0f;
+    dgr[i - half] = pack_bf16x2(v[0], v[1]);
+  }
+}
+}  // namespace
+
+extern "C" int ld_dn_conv16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  LD_REQUIRE(a, "ld_dn_conv16: null args");
+  LD_REQUIRE(a->ksize == 1 || a->ksize == 3, "ld_dn_conv16: ksize %d (1 or 3)", a->ksize);
+  LD_REQUIRE(a->stride == 1, "ld_dn_conv16: stride %d (1 only)", a->stride);
+  LD_REQUIRE(a->B > 0 && a->Hi > 0 && a->Wi > 0, "ld_dn_conv16: empty input B=%d H=%d W=%d", a->B, a->Hi, a->Wi);
+  LD_REQUIRE(a->Ho == a->Hi && a->Wo == a->Wi, "ld_dn_conv16: output %dx%d does not match input %dx%d at stride 1", a->Ho, a->Wo,
+             a->Hi, a->Wi);
+  LD_REQUIRE(a->Cin > 0 && a->Cin % CV_KC == 0, "ld_dn_conv16: Cin %d (a multiple of 32)", a->Cin);
+  LD_REQUIRE(a->Cout > 0 && a->Cout % CV_T == 0, "ld_dn_conv16: Cout %d (a multiple of 64)", a->Cout);
+  LD_REQUIRE(a->src && weight_bf16 && a->scale && a->shift && a->out, "ld_dn_conv16: null pointer");
+  LD_REQUIRE(((uintptr_t)a->src | (uintptr_t)weight_bf16) % 16 == 0, "ld_dn_conv16: src and weight must be 16-byte aligned");
+  const long M = (long)a->B * a->Ho * a->Wo;
+  LD_REQUIRE((M + CV_T - 1) / CV_T < (1L << 31), "ld_dn_conv16: %ld pixels", M);
+  LD_REQUIRE((long)a->ksize * a->ksize * a->Cin < (1L << 31), "ld_dn_conv16: K %ld", (long)a->ksize * a->ksize * a->Cin);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((M + CV_T - 1) / CV_T), (unsigned)(a->Cout / CV_T));
+  LD_LAUNCH(dn_conv16_kernel, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
+  LD_LAUNCH_CHECK("dn_conv16");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
+                             int ksize, int splits, void* stream) {
+  LD_REQUIRE(ksize == 1 || ksize == 3, "ld_dn_wgrad16: ksize %d (1 or 3)", ksize);
+  LD_REQUIRE(B > 0 && H > 0 && W > 0, "ld_dn_wgrad16: empty shape B=%d H=%d W=%d", B, H, W);
+  LD_REQUIRE(Cin > 0 && Cin % CV_T == 0, "ld_dn_wgrad16: Cin %d (a multiple of 64)", Cin);
+  LD_REQUIRE(Cout > 0 && Cout % CV_T == 0, "ld_dn_wgrad16: Cout %d (a multiple of 64)", Cout);
+  const long M = (long)B * H * W, nchunks = (M + CV_KC - 1) / CV_KC;
+  LD_REQUIRE(splits >= 1 && splits <= nchunks && splits <= 65535, "ld_dn_wgrad16: splits %d (1..min(%ld, 65535))", splits,
+             nchunks);
+  const long tiles = (long)(Cin / CV_T) * (Cout / CV_T);
+  LD_REQUIRE(tiles < (1L << 31), "ld_dn_wgrad16: %ld tiles", tiles);
+  LD_REQUIRE(dy && a && work && dw, "ld_dn_wgrad16: null pointer");
+  LD_REQUIRE(((uintptr_t)dy | (uintptr_t)a) % 16 == 0, "ld_dn_wgrad16: dy and a must be 16-byte aligned");
+  const long per = (nchunks + splits - 1) / splits;
+  CvWgradDev d{dy, a, work, M, nchunks, H, W, Cin, Cout, ksize, (int)per};
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LD_LAUNCH(dn_wgrad16_kernel, dim3((unsigned)tiles, (unsigned)(ksize * ksize), (unsigned)splits), dim3(256), 0, st, d);
+  const long n = (long)Cout * ksize * ksize * Cin;
+  LD_LAUNCH(dn_wgrad16_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, dw, n, splits);
+  LD_LAUNCH_CHECK("dn_wgrad16");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_pack_conv16(const float* w_oihw, void* fwd_bf16, void* dgr_bf16, int co, int cop, int ci, int cip, int k,
+                                 void* stream) {
+  LD_REQUIRE(k == 1 || k == 3, "ld_dn_pack_conv16: ksize %d (1 or 3)", k);
+  LD_REQUIRE(co > 0 && ci > 0 && cop >= co && cip >= ci, "ld_dn_pack_conv16: co %d of %d, ci %d of %d", co, cop, ci, cip);
+  LD_REQUIRE(cop % 2 == 0 && cip % 2 == 0, "ld_dn_pack_conv16: padded channels %d, %d (even)", cop, cip);
+  LD_REQUIRE(w_oihw && fwd_bf16 && dgr_bf16, "ld_dn_pack_conv16: null pointer");
+  LD_REQUIRE(((uintptr_t)fwd_bf16 | (uintptr_t)dgr_bf16) % 4 == 0, "ld_dn_pack_conv16: outputs must be 4-byte aligned");
+  const long half = (long)cop * k * k * cip / 2;
+  LD_REQUIRE((2 * half + 255) / 256 < (1L << 31), "ld_dn_pack_conv16: %ld elements", 2 * half);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LD_LAUNCH(dn_pack_conv16_kernel, dim3((unsigned)((2 * half + 255) / 256)), dim3(256), 0, st, w_oihw, reinterpret_cast<unsigned*>(fwd_bf16),
+            reinterpret_cast<unsigned*>(dgr_bf16), half, co, cop, ci, cip, k * k);
+  LD_LAUNCH_CHECK("dn_pack_conv16");
+  return LD_OK;
+}

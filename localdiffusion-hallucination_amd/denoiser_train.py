@@ -31,7 +31,7 @@ micro-batches in order.  Drawn ``t`` and noise are the rank's rows of what one r
 ranks alike).  The gather is not overlapped with the backward pass.
 
 NOT covered: 16-bit storage, more than one node, ragged shards (a batch size that is no multiple of the world size), a sharded
-evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, ``amp``, FID, writing the kernel-layout weight copies from the optimiser launch
+evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, fp16 with loss scaling, FID, writing the kernel-layout weight copies from the optimiser launch
 (the modules repack after a step, as they do under ``torch.optim.Adam``), handing padded tensors between modules.
 """
 import ctypes as C
@@ -42,7 +42,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import stream
+from .trainable import check_conv_precision, stream
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -143,11 +143,18 @@ class DenoiserTrainer:
     (``world`` 1, ``data_parallel`` False) the trainer issues the launches it always did; a group or communicator of one rank
     runs the data-parallel launches on its one copy, to the same bits.
 
+    ``conv_precision="bf16"`` (default ``"fp32"``) trains with the online model's convolutions, and both of their gradients,
+    on the bf16 matrix cores (``TrainableUnet.conv_precision``): operands rounded to bf16, fp32 accumulation, everything in
+    memory and everything else fp32, no loss scaling; the step stays reproducible bit for bit.  Checkpoints do not record it
+    (the weights are the fp32 masters) and the EMA / inference ``Unet`` is not touched.
+
     ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
     ``ema_initted`` are ``ema_pytorch``'s two buffers."""
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
-                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None):
+                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
+                 conv_precision="fp32"):
+        check_conv_precision("DenoiserTrainer", conv_precision)
         if group is not None and comm is not None:
             raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
         model = getattr(diffusion, "model", None)
@@ -168,7 +175,9 @@ class DenoiserTrainer:
         for name, v, lo in (("ema_update_every", ema_update_every, 1), ("ema_update_after_step", ema_update_after_step, 0)):
             if not isinstance(v, int) or isinstance(v, bool) or v < lo:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
-        online = TrainableUnet(**online_kwargs(model))                  # (raises ValueError for what it cannot train)
+        # (raises ValueError for what it cannot train)
+        online = TrainableUnet(**online_kwargs(model), conv_precision=conv_precision)
+        self.conv_precision = conv_precision
         dev = diffusion.device
         if dev.type != "cuda":
             raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")

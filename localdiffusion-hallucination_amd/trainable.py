@@ -7,6 +7,11 @@ kernel-layout copies of the weights (``pack_conv``, ``pack_vec``) are zero there
 parameter's ``data_ptr`` and ``_version`` (``PackedWeights``).  A module's forward and backward are the two halves of one
 ``autograd.Function``; each half is a sequence of launches that the module's ``Run`` subclass writes down, out of the launches
 every module uses (``Run``: buffers, the NHWC repack, ``ld_pc_conv``, the weight and bias gradients) and its own.
+
+``TrainableModule.conv_precision`` (``"fp32"``, the default, or ``"bf16"``) is the one switch of the convolutions' arithmetic:
+``pack_conv``, ``Run.conv`` and ``Run.wgrad_packed`` route on it.  At ``"bf16"`` the kernel-layout weights are bf16 and the
+convolution, its data gradient and its weight gradient run on ``csrc/conv16.hip`` (operands rounded to bf16, products on the
+bf16 matrix cores, fp32 accumulation); what sits in memory, and every other launch, is the same.
 """
 import ctypes as C
 
@@ -43,7 +48,7 @@ class PackedWeights:
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def _packed_for(self, dev):
-        key = (dev,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = (dev, getattr(self, "conv_precision", "fp32")) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._packed is None or self._packed[0] != key:
             with torch.no_grad():
                 self._packed = (key, self._pack(dev))
@@ -51,15 +56,34 @@ class PackedWeights:
 
 
 # ---------------------------------------------------------------------------------------------------- packing
-def pack_conv(lib, st, w, co, cop, ci, cip, k):
+CONV_PRECISIONS = ("fp32", "bf16")
+
+
+def check_conv_precision(name, value):
+    if value not in CONV_PRECISIONS:
+        raise ValueError(f"{name}: conv_precision {value!r} is not one of {', '.join(repr(v) for v in CONV_PRECISIONS)}")
+    return value
+
+
+def pack_conv(lib, st, w, co, cop, ci, cip, k, precision="fp32"):
     """OIHW [co, ci, k, k] -> forward layout [cop][k*k][cip] and data-gradient layout [cip][flipped k*k][cop], zero in the
-    padded channels."""
+    padded channels; fp32, or with ``precision="bf16"`` rounded to bf16 (what ``Run.conv`` then takes), in one launch."""
     w = w.detach().contiguous()
     kk = k * k
+    if precision == "bf16":
+        fwd, dgr = (torch.empty(cop * kk * cip, dtype=torch.bfloat16, device=w.device) for _ in range(2))
+        cabi.check(lib.ld_dn_pack_conv16(w.data_ptr(), fwd.data_ptr(), dgr.data_ptr(), co, cop, ci, cip, k, st), "dn_pack_conv16")
+        return fwd, dgr
     fwd, dgr = w.new_zeros(cop * kk * cip), w.new_zeros(cip * kk * cop)
     cabi.check(lib.ld_seg_permute3(w.data_ptr(), fwd.data_ptr(), co, ci, kk, 0, kk * cip, 1, cip, st), "permute3")
     cabi.check(lib.ld_seg_permute3(w.data_ptr(), dgr.data_ptr(), co, ci, kk, (kk - 1) * cop, 1, kk * cop, -cop, st), "permute3")
     return fwd, dgr
+
+
+def as_conv_precision(t, precision):
+    """A kernel-layout weight a module packed by itself (fp32), as ``Run.conv`` takes it at ``precision``: rounded to bf16
+    (torch's cast: round-to-nearest-even, as ``ld_dn_pack_conv16`` rounds) or as it is."""
+    return t.to(torch.bfloat16) if precision == "bf16" else t
 
 
 def pack_vec(v, n):
@@ -86,6 +110,7 @@ class Run:
         self.mod, self.p, self.dev, self.B, self.H, self.W = mod, packed, dev, B, H, W
         self.lib, self.st = cabi.lib(), stream(dev)
         self.fill = mod.debug_fill
+        self.bf16 = getattr(mod, "conv_precision", "fp32") == "bf16"      # (the precision ``packed`` was made at)
 
     def empty(self, *shape, dtype=torch.float32):
         t = torch.empty(*shape, dtype=dtype, device=self.dev)
@@ -117,7 +142,14 @@ class Run:
         a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
         a.residual, a.out = cabi.ptr(residual), out.data_ptr()
         a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, H, W, cin, H, W, cout, k, 1, 0
-        cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
+        if (weight.dtype == torch.bfloat16) != self.bf16:
+            raise RuntimeError(f"{type(self.mod).__name__}: a {weight.dtype} kernel-layout weight at conv_precision "
+                               f"{'bf16' if self.bf16 else 'fp32'} (the module's _pack does not pass the precision on)")
+        if self.bf16:
+            a.weight = None
+            cabi.check(self.lib.ld_dn_conv16(C.byref(a), weight.data_ptr(), self.st), "dn_conv16")
+        else:
+            cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
         return out
 
     def wgrad_packed(self, dy, a, cop, cip, k, hw=None):
@@ -127,8 +159,8 @@ class Run:
         kk = k * k
         splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cip, cop, k))
         work, dwp = self.empty(splits * cop * kk * cip), self.empty(cop * kk * cip)
-        cabi.check(self.lib.ld_seg_wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cip, cop, k,
-                                         splits, self.st), "seg_wgrad")
+        wgrad, what = (self.lib.ld_dn_wgrad16, "dn_wgrad16") if self.bf16 else (self.lib.ld_seg_wgrad, "seg_wgrad")
+        cabi.check(wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cip, cop, k, splits, self.st), what)
         return dwp
 
     def wgrad(self, dy, a, co, cop, ci, cip, k, hw=None):
@@ -182,7 +214,14 @@ class TrainableModule(PackedWeights, nn.Module):
     output."""
 
     debug_fill = None       # a float: every buffer the module allocates is filled with it first (tests: NaN)
+    conv_precision = "fp32"  # or "bf16": the operands of every convolution and of its two gradients are rounded to bf16 and
+    #                          multiplied on the bf16 matrix cores with fp32 accumulation; everything else stays fp32
     Run = None
+
+    def __setattr__(self, name, value):
+        if name == "conv_precision":
+            check_conv_precision(type(self).__name__, value)
+        super().__setattr__(name, value)
 
     def _run(self, x):
         return self.Run(self, self._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])

@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import pad64, stream
+from .trainable import check_conv_precision, pad64, stream
 from .weights import UnetConfig
 
 
@@ -189,8 +189,9 @@ class TrainableUnet(nn.Module):
     def __init__(self, dim, init_dim=None, out_dim=None, dim_mults=(1, 2, 4, 8), channels=1, self_condition=False, cond_img=True,
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
-                 full_attn=(False, False, False, True), flash_attn=False, mode="mri"):
+                 full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32"):
         super().__init__()
+        check_conv_precision("TrainableUnet", conv_precision)
         for flag, what in ((self_condition, "self_condition"), (learned_variance, "learned_variance"),
                            (learned_sinusoidal_cond, "learned_sinusoidal_cond"), (random_fourier_features, "random_fourier_features")):
             if flag:
@@ -246,6 +247,9 @@ class TrainableUnet(nn.Module):
                                            Upsample(cout, cin) if j < n - 1 else Conv2d(cout, cin, 3, padding=1)]))
         self.final_res_block = block(2 * dim, dim)
         self.final_conv = Conv2d(dim, self.out_dim, 1)
+        self._conv_precision = "fp32"
+        if conv_precision != "fp32":                 # (the default is the modules' class attribute: nothing to hand down)
+            self.conv_precision = conv_precision
 
     @property
     def downsample_factor(self):
@@ -262,6 +266,20 @@ class TrainableUnet(nn.Module):
         for m in self.modules():
             if m is not self and hasattr(type(m), "debug_fill"):
                 m.debug_fill = value
+
+    @property
+    def conv_precision(self):
+        return self._conv_precision
+
+    @conv_precision.setter
+    def conv_precision(self, value):
+        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every convolution of every sub-module, and both of its gradients, round
+        their operands to bf16 and multiply on the bf16 matrix cores with fp32 accumulation (``TrainableModule``); activations,
+        parameters, gradients, the norms, the attention cores, the head and the time MLP stay fp32."""
+        self._conv_precision = check_conv_precision("TrainableUnet", value)
+        for m in self.modules():
+            if m is not self and hasattr(type(m), "conv_precision"):
+                m.conv_precision = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

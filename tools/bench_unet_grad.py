@@ -3,7 +3,7 @@
 restated in eager PyTorch (autograd, MIOpen convolutions, ``F.group_norm``, einsum attention) on the same GPU in one process,
 fp32, ms per forward + backward.
 
-  python tools/bench_unet_grad.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300]
+  python tools/bench_unet_grad.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300] [--conv-precision fp32|bf16]
 A case is data:H = W:batch; the default cases are cfg3 (mvtec, 3 x 256^2, B = 8), mri at 256^2 with B = 8 and mnist at 28^2
 with B = 64.  Every case runs in a child process of its own under a time limit (``--timeout`` seconds; the HIP and the eager
 net share that process), and the first case that fails or runs out of time ends the run: nothing more is started on the GPU
@@ -11,7 +11,9 @@ after it.  Per case: 3 warm-up calls, then the median of 20 calls timed with eve
 gradient is a fixed tensor).  Eager PyTorch is timed with its inputs in NCHW and in channels_last.  One more HIP call under
 the library's per-launch timing session gives the launch count and the split of the kernel time over the kernel families,
 with the boundary repacks (``dn_pack_nhwc``), the glue (``dn_join``) and the time MLP each named.  Prints one line per case,
-the split, and a JSON list at the end.
+the split, and a JSON list at the end.  ``--conv-precision bf16`` times the HIP net with its convolutions on the bf16 matrix
+cores (``TrainableUnet(conv_precision="bf16")``); eager PyTorch stays fp32, and the printed output difference then holds the
+operands' rounding.
 """
 import os
 import sys
@@ -30,6 +32,8 @@ KWARGS = {"mri": dict(mode="mri"), "mnist": dict(dim_mults=(1, 2, 4), full_attn=
 FAMILIES = (("dn_pack_nhwc", "dn_pack_nhwc (boundary repacks)"), ("dn_join", "dn_join (cat, attn(x) + x)"),
             ("dn_time_mlp", "time MLP"), ("dn_time_proj", "time projections"), ("pc_conv (forward)", "convolutions, forward"),
             ("pc_conv (data gradient)", "convolutions, data gradient"), ("seg_wgrad", "convolutions, weight gradient"),
+            ("dn_conv16 (forward)", "convolutions, forward"), ("dn_conv16 (data gradient)", "convolutions, data gradient"),
+            ("dn_wgrad16", "convolutions, weight gradient"), ("dn_pack_conv16", "weight packing (bf16)"),
             ("dn_colsum", "bias gradients"), ("dn_gn", "GroupNorm"), ("dn_la_", "linear attention"), ("dn_fa_", "full attention"),
             ("dn_rms_", "RMSNorm"), ("dn_head_", "head"), ("seg_pool", "max pool"))
 
@@ -156,7 +160,7 @@ def families(split):
 def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
-    net = ldh.TrainableUnet(dim=32, **KWARGS[data]).cuda()
+    net = ldh.TrainableUnet(dim=32, conv_precision=a.conv_precision, **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -179,7 +183,7 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
                 kernels_ms=sum(v[0] for v in split.values()), launches=sum(v[1] for v in split.values()), split=fam)
 
@@ -189,10 +193,10 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:9.3f} ms, channels_last {r['eager_nhwc_ms']:9.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f}; outputs differ by {r['out_diff_to_eager']:.1e})")
-    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d}: HIP {r['hip_ms']:9.3f} ms, {r['launches']} launches, kernels "
+    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']}: HIP {r['hip_ms']:9.3f} ms, {r['launches']} launches, kernels "
           f"{r['kernels_ms']:9.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, CASES, run_case, report))
+    sys.exit(grad_bench.main(__file__, CASES, run_case, report, conv_precision=True))

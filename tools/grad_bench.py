@@ -46,8 +46,8 @@ class TimedLib:
 
         def wrapped(*args):
             label = name[3:]
-            if name == "ld_pc_conv":
-                label = "pc_conv (forward)" if self.phase == "forward" else "pc_conv (data gradient)"
+            if name in ("ld_pc_conv", "ld_dn_conv16"):
+                label += " (forward)" if self.phase == "forward" else " (data gradient)"
             if name == "ld_dn_pack_nhwc":
                 label = f"dn_pack_nhwc ({self.phase})"
             n0 = self._lib.ld_timing_count()
@@ -109,15 +109,19 @@ def print_split(split, kernels_ms):
         print(f"      {k:28s} {v['ms']:9.3f} ms  {100 * v['ms'] / kernels_ms:5.1f} %  ({v['launches']} launches)")
 
 
-def main(tool, cases, run_case, report, heads=False):
+def main(tool, cases, run_case, report, heads=False, conv_precision=False):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
-    returns the case's JSON row and ``report(row)`` prints it.  Every case runs in a child process (``tool --child``) under
+    returns the case's JSON row and ``report(row)`` prints it.  ``conv_precision``: the tool takes ``--conv-precision {fp32,bf16}``
+    (``args.conv_precision``; the eager side stays fp32).  Every case runs in a child process (``tool --child``) under
     ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is started on the GPU after
     it."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     if heads:
         ap.add_argument("--heads", type=int, default=4)
+    if conv_precision:
+        ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "bf16"],
+                        help="the HIP side's convolutions: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -130,7 +134,8 @@ def main(tool, cases, run_case, report, heads=False):
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup") if hasattr(a, k) for w in ("--" + k, str(getattr(a, k)))]
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision") if hasattr(a, k)
+                 for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:
         name = ":".join(str(v) for v in case)

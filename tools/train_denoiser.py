@@ -48,6 +48,8 @@ def parse(argv=None):
     ap.add_argument("--timesteps", type=int, default=250)
     ap.add_argument("--objective", default="pred_v", choices=["pred_noise", "pred_x0", "pred_v"])
     ap.add_argument("--train-lr", type=float, default=1e-4)
+    ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "bf16"],
+                    help="bf16: the convolutions and their gradients on the bf16 matrix cores (operands rounded, fp32 accumulation)")
     ap.add_argument("--save-every", type=int, default=100)
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
@@ -89,7 +91,8 @@ def setup(a, **trainer_kw):
     gd = ldh.GaussianDiffusion(config, net, image_size=int(hr.shape[2]), timesteps=a.timesteps, objective=a.objective)
     if a.init:
         print("init:", checkpoint.load_reference_checkpoint(a.init, gd))
-    trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr, **trainer_kw)
+    trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr,
+                                  conv_precision=a.conv_precision, **trainer_kw)
     return trainer, batches(tr_idx), batches(va_idx)
 
 
