@@ -754,6 +754,12 @@ int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C);
  * may be residual.  C a multiple of 4 * groups, ldc a multiple of 4, pointers 16-byte aligned. */
 int ld_dn_gn_forward(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
                      double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups, void* stream);
+/* The same with out in bf16 (act_storage = "bf16": an activation only convolutions read), [B, H, W, ldc] at the same pixel
+ * stride in elements: the fp32 value above, rounded to nearest even as the bf16 convolutions round an fp32 activation; the
+ * padding is zeros, stat is unchanged.  residual stays fp32 and cannot be out.  out_bf16 16-byte aligned. */
+int ld_dn_gn_forward_to16(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
+                          double* work, float* stat, void* out_bf16, int B, int H, int W, int C, int ldc, int groups,
+                          void* stream);
 /* Its backward from dout (the gradient of silu(a)), the saved y and stat; a is recomputed.  dgamma, dbeta [C], dfilm
  * [B][2 C] (NULL exactly when film is), dy [B, H, W, ldc] (may be dout).  One reduction pass over dout and y, a
  * finalisation, one elementwise pass. */
@@ -772,6 +778,9 @@ int ld_dn_time_proj_backward(const float* dfilm, const float* temb, const float*
 /* out [B, H, W, ldc] (channels C..ldc-1 zero) from a tensor [B, C, H, W] with strides (sb, sc, sh, sw) in floats. */
 int ld_dn_pack_nhwc(const float* x, float* out, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
                     int ldc, void* stream);
+/* The same with out in bf16 (rounded to nearest even, the padding zero); ldc even, out_bf16 4-byte aligned. */
+int ld_dn_pack_nhwc_to16(const float* x, void* out_bf16, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh,
+                         int64_t sw, int ldc, void* stream);
 /* out [d0][d1][d2] (contiguous) = in[off + i0 s0 + i1 s1 + i2 s2]: the inverse of ld_seg_permute3 (a padded OHWI weight
  * gradient back to the parameter's OIHW). */
 int ld_dn_gather3(const float* in, float* out, int d0, int d1, int d2, int64_t off, int64_t s0, int64_t s1, int64_t s2,
@@ -1002,6 +1011,14 @@ int ld_dn_conv16(const ld_pc_conv_args* args, const void* weight_bf16, void* str
  * multiples of 64; 1 <= splits <= ceil(B H W / 32) (ld_seg_wgrad_splits gives the count); dy and a 16-byte aligned. */
 int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout, int ksize,
                   int splits, void* stream);
+/* ld_dn_conv16 and ld_dn_wgrad16 on an activation that is bf16 in memory (act_storage = "bf16"): args->src, or a, points at a
+ * bf16 NHWC tensor of the same shape and the same pixel stride in elements, 16-byte aligned; dy, the residual and every
+ * output stay fp32.  The loader copies where the fp32 one rounds and everything behind it is the same code, so the result
+ * is bit for bit that of the fp32 tensor which rounds to this one; taps outside the image and rows beyond the last pixel are
+ * zeros.  Same shapes, same refusals, same work buffer and split count. */
+int ld_dn_conv16_from16(const ld_pc_conv_args* args, const void* weight_bf16, void* stream);
+int ld_dn_wgrad16_from16(const float* dy, const void* a_bf16, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
+                         int ksize, int splits, void* stream);
 /* An OIHW fp32 parameter [co][ci][k][k] to the two bf16 kernel layouts in one launch: fwd [cop][k * k][cip] and dgr
  * [cip][k * k, flipped][cop] (dgr[c][k * k - 1 - t][o] = w[o][c][t]), zero in the padded channels.  k 1 or 3; cop >= co and
  * cip >= ci, both even. */

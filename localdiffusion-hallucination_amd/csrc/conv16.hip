@@ -16,6 +16,16 @@
 //     the four rounded pairs.  One slab of fp32 partial sums per split, added in index order by a second kernel (no
 //     floating-point atomics: a step is reproducible bit for bit); a split without chunks writes a zero slab.
 //   * dn_pack_conv16_kernel: an OIHW fp32 parameter to the two bf16 layouts in one launch, zero in the padded channels.
+//
+// The _from16 entry points (act_storage = "bf16") run the same two kernels on an activation that is ALREADY bf16 in memory
+// (same NHWC shape, same pixel stride in elements): the loader copies where the fp32 one rounds, and everything behind it
+// -- the LDS image, the MFMA order, the epilogue, the slabs -- is the same code, so the result is bit for bit that of the
+// fp32 tensor which rounds to this one.  The convolution's loader takes 8 bf16 (16 bytes) of one pixel per thread, four
+// threads a pixel's 32-channel chunk, and stores them with one ds_write_b128 (the weight tile's shape); the weight gradient's
+// keeps its thread map (four channels of two neighbouring pixels, now two 8-byte loads) and pairs the halves of the two
+// pixels' dwords for the same four transposed ds_write_b32.
+#include <type_traits>
+
 #include "common.hip.h"
 
 namespace {
@@ -31,17 +41,21 @@ __device__ __forceinline__ bf16x8 cv_frag(const cv_bf16 (*img)[CV_LD], int row, 
 }
 
 // ------------------------------------------------------------------------------------------------ convolution
+// A16: a.src points at bf16 (8 per thread and chunk, one row) instead of fp32 (4 per thread and chunk, two rows)
+template <bool A16>
 __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const cv_bf16* __restrict__ w) {
   __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [pixel][k]
   __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [output channel][k]
-  constexpr int UA = CV_T / 32;
+  constexpr int UA = A16 ? 1 : CV_T / 32;
+  using RA = std::conditional_t<A16, uint4, float4>;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
   const long M = (long)a.B * a.Ho * a.Wo;
   const long p0 = (long)blockIdx.x * CV_T;
   const int n0 = blockIdx.y * CV_T;
   const int ks = a.ksize, pad = ks == 3 ? 1 : 0, nch = a.Cin / CV_KC, K = ks * ks * a.Cin;
-  const int lr = tid >> 3, lk = (tid & 7) * 4;       // activations: rows lr and lr + 32, 4 floats at k offset lk
+  // activations: rows lr and lr + 32, 4 floats at k offset lk; in bf16 row lr, 8 bf16 at k offset lk
+  const int lr = A16 ? tid >> 2 : tid >> 3, lk = A16 ? (tid & 3) * 8 : (tid & 7) * 4;
   const int wr = tid >> 2, wk = (tid & 3) * 8;       // weights: row wr, 8 bf16 at k offset wk
   int pb[UA], py[UA], px[UA];
   bool pv[UA];
@@ -58,16 +72,24 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
   auto fa = [&](int q, int u) {
     const int tap = q / nch, c0 = (q - tap * nch) * CV_KC;
     const int iy = py[u] - pad + tap / ks, ix = px[u] - pad + tap % ks;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (pv[u] && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi)
-      v = *reinterpret_cast<const float4*>(a.src + (((long)pb[u] * a.Hi + iy) * a.Wi + ix) * a.Cin + c0 + lk);
-    return v;
+    if constexpr (A16) {
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (pv[u] && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi)
+        v = *reinterpret_cast<const uint4*>(reinterpret_cast<const cv_bf16*>(a.src) +
+                                            (((long)pb[u] * a.Hi + iy) * a.Wi + ix) * a.Cin + c0 + lk);
+      return v;
+    } else {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (pv[u] && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi)
+        v = *reinterpret_cast<const float4*>(a.src + (((long)pb[u] * a.Hi + iy) * a.Wi + ix) * a.Cin + c0 + lk);
+      return v;
+    }
   };
   auto fb = [&](int q) { return *reinterpret_cast<const uint4*>(w + (long)(n0 + wr) * K + q * CV_KC + wk); };
   cv_f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  float4 ra[UA];
+  RA ra[UA];
   uint4 rb;
 #pragma unroll
   for (int u = 0; u < UA; ++u) ra[u] = fa(0, u);
@@ -77,8 +99,10 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
   for (int q = 0; q < nq; ++q) {
     __syncthreads();                                  // the previous chunk's reads of the tiles are done
 #pragma unroll
-    for (int u = 0; u < UA; ++u)
-      *reinterpret_cast<uint2*>(&sa[lr + 32 * u][lk]) = make_uint2(pack_bf16x2(ra[u].x, ra[u].y), pack_bf16x2(ra[u].z, ra[u].w));
+    for (int u = 0; u < UA; ++u) {
+      if constexpr (A16) *reinterpret_cast<uint4*>(&sa[lr][lk]) = ra[u];
+      else *reinterpret_cast<uint2*>(&sa[lr + 32 * u][lk]) = make_uint2(pack_bf16x2(ra[u].x, ra[u].y), pack_bf16x2(ra[u].z, ra[u].w));
+    }
     *reinterpret_cast<uint4*>(&sb[wr][wk]) = rb;
     __syncthreads();
     if (q + 1 < nq) {
@@ -106,11 +130,13 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 struct CvWgradDev {
-  const float* dy; const float* a; float* work;
+  const float* dy; const void* a; float* work;      // a: fp32, or bf16 for the A16 kernel
   long M, nchunks;
   int H, W, Cin, Cout, ks, chunks_per_split;
 };
 
+// A16: d.a points at bf16; rb then holds the four channels of a pixel as two dwords of bf16 pairs
+template <bool A16>
 __global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
   __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [output channel][pixel of the chunk]
   __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [input channel][pixel of the chunk]
@@ -123,19 +149,23 @@ __global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
   const long c0 = (long)blockIdx.z * d.chunks_per_split;
   const long c1 = c0 + d.chunks_per_split < d.nchunks ? c0 + d.chunks_per_split : d.nchunks;
   const int lp = (tid >> 4) * 2, lc = (tid & 15) * 4;         // loader: pixels lp and lp + 1 of the chunk, 4 channels
-  float4 ra[2], rb[2];
+  using RB = std::conditional_t<A16, uint2, float4>;
+  float4 ra[2];
+  RB rb[2];
   auto fetch = [&](long q) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long p = q * CV_KC + lp + u;
       ra[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      rb[u] = ra[u];
+      if constexpr (A16) rb[u] = make_uint2(0u, 0u);
+      else rb[u] = ra[u];
       if (p < d.M) {
         ra[u] = *reinterpret_cast<const float4*>(d.dy + p * d.Cout + co0 + lc);
         const int x = (int)(p % d.W), y = (int)((p / d.W) % d.H);
         const int yy = y + oy, xx = x + ox;
         if (yy >= 0 && yy < d.H && xx >= 0 && xx < d.W)        // same image: the shifted pixel is p + oy * W + ox
-          rb[u] = *reinterpret_cast<const float4*>(d.a + (p + (long)oy * d.W + ox) * d.Cin + ci0 + lc);
+          rb[u] = *reinterpret_cast<const RB*>(static_cast<const std::conditional_t<A16, cv_bf16, float>*>(d.a) +
+                                               (p + (long)oy * d.W + ox) * d.Cin + ci0 + lc);
       }
     }
   };
@@ -150,10 +180,17 @@ __global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
     *reinterpret_cast<unsigned*>(&sa[lc + 1][lp]) = pack_bf16x2(ra[0].y, ra[1].y);
     *reinterpret_cast<unsigned*>(&sa[lc + 2][lp]) = pack_bf16x2(ra[0].z, ra[1].z);
     *reinterpret_cast<unsigned*>(&sa[lc + 3][lp]) = pack_bf16x2(ra[0].w, ra[1].w);
-    *reinterpret_cast<unsigned*>(&sb[lc][lp]) = pack_bf16x2(rb[0].x, rb[1].x);
-    *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = pack_bf16x2(rb[0].y, rb[1].y);
-    *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = pack_bf16x2(rb[0].z, rb[1].z);
-    *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = pack_bf16x2(rb[0].w, rb[1].w);
+    if constexpr (A16) {                                      // (low half: the even channel, and the first pixel of a pair)
+      *reinterpret_cast<unsigned*>(&sb[lc][lp]) = (rb[0].x & 0xffffu) | (rb[1].x << 16);
+      *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = (rb[0].x >> 16) | (rb[1].x & 0xffff0000u);
+      *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = (rb[0].y & 0xffffu) | (rb[1].y << 16);
+      *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = (rb[0].y >> 16) | (rb[1].y & 0xffff0000u);
+    } else {
+      *reinterpret_cast<unsigned*>(&sb[lc][lp]) = pack_bf16x2(rb[0].x, rb[1].x);
+      *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = pack_bf16x2(rb[0].y, rb[1].y);
+      *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = pack_bf16x2(rb[0].z, rb[1].z);
+      *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = pack_bf16x2(rb[0].w, rb[1].w);
+    }
     __syncthreads();
     if (q + 1 < c1) fetch(q + 1);
 #pragma unroll
@@ -202,48 +239,78 @@ __global__ void dn_pack_conv16_kernel(const float* __restrict__ w, unsigned* fwd
 }
 }  // namespace
 
-extern "C" int ld_dn_conv16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  LD_REQUIRE(a, "ld_dn_conv16: null args");
-  LD_REQUIRE(a->ksize == 1 || a->ksize == 3, "ld_dn_conv16: ksize %d (1 or 3)", a->ksize);
-  LD_REQUIRE(a->stride == 1, "ld_dn_conv16: stride %d (1 only)", a->stride);
-  LD_REQUIRE(a->B > 0 && a->Hi > 0 && a->Wi > 0, "ld_dn_conv16: empty input B=%d H=%d W=%d", a->B, a->Hi, a->Wi);
-  LD_REQUIRE(a->Ho == a->Hi && a->Wo == a->Wi, "ld_dn_conv16: output %dx%d does not match input %dx%d at stride 1", a->Ho, a->Wo,
+namespace {
+// ld_dn_conv16 and ld_dn_conv16_from16: `name` is the entry point's, `a16` says what args->src points at
+int cv_conv(const char* name, bool a16, const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  LD_REQUIRE(a, "%s: null args", name);
+  LD_REQUIRE(a->ksize == 1 || a->ksize == 3, "%s: ksize %d (1 or 3)", name, a->ksize);
+  LD_REQUIRE(a->stride == 1, "%s: stride %d (1 only)", name, a->stride);
+  LD_REQUIRE(a->B > 0 && a->Hi > 0 && a->Wi > 0, "%s: empty input B=%d H=%d W=%d", name, a->B, a->Hi, a->Wi);
+  LD_REQUIRE(a->Ho == a->Hi && a->Wo == a->Wi, "%s: output %dx%d does not match input %dx%d at stride 1", name, a->Ho, a->Wo,
              a->Hi, a->Wi);
-  LD_REQUIRE(a->Cin > 0 && a->Cin % CV_KC == 0, "ld_dn_conv16: Cin %d (a multiple of 32)", a->Cin);
-  LD_REQUIRE(a->Cout > 0 && a->Cout % CV_T == 0, "ld_dn_conv16: Cout %d (a multiple of 64)", a->Cout);
-  LD_REQUIRE(a->src && weight_bf16 && a->scale && a->shift && a->out, "ld_dn_conv16: null pointer");
-  LD_REQUIRE(((uintptr_t)a->src | (uintptr_t)weight_bf16) % 16 == 0, "ld_dn_conv16: src and weight must be 16-byte aligned");
+  LD_REQUIRE(a->Cin > 0 && a->Cin % CV_KC == 0, "%s: Cin %d (a multiple of 32)", name, a->Cin);
+  LD_REQUIRE(a->Cout > 0 && a->Cout % CV_T == 0, "%s: Cout %d (a multiple of 64)", name, a->Cout);
+  LD_REQUIRE(a->src && weight_bf16 && a->scale && a->shift && a->out, "%s: null pointer", name);
+  LD_REQUIRE(((uintptr_t)a->src | (uintptr_t)weight_bf16) % 16 == 0, "%s: src%s and weight must be 16-byte aligned", name,
+             a16 ? " (bf16)" : "");
   const long M = (long)a->B * a->Ho * a->Wo;
-  LD_REQUIRE((M + CV_T - 1) / CV_T < (1L << 31), "ld_dn_conv16: %ld pixels", M);
-  LD_REQUIRE((long)a->ksize * a->ksize * a->Cin < (1L << 31), "ld_dn_conv16: K %ld", (long)a->ksize * a->ksize * a->Cin);
+  LD_REQUIRE((M + CV_T - 1) / CV_T < (1L << 31), "%s: %ld pixels", name, M);
+  LD_REQUIRE((long)a->ksize * a->ksize * a->Cin < (1L << 31), "%s: K %ld", name, (long)a->ksize * a->ksize * a->Cin);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((M + CV_T - 1) / CV_T), (unsigned)(a->Cout / CV_T));
-  LD_LAUNCH(dn_conv16_kernel, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
-  LD_LAUNCH_CHECK("dn_conv16");
+  if (a16) {
+    LD_LAUNCH(dn_conv16_kernel<true>, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
+  } else {
+    LD_LAUNCH(dn_conv16_kernel<false>, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
+  }
+  LD_LAUNCH_CHECK(a16 ? "dn_conv16_from16" : "dn_conv16");
   return LD_OK;
+}
+
+int cv_wgrad(const char* name, bool a16, const float* dy, const void* a, float* work, float* dw, int B, int H, int W, int Cin,
+             int Cout, int ksize, int splits, void* stream) {
+  LD_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize %d (1 or 3)", name, ksize);
+  LD_REQUIRE(B > 0 && H > 0 && W > 0, "%s: empty shape B=%d H=%d W=%d", name, B, H, W);
+  LD_REQUIRE(Cin > 0 && Cin % CV_T == 0, "%s: Cin %d (a multiple of 64)", name, Cin);
+  LD_REQUIRE(Cout > 0 && Cout % CV_T == 0, "%s: Cout %d (a multiple of 64)", name, Cout);
+  const long M = (long)B * H * W, nchunks = (M + CV_KC - 1) / CV_KC;
+  LD_REQUIRE(splits >= 1 && splits <= nchunks && splits <= 65535, "%s: splits %d (1..min(%ld, 65535))", name, splits, nchunks);
+  const long tiles = (long)(Cin / CV_T) * (Cout / CV_T);
+  LD_REQUIRE(tiles < (1L << 31), "%s: %ld tiles", name, tiles);
+  LD_REQUIRE(dy && a && work && dw, "%s: null pointer", name);
+  LD_REQUIRE(((uintptr_t)dy | (uintptr_t)a) % 16 == 0, "%s: dy and a%s must be 16-byte aligned", name, a16 ? " (bf16)" : "");
+  const long per = (nchunks + splits - 1) / splits;
+  CvWgradDev d{dy, a, work, M, nchunks, H, W, Cin, Cout, ksize, (int)per};
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles, (unsigned)(ksize * ksize), (unsigned)splits);
+  if (a16) {
+    LD_LAUNCH(dn_wgrad16_kernel<true>, grid, dim3(256), 0, st, d);
+  } else {
+    LD_LAUNCH(dn_wgrad16_kernel<false>, grid, dim3(256), 0, st, d);
+  }
+  const long n = (long)Cout * ksize * ksize * Cin;
+  LD_LAUNCH(dn_wgrad16_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, dw, n, splits);
+  LD_LAUNCH_CHECK(a16 ? "dn_wgrad16_from16" : "dn_wgrad16");
+  return LD_OK;
+}
+}  // namespace
+
+extern "C" int ld_dn_conv16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  return cv_conv("ld_dn_conv16", false, a, weight_bf16, stream);
+}
+
+extern "C" int ld_dn_conv16_from16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  return cv_conv("ld_dn_conv16_from16", true, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
                              int ksize, int splits, void* stream) {
-  LD_REQUIRE(ksize == 1 || ksize == 3, "ld_dn_wgrad16: ksize %d (1 or 3)", ksize);
-  LD_REQUIRE(B > 0 && H > 0 && W > 0, "ld_dn_wgrad16: empty shape B=%d H=%d W=%d", B, H, W);
-  LD_REQUIRE(Cin > 0 && Cin % CV_T == 0, "ld_dn_wgrad16: Cin %d (a multiple of 64)", Cin);
-  LD_REQUIRE(Cout > 0 && Cout % CV_T == 0, "ld_dn_wgrad16: Cout %d (a multiple of 64)", Cout);
-  const long M = (long)B * H * W, nchunks = (M + CV_KC - 1) / CV_KC;
-  LD_REQUIRE(splits >= 1 && splits <= nchunks && splits <= 65535, "ld_dn_wgrad16: splits %d (1..min(%ld, 65535))", splits,
-             nchunks);
-  const long tiles = (long)(Cin / CV_T) * (Cout / CV_T);
-  LD_REQUIRE(tiles < (1L << 31), "ld_dn_wgrad16: %ld tiles", tiles);
-  LD_REQUIRE(dy && a && work && dw, "ld_dn_wgrad16: null pointer");
-  LD_REQUIRE(((uintptr_t)dy | (uintptr_t)a) % 16 == 0, "ld_dn_wgrad16: dy and a must be 16-byte aligned");
-  const long per = (nchunks + splits - 1) / splits;
-  CvWgradDev d{dy, a, work, M, nchunks, H, W, Cin, Cout, ksize, (int)per};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LD_LAUNCH(dn_wgrad16_kernel, dim3((unsigned)tiles, (unsigned)(ksize * ksize), (unsigned)splits), dim3(256), 0, st, d);
-  const long n = (long)Cout * ksize * ksize * Cin;
-  LD_LAUNCH(dn_wgrad16_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, dw, n, splits);
-  LD_LAUNCH_CHECK("dn_wgrad16");
-  return LD_OK;
+  return cv_wgrad("ld_dn_wgrad16", false, dy, a, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
+}
+
+extern "C" int ld_dn_wgrad16_from16(const float* dy, const void* a_bf16, float* work, float* dw, int B, int H, int W, int Cin,
+                                    int Cout, int ksize, int splits, void* stream) {
+  return cv_wgrad("ld_dn_wgrad16_from16", true, dy, a_bf16, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
 }
 
 extern "C" int ld_dn_pack_conv16(const float* w_oihw, void* fwd_bf16, void* dgr_bf16, int co, int cop, int ci, int cip, int k,

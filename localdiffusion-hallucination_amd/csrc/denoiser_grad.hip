@@ -13,10 +13,21 @@
 // to fill the chip at the small maps.  The sums of a workgroup meet inside each wave first (where the lanes of a wave hold
 // whole rows of pixels), then once through LDS.  sigma(a) is v_exp_f32 + v_rcp_f32 (1 ulp each): with libm's expf and an
 // IEEE divide the passes would be VALU-bound, and the difference is two orders below the fp32 tolerance of the results.
+//
+// ld_dn_gn_forward_to16 and ld_dn_pack_nhwc_to16 (act_storage = "bf16") are the same passes writing bf16: the fp32 value is
+// computed by the same code and rounded to nearest even on its way out (pack_bf16x2, what the bf16 convolutions' loaders do
+// to an fp32 activation), so a convolution that reads the result computes what it computes from the fp32 tensor.
+#include <type_traits>
+
 #include "common.hip.h"
 #include "dn_common.hip.h"
 
 namespace {
+
+// four consecutive channels of a bf16 activation: rounded to nearest even, one 8-byte store
+__device__ __forceinline__ void st4(bf16* p, float a, float b, float c, float d) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
+}
 
 __device__ __forceinline__ float dn_sigmoid(float a) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * a));
@@ -101,9 +112,11 @@ __device__ __forceinline__ DnCoef dn_coef(const float* stat, const float* gamma,
 }
 
 // ---------------------------------------------------------------- forward, pass 2: out = silu(a) (+ residual)
+// TO: float, or bf16 (out has the same pixel stride in elements)
+template <typename TO>
 __global__ __launch_bounds__(DN_BS) void dn_gn_apply_kernel(const float* __restrict__ y, const float* __restrict__ stat,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            const float* __restrict__ film, const float* residual, float* out,
+                                                            const float* __restrict__ film, const float* residual, TO* out,
                                                             long HW, int C, int ldc, int G, long ppc) {
   const DnPos t = dn_pos(ldc / 4, HW, ppc);
   if (!t.active) return;
@@ -354,17 +367,28 @@ __global__ __launch_bounds__(256) void dn_time_proj_bwd_kernel(const float* __re
 
 // ---------------------------------------------------------------- layouts
 // out [B, H, W, ldc] (channels C..ldc-1 zero) from a tensor [B, C, H, W] of any strides
-__global__ __launch_bounds__(256) void dn_pack_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, long n, int C,
-                                                           int H, int W, long sb, long sc, long sh, long sw, int ldc) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ float dn_nchw_at(const float* __restrict__ x, long i, int C, int H, int W, long sb, long sc, long sh,
+                                            long sw, int ldc) {
   const int c = (int)(i % ldc);
   long p = i / ldc;
   const int xx = (int)(p % W);
   p /= W;
   const int yy = (int)(p % H);
   const long b = p / H;
-  out[i] = c < C ? x[b * sb + c * sc + yy * sh + xx * sw] : 0.0f;
+  return c < C ? x[b * sb + c * sc + yy * sh + xx * sw] : 0.0f;
+}
+__global__ __launch_bounds__(256) void dn_pack_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, long n, int C,
+                                                           int H, int W, long sb, long sc, long sh, long sw, int ldc) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = dn_nchw_at(x, i, C, H, W, sb, sc, sh, sw, ldc);
+}
+// the same in bf16: one thread per pair of neighbouring channels (ldc even), n the number of pairs
+__global__ __launch_bounds__(256) void dn_pack_nhwc_to16_kernel(const float* __restrict__ x, unsigned* __restrict__ out, long n,
+                                                                int C, int H, int W, long sb, long sc, long sh, long sw, int ldc) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = pack_bf16x2(dn_nchw_at(x, 2 * i, C, H, W, sb, sc, sh, sw, ldc), dn_nchw_at(x, 2 * i + 1, C, H, W, sb, sc, sh, sw, ldc));
 }
 // out [d0][d1][d2] (contiguous) from in[off + i0 s0 + i1 s1 + i2 s2]: ld_seg_permute3's inverse
 __global__ __launch_bounds__(256) void dn_gather3_kernel(const float* __restrict__ in, float* __restrict__ out, long n, int d1,
@@ -427,15 +451,19 @@ extern "C" int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C) {
   return (int64_t)B * (nchunk + 2) * C * 2 * (int64_t)sizeof(double);
 }
 
-extern "C" int ld_dn_gn_forward(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
-                                double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups,
-                                void* stream) {
+namespace {
+// ld_dn_gn_forward (TO = float) and ld_dn_gn_forward_to16 (TO = bf16)
+template <typename TO>
+int dn_gn_forward(const char* name, const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
+                  double* work, float* stat, TO* out, int B, int H, int W, int C, int ldc, int groups, void* stream) {
   LD_REQUIRE(dn_gn_shape_ok(B, H, W, C, ldc, groups),
-             "ld_dn_gn_forward: B=%d H=%d W=%d C=%d ldc=%d groups=%d (C a multiple of 4 * groups, ldc >= C a multiple of 4)", B,
-             H, W, C, ldc, groups);
-  LD_REQUIRE(y && gamma && beta && work && stat && out, "ld_dn_gn_forward: null pointer");
+             "%s: B=%d H=%d W=%d C=%d ldc=%d groups=%d (C a multiple of 4 * groups, ldc >= C a multiple of 4)", name, B, H, W, C,
+             ldc, groups);
+  LD_REQUIRE(y && gamma && beta && work && stat && out, "%s: null pointer", name);
   LD_REQUIRE(dn_aligned16(y) && dn_aligned16(gamma) && dn_aligned16(beta) && dn_aligned16(film) && dn_aligned16(residual) &&
-                 dn_aligned16(out), "ld_dn_gn_forward: a pointer is not 16-byte aligned");
+                 dn_aligned16(out), "%s: a pointer is not 16-byte aligned", name);
+  LD_REQUIRE((std::is_same<TO, float>::value) || static_cast<const void*>(residual) != static_cast<const void*>(out),
+             "%s: residual (fp32) cannot alias out (bf16)", name);
   const long HW = (long)H * W;
   hipStream_t st = dn_st(stream);
   long ppc;
@@ -448,10 +476,24 @@ extern "C" int ld_dn_gn_forward(const float* y, const float* gamma, const float*
   long ppa;
   int na;
   dn_runs(B, HW, ldc / 4, ppa, na);
-  LD_LAUNCH(dn_gn_apply_kernel, dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS), 0,
-            st, y, (const float*)stat, gamma, beta, film, residual, out, HW, C, ldc, groups, ppa);
-  LD_LAUNCH_CHECK("dn_gn_forward");
+  LD_LAUNCH(dn_gn_apply_kernel<TO>, dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS),
+            0, st, y, (const float*)stat, gamma, beta, film, residual, out, HW, C, ldc, groups, ppa);
+  LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
+}
+}  // namespace
+
+extern "C" int ld_dn_gn_forward(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
+                                double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups,
+                                void* stream) {
+  return dn_gn_forward<float>("ld_dn_gn_forward", y, gamma, beta, film, residual, work, stat, out, B, H, W, C, ldc, groups, stream);
+}
+
+extern "C" int ld_dn_gn_forward_to16(const float* y, const float* gamma, const float* beta, const float* film,
+                                     const float* residual, double* work, float* stat, void* out_bf16, int B, int H, int W, int C,
+                                     int ldc, int groups, void* stream) {
+  return dn_gn_forward<bf16>("ld_dn_gn_forward_to16", y, gamma, beta, film, residual, work, stat, static_cast<bf16*>(out_bf16), B, H,
+                             W, C, ldc, groups, stream);
 }
 
 extern "C" int ld_dn_gn_backward(const float* dout, const float* y, const float* stat, const float* gamma, const float* beta,
@@ -532,6 +574,22 @@ extern "C" int ld_dn_pack_nhwc(const float* x, float* out, int B, int C, int H, 
   LD_LAUNCH(dn_pack_nhwc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dn_st(stream), x, out, n, C, H, W, (long)sb,
             (long)sc, (long)sh, (long)sw, ldc);
   LD_LAUNCH_CHECK("dn_pack_nhwc");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_pack_nhwc_to16(const float* x, void* out_bf16, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh,
+                                    int64_t sw, int ldc, void* stream) {
+  LD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && ldc >= C, "ld_dn_pack_nhwc_to16: shape B=%d C=%d H=%d W=%d ldc=%d", B, C, H, W,
+             ldc);
+  LD_REQUIRE(ldc % 2 == 0, "ld_dn_pack_nhwc_to16: ldc %d (even)", ldc);
+  LD_REQUIRE(sb >= 0 && sc >= 0 && sh >= 0 && sw >= 0, "ld_dn_pack_nhwc_to16: negative stride");
+  LD_REQUIRE(x && out_bf16, "ld_dn_pack_nhwc_to16: null pointer");
+  LD_REQUIRE(reinterpret_cast<uintptr_t>(out_bf16) % 4 == 0, "ld_dn_pack_nhwc_to16: out must be 4-byte aligned");
+  const long n = (long)B * H * W * ldc / 2;
+  LD_REQUIRE((n + 255) / 256 < (1L << 31), "ld_dn_pack_nhwc_to16: %ld elements", 2 * n);
+  LD_LAUNCH(dn_pack_nhwc_to16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dn_st(stream), x,
+            static_cast<unsigned*>(out_bf16), n, C, H, W, (long)sb, (long)sc, (long)sh, (long)sw, ldc);
+  LD_LAUNCH_CHECK("dn_pack_nhwc_to16");
   return LD_OK;
 }
 

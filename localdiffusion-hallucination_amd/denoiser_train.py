@@ -42,7 +42,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import check_conv_precision, stream
+from .trainable import check_act_storage, check_act_storage_precision, check_conv_precision, stream
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -148,13 +148,19 @@ class DenoiserTrainer:
     memory and everything else fp32, no loss scaling; the step stays reproducible bit for bit.  Checkpoints do not record it
     (the weights are the fp32 masters) and the EMA / inference ``Unet`` is not touched.
 
+    ``act_storage="bf16"`` (default ``"fp32"``; with ``conv_precision="bf16"`` only, refused otherwise) keeps the activations
+    that only convolutions read as bf16 (``TrainableUnet.act_storage``): less memory and traffic, the same bits in the loss,
+    every gradient and every parameter -- so a data-parallel run needs nothing new and a checkpoint does not record it either.
+
     ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
     ``ema_initted`` are ``ema_pytorch``'s two buffers."""
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
-                 conv_precision="fp32"):
+                 conv_precision="fp32", act_storage="fp32"):
         check_conv_precision("DenoiserTrainer", conv_precision)
+        check_act_storage("DenoiserTrainer", act_storage)
+        check_act_storage_precision("DenoiserTrainer", act_storage, conv_precision)
         if group is not None and comm is not None:
             raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
         model = getattr(diffusion, "model", None)
@@ -176,8 +182,8 @@ class DenoiserTrainer:
             if not isinstance(v, int) or isinstance(v, bool) or v < lo:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
         # (raises ValueError for what it cannot train)
-        online = TrainableUnet(**online_kwargs(model), conv_precision=conv_precision)
-        self.conv_precision = conv_precision
+        online = TrainableUnet(**online_kwargs(model), conv_precision=conv_precision, act_storage=act_storage)
+        self.conv_precision, self.act_storage = conv_precision, act_storage
         dev = diffusion.device
         if dev.type != "cuda":
             raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")

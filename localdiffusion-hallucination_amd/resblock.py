@@ -21,13 +21,14 @@ the input checks are ``trainable.py``'s, shared with the two attention modules.
 NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``, full
 attention is in ``attention_grad.py``, Down/Upsample, the 7x7 stem, the head and the plain 3x3 are in ``resample.py``, the
 ResUnet condition encoder is in ``condenc.py``, the time MLP in front of the blocks and ``TrainableUnet`` assembling the
-backward of its blocks are in ``unet_grad.py``): a fused optimiser / EMA step, a ``Trainer``, and 16-bit storage.
+backward of its blocks are in ``unet_grad.py``): 16-bit storage beyond ``act_storage``'s conv-only activations (the
+convolution outputs ``y1`` / ``y2``, gradients).
 """
 import torch
 from torch import nn
 
 from . import _cabi as cabi
-from .trainable import Run, TrainableModule, ones_zeros, pack_conv, pack_vec, pad64, stream
+from .trainable import Run, TrainableModule, check_act_storage_precision, ones_zeros, pack_conv, pack_vec, pad64, stream
 
 
 class _Block(nn.Module):
@@ -63,13 +64,15 @@ class _Run(Run):
     def gn_work(self):
         return self.work(self.lib.ld_dn_gn_work_bytes(self.B, self.H, self.W, self.mod.dim_out))
 
-    def gn_forward(self, y, gamma, beta, film, residual, out=None):
+    def gn_forward(self, y, gamma, beta, film, residual, out=None, dtype=torch.float32):
+        """``dtype``: of a fresh ``out``; ``torch.bfloat16`` for one that only bf16 convolutions read."""
         blk = self.mod
         stat = self.empty(self.B, blk.groups, 2)
-        out = self.empty(self.B, self.H, self.W, blk.cop) if out is None else out
-        cabi.check(self.lib.ld_dn_gn_forward(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), cabi.ptr(film), cabi.ptr(residual),
-                                             self.gn_work().data_ptr(), stat.data_ptr(), out.data_ptr(), self.B, self.H, self.W,
-                                             blk.dim_out, blk.cop, blk.groups, self.st), "dn_gn_forward")
+        out = self.empty(self.B, self.H, self.W, blk.cop, dtype=dtype) if out is None else out
+        to16 = out.dtype == torch.bfloat16
+        fn, what = (self.lib.ld_dn_gn_forward_to16, "dn_gn_forward_to16") if to16 else (self.lib.ld_dn_gn_forward, "dn_gn_forward")
+        cabi.check(fn(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), cabi.ptr(film), cabi.ptr(residual), self.gn_work().data_ptr(),
+                      stat.data_ptr(), out.data_ptr(), self.B, self.H, self.W, blk.dim_out, blk.cop, blk.groups, self.st), what)
         return out, stat
 
     def gn_backward(self, dout, y, stat, gamma, beta, film, dy):
@@ -86,7 +89,10 @@ class _Run(Run):
     def forward(self, x, temb, keep=True):              # (keep: the GroupNorm kernels always write their statistics)
         blk, p, lib = self.mod, self.p, self.lib
         ci, co, cip, cop = blk.dim, blk.dim_out, blk.cip, blk.cop
-        xp = self.nhwc(x, ci, cip)
+        # act_storage "bf16": what only the convolutions read is bf16 -- h1 always; the block's own copy of x where a res_conv
+        # reads it (without one it is also the fp32 residual of the second GroupNorm; an x read in place is no copy)
+        a16 = torch.bfloat16 if self.act16 else torch.float32
+        xp = self.nhwc(x, ci, cip, dtype=a16 if blk.has_res_conv else torch.float32)
         film = None
         if temb is not None:
             temb = temb.contiguous()
@@ -95,7 +101,7 @@ class _Run(Run):
             cabi.check(lib.ld_dn_time_proj(temb.data_ptr(), w.data_ptr(), b.data_ptr(), film.data_ptr(), self.B, temb.shape[1],
                                            2 * co, self.st), "dn_time_proj")
         y1 = self.conv(xp, p.w1f, p.b1, cip, cop, 3)
-        h1, stat1 = self.gn_forward(y1, p.g1, p.be1, film, None)
+        h1, stat1 = self.gn_forward(y1, p.g1, p.be1, film, None, dtype=a16)
         y2 = self.conv(h1, p.w2f, p.b2, cop, cop, 3)
         res = self.conv(xp, p.wrf, p.br, cip, cop, 1) if blk.has_res_conv else xp
         out, stat2 = self.gn_forward(y2, p.g2, p.be2, None, res, out=res if blk.has_res_conv else None)
@@ -136,9 +142,15 @@ class ResnetBlock(TrainableModule):
     ``forward(x, time_emb=None)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is
     read in place), ``time_emb`` [B, time_emb_dim]; returns [B, dim_out, H, W] (a ``channels_last``-strided view of the
     kernels' NHWC output).  ``dim`` and ``dim_out`` are multiples of 32, ``groups`` divides ``dim_out`` with ``dim_out /
-    groups`` a multiple of 4; any H, W >= 1."""
+    groups`` a multiple of 4; any H, W >= 1.
+
+    ``act_storage = "bf16"`` (with ``conv_precision = "bf16"``; refused with ``ValueError`` otherwise): block1's GroupNorm ->
+    FiLM -> SiLU output, and the block's padded NHWC copy of ``x`` when it has a ``res_conv`` and makes one, are written, read
+    and saved for the backward as bf16 -- what every convolution that reads them rounds them to anyway, so the output and
+    every gradient keep their bits.  The convolution outputs, the statistics, all gradients and the result stay fp32."""
 
     Run = _Run
+    ACT_STORAGES = ("fp32", "bf16")
 
     def __init__(self, dim, dim_out, *, time_emb_dim=None, groups=8):
         super().__init__()
@@ -166,4 +178,5 @@ class ResnetBlock(TrainableModule):
                 raise ValueError(f"ResnetBlock: time_emb must be float32 [{x.shape[0]}, {self.time_emb_dim}] on {x.device}")
 
     def forward(self, x, time_emb=None):
+        check_act_storage_precision("ResnetBlock", self.act_storage, self.conv_precision)
         return super().forward(x, time_emb)

@@ -12,6 +12,13 @@ every module uses (``Run``: buffers, the NHWC repack, ``ld_pc_conv``, the weight
 ``pack_conv``, ``Run.conv`` and ``Run.wgrad_packed`` route on it.  At ``"bf16"`` the kernel-layout weights are bf16 and the
 convolution, its data gradient and its weight gradient run on ``csrc/conv16.hip`` (operands rounded to bf16, products on the
 bf16 matrix cores, fp32 accumulation); what sits in memory, and every other launch, is the same.
+
+``TrainableModule.act_storage`` (``"fp32"``, the default, or ``"bf16"``) says how a module keeps the activations that only its
+convolutions read.  At ``conv_precision="bf16"`` every convolution launch rounds such a tensor to bf16 on its way into LDS, so
+storing it as bf16 in the first place (``Run.nhwc(dtype=)``, a producer's ``_to16`` launch) changes no bit of any result and
+halves what the producer writes, what the convolutions read and what autograd keeps.  ``Run.conv`` and ``Run.wgrad_packed``
+pick the ``_from16`` entry point from the dtype of the activation they are handed.  A module accepts the values it implements
+(``ACT_STORAGES``): ``"bf16"`` on ``ResnetBlock`` only so far.
 """
 import ctypes as C
 
@@ -65,6 +72,19 @@ def check_conv_precision(name, value):
     return value
 
 
+def check_act_storage(name, value, allowed=("fp32", "bf16")):
+    if not isinstance(value, str) or value not in allowed:
+        raise ValueError(f"{name}: act_storage {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
+    return value
+
+
+def check_act_storage_precision(name, act_storage, conv_precision):
+    """bf16 storage of the conv-only activations is exact only where the convolutions round them to bf16 anyway."""
+    if act_storage == "bf16" and conv_precision != "bf16":
+        raise ValueError(f"{name}: act_storage 'bf16' needs conv_precision 'bf16' (the fp32 convolutions do not round their "
+                         "activations: the rounding would change results)")
+
+
 def pack_conv(lib, st, w, co, cop, ci, cip, k, precision="fp32"):
     """OIHW [co, ci, k, k] -> forward layout [cop][k*k][cip] and data-gradient layout [cip][flipped k*k][cop], zero in the
     padded channels; fp32, or with ``precision="bf16"`` rounded to bf16 (what ``Run.conv`` then takes), in one launch."""
@@ -111,6 +131,7 @@ class Run:
         self.lib, self.st = cabi.lib(), stream(dev)
         self.fill = mod.debug_fill
         self.bf16 = getattr(mod, "conv_precision", "fp32") == "bf16"      # (the precision ``packed`` was made at)
+        self.act16 = getattr(mod, "act_storage", "fp32") == "bf16"        # conv-only activations are kept as bf16
 
     def empty(self, *shape, dtype=torch.float32):
         t = torch.empty(*shape, dtype=dtype, device=self.dev)
@@ -125,15 +146,30 @@ class Run:
         """The map size of a launch: the run's own unless the caller names another (``hw = (H, W)``)."""
         return (self.H, self.W) if hw is None else hw
 
-    def nhwc(self, t, c, cp, hw=None):
-        """[B, c, H, W] of any strides -> NHWC with pixel stride cp; no copy when it already is that."""
+    def nhwc(self, t, c, cp, hw=None, dtype=torch.float32):
+        """[B, c, H, W] (fp32) of any strides -> NHWC with pixel stride cp; no copy when it already is that.  ``dtype`` is the
+        copy's: ``torch.bfloat16`` for one that only bf16 convolutions read (a tensor read in place stays what it is)."""
         B, (H, W) = self.B, self.hw(hw)
         if c == cp and t.stride() == (H * W * c, 1, W * c, c) and t.data_ptr() % 16 == 0:
             return t
-        out = self.empty(B, H, W, cp)
+        out = self.empty(B, H, W, cp, dtype=dtype)
         sb, sc, sh, sw = t.stride()
-        cabi.check(self.lib.ld_dn_pack_nhwc(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st), "pack_nhwc")
+        if dtype == torch.bfloat16:
+            cabi.check(self.lib.ld_dn_pack_nhwc_to16(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st),
+                       "pack_nhwc_to16")
+        else:
+            cabi.check(self.lib.ld_dn_pack_nhwc(t.data_ptr(), out.data_ptr(), B, c, H, W, sb, sc, sh, sw, cp, self.st), "pack_nhwc")
         return out
+
+    def from16(self, act):
+        """Whether ``act``, an activation a convolution launch is about to read, is bf16 in memory (the ``_from16`` entry
+        points); that is refused where the convolutions are fp32."""
+        if act.dtype != torch.bfloat16:
+            return False
+        if not self.bf16:
+            raise RuntimeError(f"{type(self.mod).__name__}: a bfloat16 activation at conv_precision 'fp32' (only the bf16 "
+                               "convolutions read 16-bit storage)")
+        return True
 
     def conv(self, src, weight, shift, cin, cout, k, residual=None, hw=None):
         H, W = self.hw(hw)
@@ -145,7 +181,10 @@ class Run:
         if (weight.dtype == torch.bfloat16) != self.bf16:
             raise RuntimeError(f"{type(self.mod).__name__}: a {weight.dtype} kernel-layout weight at conv_precision "
                                f"{'bf16' if self.bf16 else 'fp32'} (the module's _pack does not pass the precision on)")
-        if self.bf16:
+        if self.from16(src):
+            a.weight = None
+            cabi.check(self.lib.ld_dn_conv16_from16(C.byref(a), weight.data_ptr(), self.st), "dn_conv16_from16")
+        elif self.bf16:
             a.weight = None
             cabi.check(self.lib.ld_dn_conv16(C.byref(a), weight.data_ptr(), self.st), "dn_conv16")
         else:
@@ -159,7 +198,10 @@ class Run:
         kk = k * k
         splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cip, cop, k))
         work, dwp = self.empty(splits * cop * kk * cip), self.empty(cop * kk * cip)
-        wgrad, what = (self.lib.ld_dn_wgrad16, "dn_wgrad16") if self.bf16 else (self.lib.ld_seg_wgrad, "seg_wgrad")
+        if self.from16(a):
+            wgrad, what = self.lib.ld_dn_wgrad16_from16, "dn_wgrad16_from16"
+        else:
+            wgrad, what = (self.lib.ld_dn_wgrad16, "dn_wgrad16") if self.bf16 else (self.lib.ld_seg_wgrad, "seg_wgrad")
         cabi.check(wgrad(dy.data_ptr(), a.data_ptr(), work.data_ptr(), dwp.data_ptr(), B, H, W, cip, cop, k, splits, self.st), what)
         return dwp
 
@@ -216,11 +258,16 @@ class TrainableModule(PackedWeights, nn.Module):
     debug_fill = None       # a float: every buffer the module allocates is filled with it first (tests: NaN)
     conv_precision = "fp32"  # or "bf16": the operands of every convolution and of its two gradients are rounded to bf16 and
     #                          multiplied on the bf16 matrix cores with fp32 accumulation; everything else stays fp32
+    act_storage = "fp32"     # or "bf16" where the module has it (ACT_STORAGES): the activations that only its convolutions read
+    #                          are written, read and saved as bf16; at conv_precision "bf16" only, where no result changes
+    ACT_STORAGES = ("fp32",)
     Run = None
 
     def __setattr__(self, name, value):
         if name == "conv_precision":
             check_conv_precision(type(self).__name__, value)
+        elif name == "act_storage":
+            check_act_storage(type(self).__name__, value, self.ACT_STORAGES)
         super().__setattr__(name, value)
 
     def _run(self, x):

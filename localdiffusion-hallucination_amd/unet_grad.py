@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import check_conv_precision, pad64, stream
+from .trainable import check_act_storage, check_conv_precision, pad64, stream
 from .weights import UnetConfig
 
 
@@ -189,9 +189,11 @@ class TrainableUnet(nn.Module):
     def __init__(self, dim, init_dim=None, out_dim=None, dim_mults=(1, 2, 4, 8), channels=1, self_condition=False, cond_img=True,
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
-                 full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32"):
+                 full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
+                 act_storage="fp32"):
         super().__init__()
         check_conv_precision("TrainableUnet", conv_precision)
+        check_act_storage("TrainableUnet", act_storage)
         for flag, what in ((self_condition, "self_condition"), (learned_variance, "learned_variance"),
                            (learned_sinusoidal_cond, "learned_sinusoidal_cond"), (random_fourier_features, "random_fourier_features")):
             if flag:
@@ -250,6 +252,9 @@ class TrainableUnet(nn.Module):
         self._conv_precision = "fp32"
         if conv_precision != "fp32":                 # (the default is the modules' class attribute: nothing to hand down)
             self.conv_precision = conv_precision
+        self._act_storage = "fp32"
+        if act_storage != "fp32":
+            self.act_storage = act_storage
 
     @property
     def downsample_factor(self):
@@ -280,6 +285,20 @@ class TrainableUnet(nn.Module):
         for m in self.modules():
             if m is not self and hasattr(type(m), "conv_precision"):
                 m.conv_precision = value
+
+    @property
+    def act_storage(self):
+        return self._act_storage
+
+    @act_storage.setter
+    def act_storage(self, value):
+        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``ResnetBlock`` keeps the activations that only its convolutions read
+        as bf16 (``ResnetBlock``); that needs ``conv_precision = "bf16"``, where it changes no bit of any result.  The other
+        modules have no such storage yet and stay fp32."""
+        self._act_storage = check_act_storage("TrainableUnet", value)
+        for m in self.modules():
+            if isinstance(m, ResnetBlock):
+                m.act_storage = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

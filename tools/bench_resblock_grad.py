@@ -3,7 +3,7 @@
 restated in eager PyTorch (autograd, MIOpen convolutions) on the same GPU in one process, fp32, ms per forward + backward.
 
   python tools/bench_resblock_grad.py [--batch 8] [--iters 20] [--warmup 3] [--cases 32:256,64:128,128:64,256:32]
-                                      [--timeout 300]
+                                      [--timeout 300] [--conv-precision fp32|bf16] [--act-storage fp32|bf16]
 The default cases are cfg3's four levels (dim -> dim at H = W).  Every case runs in a child process of its own under a time
 limit (``--timeout`` seconds; the HIP and the eager block share that process), and the first case that fails or runs out of
 time ends the run: nothing more is started on the GPU after it.  Per case: 3 warm-up calls, then the median of 20 calls
@@ -12,7 +12,9 @@ layout; a channel count that is not a multiple of 64 is repacked with padding ei
 memory formats.  One more HIP call under the library's per-launch timing session gives the split of the time over the
 entry points, and the achieved bandwidth of the two GroupNorm-backward passes against 8 TB/s (bytes: dout and y read by
 each pass, dy written once; padded channels are written but never read).  Prints one line per case, the split, and a JSON
-list at the end.
+list at the end.  ``--conv-precision bf16`` runs the HIP block's convolutions on the bf16 matrix cores and ``--act-storage
+bf16`` (with it) keeps block1's activation as bf16 (``ResnetBlock.act_storage``; dim -> dim blocks have no ``res_conv``, so x
+stays fp32); eager PyTorch stays fp32.
 """
 import os
 import sys
@@ -50,6 +52,7 @@ def run_case(dim, H, a):
     B = a.batch
     torch.manual_seed(0)
     blk = ldh.ResnetBlock(dim, dim, time_emb_dim=TIME_DIM).cuda()
+    blk.conv_precision, blk.act_storage = a.conv_precision, a.act_storage
     x = torch.randn(B, dim, H, H, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
     temb = torch.randn(B, TIME_DIM, device="cuda").requires_grad_(True)
     dout = (torch.randn(B, dim, H, H, device="cuda") / (B * H * H)).contiguous(memory_format=torch.channels_last)
@@ -68,7 +71,7 @@ def run_case(dim, H, a):
     gn_pass_ms = sum((ms[0] + ms[2] for label, ms in calls if label == "dn_gn_backward" and len(ms) == 3), 0.0)
     eager = {} if a.no_eager else grad_bench.eager_ms(blk, eager_block, x, [temb], dout, a.iters, a.warmup)
     best = min(eager.values()) if eager else None
-    return dict(dim=dim, H=H, B=B, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(dim=dim, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), kernels_ms=sum(v[0] for v in split.values()),
                 gn_backward_passes_ms=gn_pass_ms,
                 gn_backward_gbs=(gn_bytes(dim, B, H) / (gn_pass_ms * 1e6) if gn_pass_ms else None),
@@ -80,7 +83,8 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:8.3f} ms, channels_last {r['eager_nhwc_ms']:8.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f})")
-    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']}: HIP {r['hip_ms']:8.3f} ms   {eg}")
+    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']} {r['conv_precision']} / act {r['act_storage']}: HIP {r['hip_ms']:8.3f} ms   "
+          f"{eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
     if r["gn_backward_gbs"]:
         print(f"      GroupNorm backward passes: {gn_bytes(r['dim'], r['B'], r['H']) / 1e6:.1f} MB in {r['gn_backward_passes_ms']:.3f} ms = "
@@ -89,4 +93,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report))
+    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report, conv_precision=True))

@@ -4,6 +4,7 @@ restated in eager PyTorch (autograd, MIOpen convolutions, ``F.group_norm``, eins
 fp32, ms per forward + backward.
 
   python tools/bench_unet_grad.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300] [--conv-precision fp32|bf16]
+                                  [--act-storage fp32|bf16]
 A case is data:H = W:batch; the default cases are cfg3 (mvtec, 3 x 256^2, B = 8), mri at 256^2 with B = 8 and mnist at 28^2
 with B = 64.  Every case runs in a child process of its own under a time limit (``--timeout`` seconds; the HIP and the eager
 net share that process), and the first case that fails or runs out of time ends the run: nothing more is started on the GPU
@@ -13,7 +14,9 @@ the library's per-launch timing session gives the launch count and the split of 
 with the boundary repacks (``dn_pack_nhwc``), the glue (``dn_join``) and the time MLP each named.  Prints one line per case,
 the split, and a JSON list at the end.  ``--conv-precision bf16`` times the HIP net with its convolutions on the bf16 matrix
 cores (``TrainableUnet(conv_precision="bf16")``); eager PyTorch stays fp32, and the printed output difference then holds the
-operands' rounding.
+operands' rounding.  ``--act-storage bf16`` (with ``--conv-precision bf16``) keeps the activations that only convolutions read
+as bf16 (``TrainableUnet(act_storage="bf16")``): the same results; the row's ``peak_mb`` (``torch.cuda.max_memory_allocated`` over
+the timed HIP calls) shows what it saves.
 """
 import os
 import sys
@@ -33,6 +36,7 @@ FAMILIES = (("dn_pack_nhwc", "dn_pack_nhwc (boundary repacks)"), ("dn_join", "dn
             ("dn_time_mlp", "time MLP"), ("dn_time_proj", "time projections"), ("pc_conv (forward)", "convolutions, forward"),
             ("pc_conv (data gradient)", "convolutions, data gradient"), ("seg_wgrad", "convolutions, weight gradient"),
             ("dn_conv16 (forward)", "convolutions, forward"), ("dn_conv16 (data gradient)", "convolutions, data gradient"),
+            ("dn_conv16_from16 (forward)", "convolutions, forward"), ("dn_conv16_from16 (data gradient)", "convolutions, data gradient"),
             ("dn_wgrad16", "convolutions, weight gradient"), ("dn_pack_conv16", "weight packing (bf16)"),
             ("dn_colsum", "bias gradients"), ("dn_gn", "GroupNorm"), ("dn_la_", "linear attention"), ("dn_fa_", "full attention"),
             ("dn_rms_", "RMSNorm"), ("dn_head_", "head"), ("seg_pool", "max pool"))
@@ -160,7 +164,7 @@ def families(split):
 def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
-    net = ldh.TrainableUnet(dim=32, conv_precision=a.conv_precision, **KWARGS[data]).cuda()
+    net = ldh.TrainableUnet(dim=32, conv_precision=a.conv_precision, act_storage=a.act_storage, **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -175,7 +179,9 @@ def run_case(data, H, B, a):
         out.backward(dout)
         return out
 
+    torch.cuda.reset_peak_memory_stats()
     hip = grad_bench.time_ms(hip_step, a.iters, a.warmup)
+    peak = torch.cuda.max_memory_allocated()
     split, _ = grad_bench.kernel_split(hip_step)
     fam = families(split)
     eager, diff = {}, None
@@ -183,7 +189,7 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, peak_mb=peak / 2 ** 20, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
                 kernels_ms=sum(v[0] for v in split.values()), launches=sum(v[1] for v in split.values()), split=fam)
 
@@ -193,8 +199,8 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:9.3f} ms, channels_last {r['eager_nhwc_ms']:9.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f}; outputs differ by {r['out_diff_to_eager']:.1e})")
-    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']}: HIP {r['hip_ms']:9.3f} ms, {r['launches']} launches, kernels "
-          f"{r['kernels_ms']:9.3f} ms   {eg}")
+    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']}: HIP {r['hip_ms']:9.3f} ms, "
+          f"peak {r['peak_mb']:8.1f} MiB, {r['launches']} launches, kernels {r['kernels_ms']:9.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
 
 

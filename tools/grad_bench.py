@@ -46,10 +46,10 @@ class TimedLib:
 
         def wrapped(*args):
             label = name[3:]
-            if name in ("ld_pc_conv", "ld_dn_conv16"):
+            if name in ("ld_pc_conv", "ld_dn_conv16", "ld_dn_conv16_from16"):
                 label += " (forward)" if self.phase == "forward" else " (data gradient)"
-            if name == "ld_dn_pack_nhwc":
-                label = f"dn_pack_nhwc ({self.phase})"
+            if name in ("ld_dn_pack_nhwc", "ld_dn_pack_nhwc_to16"):
+                label += f" ({self.phase})"
             n0 = self._lib.ld_timing_count()
             rc = fn(*args)
             self.calls.append((label, n0, self._lib.ld_timing_count()))
@@ -112,7 +112,7 @@ def print_split(split, kernels_ms):
 def main(tool, cases, run_case, report, heads=False, conv_precision=False):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
     returns the case's JSON row and ``report(row)`` prints it.  ``conv_precision``: the tool takes ``--conv-precision {fp32,bf16}``
-    (``args.conv_precision``; the eager side stays fp32).  Every case runs in a child process (``tool --child``) under
+    and ``--act-storage {fp32,bf16}`` (``args.conv_precision``, ``args.act_storage``; the eager side stays fp32).  Every case runs in a child process (``tool --child``) under
     ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is started on the GPU after
     it."""
     ap = argparse.ArgumentParser()
@@ -122,6 +122,8 @@ def main(tool, cases, run_case, report, heads=False, conv_precision=False):
     if conv_precision:
         ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "bf16"],
                         help="the HIP side's convolutions: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
+        ap.add_argument("--act-storage", default="fp32", choices=["fp32", "bf16"],
+                        help="bf16 (with --conv-precision bf16): the HIP side keeps the activations only convolutions read as bf16")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -134,7 +136,7 @@ def main(tool, cases, run_case, report, heads=False, conv_precision=False):
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision") if hasattr(a, k)
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision", "act_storage") if hasattr(a, k)
                  for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:
