@@ -825,6 +825,24 @@ int ld_dn_la_backward_reduce(const float* qkv, const float* dout, const float* c
  * dk[d] = ks[d] (sum_e dctx[d][e] v[e] - rk[d]), dv[e] = sum_d dctx[d][e] ks[d]. */
 int ld_dn_la_backward_apply(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
                             const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The same four passes on the bf16 matrix cores (csrc/linattn16.hip; LinearAttention.attn_precision = "bf16"): the same
+ * arguments, fp32 tensors, layouts, `work`, parts and refusals.  Both operands of every 32 x 32 product are rounded to bf16
+ * (round-to-nearest-even, NaN kept, as ld_dn_conv16 rounds) and multiplied by v_mfma_f32_32x32x16_bf16: exact products, an
+ * fp32 accumulator.  Nothing else is rounded; every sum keeps one order, no atomics, nothing allocates.
+ * context16: P = exp(k - m_part) is computed in fp32 and then rounded, v is rounded; m and Z are ld_dn_la_context's (Z sums
+ * the unrounded P: fp32 inside a run, fp64 across runs); the products leave the fp32 accumulator into fp64 every 16 tiles
+ * of 64 pixels, where a wave's accumulator has summed 256 pixels; the fp64 parts and the merge launch are unchanged. */
+int ld_dn_la_context16(const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W, int heads, int ld3,
+                       void* stream);
+/* out16: p = softmax_d(q) in fp32, then rounded; ctx rounded; the product times 32^-0.5 in fp32. */
+int ld_dn_la_out16(const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* backward_reduce16: p and dout rounded; the merge (32^-0.5, rk from the fp32 dctx and ctx in fp64) is unchanged. */
+int ld_dn_la_backward_reduce16(const float* qkv, const float* dout, const float* ctx, double* work, float* dctx, float* rk, int B,
+                               int H, int W, int heads, int ld3, int ldo, void* stream);
+/* backward_apply16: s = ctx dout, tk = dctx v and dv = dctx^T ks with all six operands rounded; ks, p, the dot product, rk
+ * and the three output formulas in fp32 with the unrounded p and ks, as ld_dn_la_backward_apply writes them. */
+int ld_dn_la_backward_apply16(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
+                              const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
 
 /* ---- training the denoiser, third slice: csrc/attention_grad.hip ------------------------------------------------------------
  * The core of a trainable full Attention (ddpm.py:253-282, attend.py's non-flash path): softmax(q k^T 32^-0.5) v per

@@ -23,7 +23,7 @@ This file holds the module's two launch sequences and its constructor; the rest 
 from torch import nn
 
 from . import _cabi as cabi
-from .linattn_grad import AttentionPacked, RMSNormRun, attention_init
+from .linattn_grad import AttentionPacked, AttnPrecision, RMSNormRun, attention_init
 from .trainable import TrainableModule
 
 
@@ -62,12 +62,15 @@ class _Run(RMSNormRun):
         return dxp[..., :m.dim].permute(0, 3, 1, 2), (), g
 
 
-class Attention(TrainableModule):
+class Attention(AttnPrecision, TrainableModule):
     """``Attention(dim, heads=4, dim_head=32)`` of ddpm.py:253-282, forward and backward in HIP (fp32).
 
     ``forward(x)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is read in place);
     returns ``to_out(...)`` [B, dim, H, W], a ``channels_last``-strided view of the kernels' NHWC output, without the
-    residual.  ``dim`` is a positive multiple of 32, ``heads >= 1``, ``dim_head`` is 32; any H, W >= 1."""
+    residual.  ``dim`` is a positive multiple of 32, ``heads >= 1``, ``dim_head`` is 32; any H, W >= 1.
+
+    ``attn_precision`` is ``"fp32"``, the only value so far (``ATTN_PRECISIONS``): the full-softmax core has no bf16 kernels
+    yet, and ``"bf16"`` is refused with ``ValueError``."""
 
     Run = _Run
 

@@ -8,6 +8,8 @@ apply passes of its backward) and the convolution kernels the library already ha
 ``to_qkv``, ``to_out.0`` and the two data gradients on the transposed weights, ``ld_seg_wgrad`` for the two weight gradients
 and ``ld_dn_colsum`` for ``to_out.0.bias``.  fp32, no host synchronisation in either direction, no eager-PyTorch arithmetic
 on an activation, and bit-reproducible results (every sum is added in a fixed order; no floating-point atomics).
+``LinearAttention.attn_precision = "bf16"`` puts the four passes of the core on the bf16 matrix cores (``csrc/linattn16.hip``:
+operands rounded, fp32 accumulation, the same tensors and the same order of every sum); the default runs the fp32 launches.
 
 The layout is ``resblock.py``'s: activations NHWC with a pixel stride of the next multiple of 64 floats, zero in the
 padding; ``to_qkv``'s output is [B, H, W, pad64(3 hidden)] with q at channel 0, k at ``hidden``, v at ``2 hidden`` and a
@@ -23,7 +25,7 @@ import torch
 from torch import nn
 
 from . import _cabi as cabi
-from .trainable import Run, TrainableModule, ones_zeros, pack_conv, pack_vec, pad64, stream
+from .trainable import Run, TrainableModule, check_attn_precision, ones_zeros, pack_conv, pack_vec, pad64, stream
 
 DIM_HEAD = 32
 
@@ -92,26 +94,30 @@ class _Run(RMSNormRun):
     def la_work(self):
         return self.work(self.lib.ld_dn_la_work_bytes(self.B, self.mod.heads, self.H, self.W))
 
+    def la(self, name):
+        """The core's entry point ``ld_dn_la_<name>`` at the module's ``attn_precision`` (read at every launch)."""
+        return getattr(self.lib, f"ld_dn_la_{name}16" if self.mod.attn_precision == "bf16" else f"ld_dn_la_{name}")
+
     # ------------------------------------------------------------------------------------------------ the two halves
     def forward(self, x, keep=True):
-        m, p, lib = self.mod, self.p, self.lib
+        m, p = self.mod, self.p
         B, H, W = self.B, self.H, self.W
         g1, g2 = m.norm.g.detach(), m.to_out[1].g.detach()
         xp = self.nhwc(x, m.dim, m.cp)
         xn, r1 = self.rms_forward(xp, g1, m.dim, m.cp, keep)
         qkv = self.conv(xn, p.wqf, p.zeros, m.cp, m.ld3, 1)
         ctx, kstat = self.empty(B, m.heads, 32, 32), self.empty(B, m.heads, 32, 2)
-        cabi.check(lib.ld_dn_la_context(qkv.data_ptr(), self.la_work().data_ptr(), ctx.data_ptr(), kstat.data_ptr(), B, H, W,
-                                        m.heads, m.ld3, self.st), "dn_la_context")
+        cabi.check(self.la("context")(qkv.data_ptr(), self.la_work().data_ptr(), ctx.data_ptr(), kstat.data_ptr(), B, H, W,
+                                      m.heads, m.ld3, self.st), "dn_la_context")
         att = self.empty(B, H, W, m.hp)
-        cabi.check(lib.ld_dn_la_out(qkv.data_ptr(), ctx.data_ptr(), att.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
+        cabi.check(self.la("out")(qkv.data_ptr(), ctx.data_ptr(), att.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
                    "dn_la_out")
         y = self.conv(att, p.wof, p.bo, m.hp, m.cp, 1)
         out, r2 = self.rms_forward(y, g2, m.dim, m.cp, keep)
         return out, (xp, r1, xn, qkv, ctx, kstat, att, y, r2)
 
     def backward(self, dout, saved):
-        m, p, lib = self.mod, self.p, self.lib
+        m, p = self.mod, self.p
         B, H, W = self.B, self.H, self.W
         xp, r1, xn, qkv, ctx, kstat, att, y, r2 = saved
         g1, g2 = m.norm.g.detach(), m.to_out[1].g.detach()
@@ -123,12 +129,12 @@ class _Run(RMSNormRun):
         g["to_out.0.bias"] = self.bias_grad(dy, m.dim, m.cp)
         datt = self.conv(dy, p.wod, p.zeros, m.cp, m.hp, 1)
         dctx, rk = self.empty(B, m.heads, 32, 32), self.empty(B, m.heads, 32)
-        cabi.check(lib.ld_dn_la_backward_reduce(qkv.data_ptr(), datt.data_ptr(), ctx.data_ptr(), self.la_work().data_ptr(),
-                                                dctx.data_ptr(), rk.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
+        cabi.check(self.la("backward_reduce")(qkv.data_ptr(), datt.data_ptr(), ctx.data_ptr(), self.la_work().data_ptr(),
+                                              dctx.data_ptr(), rk.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
                    "dn_la_backward_reduce")
         dqkv = self.empty(B, H, W, m.ld3)
-        cabi.check(lib.ld_dn_la_backward_apply(qkv.data_ptr(), datt.data_ptr(), ctx.data_ptr(), kstat.data_ptr(), dctx.data_ptr(),
-                                               rk.data_ptr(), dqkv.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
+        cabi.check(self.la("backward_apply")(qkv.data_ptr(), datt.data_ptr(), ctx.data_ptr(), kstat.data_ptr(), dctx.data_ptr(),
+                                             rk.data_ptr(), dqkv.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st),
                    "dn_la_backward_apply")
         g["to_qkv.weight"] = self.wgrad(dqkv, xn, 3 * m.hidden, m.ld3, m.dim, m.cp, 1)
         dxp = self.conv(dqkv, p.wqd, p.zeros, m.ld3, m.cp, 1)                # = d xn, then d x in place
@@ -136,14 +142,34 @@ class _Run(RMSNormRun):
         return dxp[..., :m.dim].permute(0, 3, 1, 2), (), g
 
 
-class LinearAttention(TrainableModule):
+class AttnPrecision:
+    """Mixin of the two attention modules: ``attn_precision``, the arithmetic of the attention core's products, validated on
+    assignment against the class's ``ATTN_PRECISIONS`` (a refused value leaves the old one in place)."""
+
+    attn_precision = "fp32"
+    ATTN_PRECISIONS = ("fp32",)
+
+    def __setattr__(self, name, value):
+        if name == "attn_precision":
+            check_attn_precision(type(self).__name__, value, self.ATTN_PRECISIONS)
+        super().__setattr__(name, value)
+
+
+class LinearAttention(AttnPrecision, TrainableModule):
     """``LinearAttention(dim, heads=4, dim_head=32)`` of ddpm.py:214-251, forward and backward in HIP (fp32).
 
     ``forward(x)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is read in place);
     returns ``to_out(...)`` [B, dim, H, W], a ``channels_last``-strided view of the kernels' NHWC output, without the
-    residual.  ``dim`` is a positive multiple of 32, ``heads >= 1``, ``dim_head`` is 32; any H, W >= 1."""
+    residual.  ``dim`` is a positive multiple of 32, ``heads >= 1``, ``dim_head`` is 32; any H, W >= 1.
+
+    ``attn_precision = "bf16"`` (default ``"fp32"``) runs the four passes of the attention core -- context, output and the
+    backward's reduce and apply -- on the bf16 matrix cores (csrc/linattn16.hip): both operands of every 32 x 32 product of
+    a head rounded to bf16, fp32 accumulation, the softmaxes, (m, Z), the merges and everything in memory fp32, every sum in
+    a fixed order.  It may change between steps; it is no part of the ``state_dict`` or of the packed weights (the core
+    has none), and it is independent of ``conv_precision``."""
 
     Run = _Run
+    ATTN_PRECISIONS = ("fp32", "bf16")
 
     def __init__(self, dim, heads=4, dim_head=32):
         super().__init__()

@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import check_act_storage, check_conv_precision, pad64, stream
+from .trainable import check_act_storage, check_attn_precision, check_conv_precision, pad64, stream
 from .weights import UnetConfig
 
 
@@ -190,10 +190,11 @@ class TrainableUnet(nn.Module):
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
-                 act_storage="fp32"):
+                 act_storage="fp32", attn_precision="fp32"):
         super().__init__()
         check_conv_precision("TrainableUnet", conv_precision)
         check_act_storage("TrainableUnet", act_storage)
+        check_attn_precision("TrainableUnet", attn_precision)
         for flag, what in ((self_condition, "self_condition"), (learned_variance, "learned_variance"),
                            (learned_sinusoidal_cond, "learned_sinusoidal_cond"), (random_fourier_features, "random_fourier_features")):
             if flag:
@@ -255,6 +256,9 @@ class TrainableUnet(nn.Module):
         self._act_storage = "fp32"
         if act_storage != "fp32":
             self.act_storage = act_storage
+        self._attn_precision = "fp32"
+        if attn_precision != "fp32":
+            self.attn_precision = attn_precision
 
     @property
     def downsample_factor(self):
@@ -299,6 +303,20 @@ class TrainableUnet(nn.Module):
         for m in self.modules():
             if isinstance(m, ResnetBlock):
                 m.act_storage = value
+
+    @property
+    def attn_precision(self):
+        return self._attn_precision
+
+    @attn_precision.setter
+    def attn_precision(self, value):
+        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``LinearAttention`` runs the four passes of its attention core on the
+        bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention`` modules have no such kernels yet and
+        stay fp32; ``conv_precision`` and ``act_storage`` are not touched, and neither needs the other."""
+        self._attn_precision = check_attn_precision("TrainableUnet", value)
+        for m in self.modules():
+            if isinstance(m, LinearAttention):
+                m.attn_precision = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)
