@@ -862,6 +862,18 @@ int64_t ld_dn_fa_work_bytes(int B, int heads, int H, int W);
  * (one per 64 keys: dk and dv). */
 int ld_dn_fa_backward(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
                       int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The same passes on the bf16 matrix cores (csrc/attention16.hip; Attention.full_attn_precision = "bf16"): the same
+ * arguments, fp32 tensors, layouts, `work` (ld_dn_fa_work_bytes) and refusals.  Both operands of every product are rounded to
+ * bf16 (round-to-nearest-even, NaN kept, as ld_dn_conv16 rounds) and multiplied by v_mfma_f32_32x32x16_bf16: exact products,
+ * an fp32 accumulator.  forward16: S = q^ k^T, the logits S 32^-0.5, the online softmax (the running maximum, alpha, the
+ * normaliser of the UNROUNDED p) and out = O / l in fp32 with ld_dn_fa_forward's formulas; O = p^ v^, p rounded after it is
+ * computed.  Every sum keeps one order, no atomics, nothing allocates, nothing of size n x n is written. */
+int ld_dn_fa_forward16(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* backward16: p = exp(q^ . k^ 32^-0.5 - lse) and delta = rowsum(dout out) (unrounded) in fp32; dP = dout^ v^T; ds = p (dP -
+ * delta) in fp32, then rounded; dq = 32^-0.5 (ds^ k^), dk = 32^-0.5 (ds^T q^), dv = p^T dout^, the scale applied to the fp32
+ * sum.  The same two passes as ld_dn_fa_backward. */
+int ld_dn_fa_backward16(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
+                        int H, int W, int heads, int ld3, int ldo, void* stream);
 
 /* ---- training the denoiser, fourth slice: csrc/resample_grad.hip -------------------------------------------------------------
  * What the layers between the blocks need besides ld_pc_conv / ld_seg_wgrad / ld_dn_colsum: Downsample's rearrangement

@@ -8,7 +8,8 @@ its backward (``csrc/linattn_grad.hip``), ``ld_pc_conv`` with ``ksize = 1`` for 
 gradients on the transposed weights, ``ld_seg_wgrad`` for the two weight gradients, ``ld_dn_colsum`` for the bias, and the
 softmax attention itself in ``csrc/attention_grad.hip``: ``ld_dn_fa_forward`` (an online softmax over tiles of 64 keys that
 keeps one number per row, ``lse``) and ``ld_dn_fa_backward`` (a row pass for dq, a column pass for dk and dv, the
-probabilities recomputed from ``qkv`` and ``lse``).  fp32, no host synchronisation in either direction, no eager-PyTorch
+probabilities recomputed from ``qkv`` and ``lse``), or their bf16 matrix-core siblings ``ld_dn_fa_forward16`` /
+``ld_dn_fa_backward16`` of ``csrc/attention16.hip`` at ``full_attn_precision = "bf16"``.  fp32 storage, no host synchronisation in either direction, no eager-PyTorch
 arithmetic on an activation, bit-reproducible results (every sum is added in a fixed order; no floating-point atomics),
 and nothing of size [n, n] is kept or written in either direction.
 
@@ -24,11 +25,15 @@ from torch import nn
 
 from . import _cabi as cabi
 from .linattn_grad import AttentionPacked, AttnPrecision, RMSNormRun, attention_init
-from .trainable import TrainableModule
+from .trainable import FULL_ATTN_PRECISIONS, TrainableModule, check_full_attn_precision
 
 
 class _Run(RMSNormRun):
     """The launches of one forward / backward of the module on one device."""
+
+    def fa(self, name):
+        """The core's entry point ``ld_dn_fa_<name>`` at the module's ``full_attn_precision`` (read at every launch)."""
+        return getattr(self.lib, f"ld_dn_fa_{name}16" if self.mod.full_attn_precision == "bf16" else f"ld_dn_fa_{name}")
 
     def forward(self, x, keep=True):
         m, p, lib = self.mod, self.p, self.lib
@@ -38,7 +43,7 @@ class _Run(RMSNormRun):
         qkv = self.conv(xn, p.wqf, p.zeros, m.cp, m.ld3, 1)
         att = self.empty(B, H, W, m.hp)
         lse = self.empty(B, m.heads, H * W) if keep else None
-        cabi.check(lib.ld_dn_fa_forward(qkv.data_ptr(), att.data_ptr(), cabi.ptr(lse), B, H, W, m.heads, m.ld3, m.hp, self.st),
+        cabi.check(self.fa("forward")(qkv.data_ptr(), att.data_ptr(), cabi.ptr(lse), B, H, W, m.heads, m.ld3, m.hp, self.st),
                    "dn_fa_forward")
         y = self.conv(att, p.wof, p.bo, m.hp, m.cp, 1)
         return y, (xp, r1, xn, qkv, att, lse)
@@ -54,15 +59,28 @@ class _Run(RMSNormRun):
         datt = self.conv(dy, p.wod, p.zeros, m.cp, m.hp, 1)
         dqkv = self.empty(B, H, W, m.ld3)
         work = self.work(lib.ld_dn_fa_work_bytes(B, m.heads, H, W))
-        cabi.check(lib.ld_dn_fa_backward(qkv.data_ptr(), att.data_ptr(), datt.data_ptr(), lse.data_ptr(), work.data_ptr(),
-                                         dqkv.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st), "dn_fa_backward")
+        cabi.check(self.fa("backward")(qkv.data_ptr(), att.data_ptr(), datt.data_ptr(), lse.data_ptr(), work.data_ptr(),
+                                       dqkv.data_ptr(), B, H, W, m.heads, m.ld3, m.hp, self.st), "dn_fa_backward")
         g["to_qkv.weight"] = self.wgrad(dqkv, xn, 3 * m.hidden, m.ld3, m.dim, m.cp, 1)
         dxp = self.conv(dqkv, p.wqd, p.zeros, m.ld3, m.cp, 1)                # = d xn, then d x in place
         g["norm.g"] = self.rms_backward(dxp, xp, m.norm.g.detach(), r1, m.dim, m.cp, dxp)
         return dxp[..., :m.dim].permute(0, 3, 1, 2), (), g
 
 
-class Attention(AttnPrecision, TrainableModule):
+class FullAttnPrecision:
+    """Mixin of ``Attention``: ``full_attn_precision``, the arithmetic of the full-softmax core's products, validated on
+    assignment against the class's ``FULL_ATTN_PRECISIONS`` (a refused value leaves the old one in place)."""
+
+    full_attn_precision = "fp32"
+    FULL_ATTN_PRECISIONS = FULL_ATTN_PRECISIONS
+
+    def __setattr__(self, name, value):
+        if name == "full_attn_precision":
+            check_full_attn_precision(type(self).__name__, value, self.FULL_ATTN_PRECISIONS)
+        super().__setattr__(name, value)
+
+
+class Attention(FullAttnPrecision, AttnPrecision, TrainableModule):
     """``Attention(dim, heads=4, dim_head=32)`` of ddpm.py:253-282, forward and backward in HIP (fp32).
 
     ``forward(x)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is read in place);
@@ -70,7 +88,15 @@ class Attention(AttnPrecision, TrainableModule):
     residual.  ``dim`` is a positive multiple of 32, ``heads >= 1``, ``dim_head`` is 32; any H, W >= 1.
 
     ``attn_precision`` is ``"fp32"``, the only value so far (``ATTN_PRECISIONS``): the full-softmax core has no bf16 kernels
-    yet, and ``"bf16"`` is refused with ``ValueError``."""
+    yet under that name, and ``"bf16"`` is refused with ``ValueError``.
+
+    ``full_attn_precision = "bf16"`` (default ``"fp32"``, ``FULL_ATTN_PRECISIONS``) runs the three passes of the core -- the
+    forward, the backward's row pass and its column pass -- on the bf16 matrix cores (csrc/attention16.hip,
+    ``ld_dn_fa_forward16`` / ``ld_dn_fa_backward16``): both operands of every product (q, k, v, dO, and the computed p and
+    ds) rounded to bf16, fp32 accumulation; the logits' scale, the online softmax, its normaliser (the unrounded p), lse,
+    delta and everything in memory stay fp32, every sum keeps one order.  It is read at every launch and may change between
+    calls; it is no part of the ``state_dict``, of the packed weights' cache key or of a checkpoint, and it is independent
+    of ``attn_precision`` (``LinearAttention``'s switch) and of ``conv_precision``."""
 
     Run = _Run
 

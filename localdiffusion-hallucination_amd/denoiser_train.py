@@ -42,7 +42,8 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import check_act_storage, check_act_storage_precision, check_attn_precision, check_conv_precision, stream
+from .trainable import (check_act_storage, check_act_storage_precision, check_attn_precision, check_conv_precision,
+                        check_full_attn_precision, stream)
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -157,13 +158,19 @@ class DenoiserTrainer:
     products rounded to bf16, fp32 accumulation, every sum in a fixed order, so the step stays reproducible bit for bit and
     data-parallel replicas stay identical.  Checkpoints do not record it.
 
+    ``full_attn_precision="bf16"`` (default ``"fp32"``; independent of the other three) does the same for the online model's
+    full-softmax ``Attention`` modules (``TrainableUnet.full_attn_precision``): q, k, v, dO and the computed p and ds rounded
+    to bf16 for the products, the softmax and its statistics fp32.  The same guarantees: no loss scaling, a step reproducible
+    bit for bit, identical replicas, nothing in a checkpoint, the EMA / inference ``Unet`` not involved.
+
     ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
     ``ema_initted`` are ``ema_pytorch``'s two buffers."""
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
-                 conv_precision="fp32", act_storage="fp32", attn_precision="fp32"):
+                 conv_precision="fp32", act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
         check_conv_precision("DenoiserTrainer", conv_precision)
+        check_full_attn_precision("DenoiserTrainer", full_attn_precision)
         check_attn_precision("DenoiserTrainer", attn_precision)
         check_act_storage("DenoiserTrainer", act_storage)
         check_act_storage_precision("DenoiserTrainer", act_storage, conv_precision)
@@ -189,8 +196,9 @@ class DenoiserTrainer:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
         # (raises ValueError for what it cannot train)
         online = TrainableUnet(**online_kwargs(model), conv_precision=conv_precision, act_storage=act_storage,
-                               attn_precision=attn_precision)
+                               attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         self.conv_precision, self.act_storage, self.attn_precision = conv_precision, act_storage, attn_precision
+        self.full_attn_precision = full_attn_precision
         dev = diffusion.device
         if dev.type != "cuda":
             raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")

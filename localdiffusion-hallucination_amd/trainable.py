@@ -81,6 +81,15 @@ def check_attn_precision(name, value, allowed=ATTN_PRECISIONS):
     return value
 
 
+FULL_ATTN_PRECISIONS = ("fp32", "bf16")
+
+
+def check_full_attn_precision(name, value, allowed=FULL_ATTN_PRECISIONS):
+    if not isinstance(value, str) or value not in allowed:
+        raise ValueError(f"{name}: full_attn_precision {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
+    return value
+
+
 def check_act_storage(name, value, allowed=("fp32", "bf16")):
     if not isinstance(value, str) or value not in allowed:
         raise ValueError(f"{name}: act_storage {value!r} is not one of {', '.join(repr(v) for v in allowed)}")

@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import check_act_storage, check_attn_precision, check_conv_precision, pad64, stream
+from .trainable import check_act_storage, check_attn_precision, check_conv_precision, check_full_attn_precision, pad64, stream
 from .weights import UnetConfig
 
 
@@ -190,8 +190,9 @@ class TrainableUnet(nn.Module):
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
-                 act_storage="fp32", attn_precision="fp32"):
+                 act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
         super().__init__()
+        check_full_attn_precision("TrainableUnet", full_attn_precision)
         check_conv_precision("TrainableUnet", conv_precision)
         check_act_storage("TrainableUnet", act_storage)
         check_attn_precision("TrainableUnet", attn_precision)
@@ -259,6 +260,9 @@ class TrainableUnet(nn.Module):
         self._attn_precision = "fp32"
         if attn_precision != "fp32":
             self.attn_precision = attn_precision
+        self._full_attn_precision = "fp32"
+        if full_attn_precision != "fp32":
+            self.full_attn_precision = full_attn_precision
 
     @property
     def downsample_factor(self):
@@ -311,12 +315,26 @@ class TrainableUnet(nn.Module):
     @attn_precision.setter
     def attn_precision(self, value):
         """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``LinearAttention`` runs the four passes of its attention core on the
-        bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention`` modules have no such kernels yet and
-        stay fp32; ``conv_precision`` and ``act_storage`` are not touched, and neither needs the other."""
+        bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention`` modules have a switch of their own
+        (``full_attn_precision``) and are not touched; ``conv_precision`` and ``act_storage`` are not touched, and neither needs the other."""
         self._attn_precision = check_attn_precision("TrainableUnet", value)
         for m in self.modules():
             if isinstance(m, LinearAttention):
                 m.attn_precision = value
+
+    @property
+    def full_attn_precision(self):
+        return self._full_attn_precision
+
+    @full_attn_precision.setter
+    def full_attn_precision(self, value):
+        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every full-softmax ``Attention`` runs the three passes of its core on the
+        bf16 matrix cores (``Attention.full_attn_precision``).  Nothing else is touched: the ``LinearAttention`` modules and
+        their ``attn_precision``, ``conv_precision`` and ``act_storage`` stay as they are, and none needs another."""
+        self._full_attn_precision = check_full_attn_precision("TrainableUnet", value)
+        for m in self.modules():
+            if isinstance(m, Attention):
+                m.full_attn_precision = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

@@ -165,7 +165,7 @@ def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
     net = ldh.TrainableUnet(dim=32, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision,
-                            **KWARGS[data]).cuda()
+                            full_attn_precision=a.full_attn_precision, **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -190,7 +190,7 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision, peak_mb=peak / 2 ** 20, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision, full_attn_precision=a.full_attn_precision, peak_mb=peak / 2 ** 20, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
                 kernels_ms=sum(v[0] for v in split.values()), launches=sum(v[1] for v in split.values()), split=fam)
 
@@ -200,10 +200,10 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:9.3f} ms, channels_last {r['eager_nhwc_ms']:9.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f}; outputs differ by {r['out_diff_to_eager']:.1e})")
-    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / attn {r['attn_precision']}: HIP {r['hip_ms']:9.3f} ms, "
+    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / attn {r['attn_precision']} / full attn {r['full_attn_precision']}: HIP {r['hip_ms']:9.3f} ms, "
           f"peak {r['peak_mb']:8.1f} MiB, {r['launches']} launches, kernels {r['kernels_ms']:9.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, CASES, run_case, report, conv_precision=True, attn_precision=True))
+    sys.exit(grad_bench.main(__file__, CASES, run_case, report, conv_precision=True, attn_precision=True, full_attn_precision=True))

@@ -109,11 +109,12 @@ def print_split(split, kernels_ms):
         print(f"      {k:28s} {v['ms']:9.3f} ms  {100 * v['ms'] / kernels_ms:5.1f} %  ({v['launches']} launches)")
 
 
-def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_precision=False):
+def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_precision=False, full_attn_precision=False):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
     returns the case's JSON row and ``report(row)`` prints it.  ``conv_precision``: the tool takes ``--conv-precision {fp32,bf16}``
     and ``--act-storage {fp32,bf16}`` (``args.conv_precision``, ``args.act_storage``; the eager side stays fp32); ``attn_precision``: it takes ``--attn-precision {fp32,bf16}``
-    (``args.attn_precision``).  Every case runs in a child process (``tool --child``) under
+    (``args.attn_precision``); ``full_attn_precision``: it takes ``--full-attn-precision {fp32,bf16}``
+    (``args.full_attn_precision``).  Every case runs in a child process (``tool --child``) under
     ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is started on the GPU after
     it."""
     ap = argparse.ArgumentParser()
@@ -128,6 +129,9 @@ def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_
     if attn_precision:
         ap.add_argument("--attn-precision", default="fp32", choices=["fp32", "bf16"],
                         help="the HIP side's LinearAttention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
+    if full_attn_precision:
+        ap.add_argument("--full-attn-precision", default="fp32", choices=["fp32", "bf16"],
+                        help="the HIP side's full-softmax Attention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -140,7 +144,8 @@ def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision", "act_storage", "attn_precision") if hasattr(a, k)
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision", "act_storage", "attn_precision", "full_attn_precision")
+                 if hasattr(a, k)
                  for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:

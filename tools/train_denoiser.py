@@ -54,6 +54,8 @@ def parse(argv=None):
                     help="bf16 (with --conv-precision bf16): activations that only convolutions read are kept as bf16; same results")
     ap.add_argument("--attn-precision", default="fp32", choices=["fp32", "bf16"],
                     help="bf16: the LinearAttention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)")
+    ap.add_argument("--full-attn-precision", default="fp32", choices=["fp32", "bf16"],
+                    help="bf16: the full-softmax Attention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)")
     ap.add_argument("--save-every", type=int, default=100)
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
@@ -97,7 +99,7 @@ def setup(a, **trainer_kw):
         print("init:", checkpoint.load_reference_checkpoint(a.init, gd))
     trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr,
                                   conv_precision=a.conv_precision, act_storage=a.act_storage,
-                                  attn_precision=a.attn_precision, **trainer_kw)
+                                  attn_precision=a.attn_precision, full_attn_precision=a.full_attn_precision, **trainer_kw)
     return trainer, batches(tr_idx), batches(va_idx)
 
 
