@@ -230,15 +230,9 @@ _SIGS = {
     "ld_dn_la_out": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_la_backward_reduce": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_la_backward_apply": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_la_context16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_la_out16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_la_backward_reduce16": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_la_backward_apply16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_fa_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_fa_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ld_dn_fa_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_fa_forward16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "ld_dn_fa_backward16": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_space_to_depth": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_depth_to_space": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_upsample2x": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
@@ -278,6 +272,9 @@ _SIGS = {
     "ld_allgather": (C.c_int, [vp, vp, C.c_size_t, vp, vp]),
     "ld_comm_destroy": (C.c_int, [vp]),
 }
+# the bf16 matrix-core sibling of an attention-core entry point takes its arguments
+_SIGS.update({name + "16": _SIGS[name] for name in ("ld_dn_la_context", "ld_dn_la_out", "ld_dn_la_backward_reduce",
+                                                    "ld_dn_la_backward_apply", "ld_dn_fa_forward", "ld_dn_fa_backward")})
 
 EXPORTS = tuple(_SIGS)
 _lib = None

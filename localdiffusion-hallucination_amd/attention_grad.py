@@ -24,8 +24,8 @@ This file holds the module's two launch sequences and its constructor; the rest 
 from torch import nn
 
 from . import _cabi as cabi
-from .linattn_grad import AttentionPacked, AttnPrecision, RMSNormRun, attention_init
-from .trainable import FULL_ATTN_PRECISIONS, TrainableModule, check_full_attn_precision
+from .linattn_grad import AttentionPacked, RMSNormRun, attention_init
+from .trainable import TrainableModule
 
 
 class _Run(RMSNormRun):
@@ -67,20 +67,7 @@ class _Run(RMSNormRun):
         return dxp[..., :m.dim].permute(0, 3, 1, 2), (), g
 
 
-class FullAttnPrecision:
-    """Mixin of ``Attention``: ``full_attn_precision``, the arithmetic of the full-softmax core's products, validated on
-    assignment against the class's ``FULL_ATTN_PRECISIONS`` (a refused value leaves the old one in place)."""
-
-    full_attn_precision = "fp32"
-    FULL_ATTN_PRECISIONS = FULL_ATTN_PRECISIONS
-
-    def __setattr__(self, name, value):
-        if name == "full_attn_precision":
-            check_full_attn_precision(type(self).__name__, value, self.FULL_ATTN_PRECISIONS)
-        super().__setattr__(name, value)
-
-
-class Attention(FullAttnPrecision, AttnPrecision, TrainableModule):
+class Attention(TrainableModule):
     """``Attention(dim, heads=4, dim_head=32)`` of ddpm.py:253-282, forward and backward in HIP (fp32).
 
     ``forward(x)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is read in place);
@@ -99,6 +86,10 @@ class Attention(FullAttnPrecision, AttnPrecision, TrainableModule):
     of ``attn_precision`` (``LinearAttention``'s switch) and of ``conv_precision``."""
 
     Run = _Run
+    attn_precision = "fp32"
+    ATTN_PRECISIONS = ("fp32",)
+    full_attn_precision = "fp32"
+    FULL_ATTN_PRECISIONS = ("fp32", "bf16")
 
     def __init__(self, dim, heads=4, dim_head=32):
         super().__init__()

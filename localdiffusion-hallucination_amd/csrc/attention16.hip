@@ -7,10 +7,7 @@
 // rules and `work` (delta [B, heads, n]) are the fp32 path's.  Nothing of size n x n is written, every sum has one fixed
 // order, no floating-point atomics, nothing allocates.
 //
-// Lane map of the MFMA (linattn16.hip), lane l with r = l & 31, hh = l >> 5: the lane holds A[r][8 hh + j] and
-// B[8 hh + j][r], j = 0..7, and D[(reg & 3) + 8 (reg >> 2) + 4 hh][r] in its 16 accumulator registers.
-//
-// Every pass issues its products transposed, the tile's rows on M and the wave's own 32 rows on N, so that a lane owns one
+// The MFMA, its lane map (lane l: r = l & 31, hh = l >> 5) and the swizzle of the cols image are mfma16.hip.h's.  Every pass issues its products transposed, the tile's rows on M and the wave's own 32 rows on N, so that a lane owns one
 // row of its side (a query in the forward and the row pass, a key in the column pass) and that row's q / dO (k / v) is a
 // B operand held in registers for the whole launch:
 //   S^T = K Q^T (keys on M):   the row maximum and the row sum are 16 in-lane values and those of lane l ^ 32;
@@ -20,7 +17,7 @@
 // The tile side comes from LDS as bf16, rounded once on its way in, in two images:
 //   rows [64][32 channels], 80-byte rows: the A operand of a contraction over channels (K, V, Q, dO) is one ds_read_b128
 //        per K-step, and 16 consecutive rows fall on 64 different banks (20 r mod 64 dwords);
-//   cols [32 channels][64 rows], 128-byte rows with linattn16's XOR swizzle of the 16-byte groups, the rows of a tile
+//   cols [32 channels][64 rows], 128-byte rows with the XOR swizzle of the 16-byte groups (mfma16_off), the rows of a tile
 //        stored in the permuted order above: the A operand of a contraction over the tile's rows (V^T, K^T, Q^T, dO^T)
 //        is one ds_read_b128 per K-step as well.  A loader thread takes four channels of two neighbouring rows that are
 //        neighbours in the permuted order too, and stores each channel's pair as one dword.
@@ -29,36 +26,18 @@
 // fp32 tile in LDS from which the result leaves as 128 contiguous bytes per (row, head).  No store reads an accumulator.
 #include "common.hip.h"
 #include "dn_common.hip.h"
+#include "fa_common.hip.h"
+#include "mfma16.hip.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f16_f32x16;
-
-constexpr int F16_D = 32;              // channels per head
-constexpr int F16_BS = 256;            // threads per workgroup: four waves
-constexpr int F16_T = 64;              // rows per workgroup and rows per LDS tile
-constexpr float F16_SCALE = 0.17677669529663687f;      // 32^-0.5
-constexpr float F16_NEG = -1e30f;      // the running maximum before the first valid key (finite on purpose)
-constexpr long F16_MAX_N = 1L << 30;   // pixels at most
 constexpr int F16_RS = 80;             // bytes per row of a rows image
-constexpr int F16_ROWS = F16_T * F16_RS;               // bytes of a rows image
-constexpr int F16_COLS = F16_D * F16_T * 2;            // bytes of a cols image
+constexpr int F16_ROWS = FA_T * F16_RS;                // bytes of a rows image
+constexpr int F16_COLS = FA_D * FA_T * 2;              // bytes of a cols image
 constexpr int F16_TS = 36;             // floats per row of the fp32 exchange tile (linattn16's L16_TS)
 
-__device__ __forceinline__ float f16_exp(float a) { return __builtin_amdgcn_exp2f(1.4426950408889634f * a); }
-__device__ __forceinline__ f16_f32x16 f16_mfma(uint4 a, uint4 b, f16_f32x16 acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ f16_f32x16 f16_zero() {
-  f16_f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-  return z;
-}
 // tile row of accumulator register i (and of element i & 7 of K-step i >> 3 of the second product)
 __device__ __forceinline__ int f16_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
-// byte offset of the 16-byte group grp of channel c in a cols image (linattn16's l16_off)
-__device__ __forceinline__ int f16_off(int c, int grp) { return c * 128 + 16 * (grp ^ (((c >> 2) ^ ((c >> 1) & 1)) & 7)); }
 
 // A loader thread's share of a 64-row tile: channels 4 l .. 4 l + 3 (l = tid & 7) of the rows at positions 2 rr, 2 rr + 1
 // (rr = tid >> 3) of the permuted order, which are the neighbouring rows f16_ldrow, f16_ldrow + 1.
@@ -90,10 +69,10 @@ __device__ __forceinline__ void f16_put_rows(unsigned char* img, const F16Raw& v
 __device__ __forceinline__ void f16_put_cols(unsigned char* img, const F16Raw& v, int tid) {
   const int rr = tid >> 3, c = 4 * (tid & 7);
   const int at = 4 * (rr & 3);
-  *reinterpret_cast<unsigned*>(img + f16_off(c, rr >> 2) + at) = pack_bf16x2(v.x[0].x, v.x[1].x);
-  *reinterpret_cast<unsigned*>(img + f16_off(c + 1, rr >> 2) + at) = pack_bf16x2(v.x[0].y, v.x[1].y);
-  *reinterpret_cast<unsigned*>(img + f16_off(c + 2, rr >> 2) + at) = pack_bf16x2(v.x[0].z, v.x[1].z);
-  *reinterpret_cast<unsigned*>(img + f16_off(c + 3, rr >> 2) + at) = pack_bf16x2(v.x[0].w, v.x[1].w);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c, rr >> 2) + at) = pack_bf16x2(v.x[0].x, v.x[1].x);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 1, rr >> 2) + at) = pack_bf16x2(v.x[0].y, v.x[1].y);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 2, rr >> 2) + at) = pack_bf16x2(v.x[0].z, v.x[1].z);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 3, rr >> 2) + at) = pack_bf16x2(v.x[0].w, v.x[1].w);
 }
 // A operand of K-step s over channels: row `row` of a rows image, channels 16 s + 8 hh .. + 7
 __device__ __forceinline__ uint4 f16_a_rows(const unsigned char* img, int row, int hh, int s) {
@@ -101,7 +80,7 @@ __device__ __forceinline__ uint4 f16_a_rows(const unsigned char* img, int row, i
 }
 // A operand of K-step s over the rows of half `half` of the tile: channel r of a cols image
 __device__ __forceinline__ uint4 f16_a_cols(const unsigned char* img, int r, int hh, int half, int s) {
-  return *reinterpret_cast<const uint4*>(img + f16_off(r, 4 * half + 2 * s + hh));
+  return *reinterpret_cast<const uint4*>(img + mfma16_off(r, 4 * half + 2 * s + hh));
 }
 // The lane's B operands of a contraction over channels from its own row in memory: channels 16 s + 8 hh .. + 7; x keeps
 // the 16 unrounded values.
@@ -118,13 +97,6 @@ __device__ __forceinline__ void f16_b_row(const float* __restrict__ src, int hh,
 __device__ __forceinline__ uint4 f16_b_acc(const float (&p)[16], int s) {
   return make_uint4(pack_bf16x2(p[8 * s], p[8 * s + 1]), pack_bf16x2(p[8 * s + 2], p[8 * s + 3]),
                     pack_bf16x2(p[8 * s + 4], p[8 * s + 5]), pack_bf16x2(p[8 * s + 6], p[8 * s + 7]));
-}
-// dst [row][c0 .. c0 + 32) = 0 for the rows of this workgroup's tile (the padding columns of an output)
-__device__ __forceinline__ void f16_zero_cols(float* __restrict__ dst, long r0, long n, int ld, int c0, int tid) {
-  const int c = c0 + 4 * (tid & 7);
-  if (c >= ld) return;
-  for (int r = tid >> 3; r < F16_T; r += F16_BS / 8)
-    if (r0 + r < n) st4(dst + (size_t)(r0 + r) * ld + c, 0.f, 0.f, 0.f, 0.f);
 }
 // The exchange tile [64 rows][F16_TS] fp32: a lane's 16 channels 8 g + 4 hh + i of row `row`, accumulator order
 __device__ __forceinline__ void f16_give(float* tile, int row, int hh, const float (&x)[16]) {
@@ -150,65 +122,65 @@ __device__ __forceinline__ void f16_flush(const float* tile, float* __restrict__
 }
 
 // ================================================================================================ forward
-__global__ __launch_bounds__(F16_BS) void fa16_forward_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+__global__ __launch_bounds__(FA_BS) void fa16_forward_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                               float* __restrict__ lse, long n, int heads, int ld3, int ldo) {
   __shared__ __attribute__((aligned(16))) unsigned char s_k[F16_ROWS];      // K  [key][channel]
   __shared__ __attribute__((aligned(16))) unsigned char s_vt[F16_COLS];     // V^T [channel][key]
-  __shared__ __attribute__((aligned(16))) float s_o[F16_T * F16_TS];
-  __shared__ float s_m[F16_T], s_l[F16_T];
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * F16_D;
+  __shared__ __attribute__((aligned(16))) float s_o[FA_T * F16_TS];
+  __shared__ float s_m[FA_T], s_l[FA_T];
+  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * FA_D;
   const int r = lane & 31, hh = lane >> 5, qh = wv & 1, kh = wv >> 1, row = 32 * qh + r;
-  const long q0 = (long)blockIdx.x * F16_T;
+  const long q0 = (long)blockIdx.x * FA_T;
   float* orow = out + (size_t)b * n * ldo;
   if (h >= heads) {
-    f16_zero_cols(orow, q0, n, ldo, h * F16_D, tid);
+    fa_zero_cols(orow, q0, n, ldo, h * FA_D, tid);
     return;
   }
-  const float* base = qkv + (size_t)b * n * ld3 + h * F16_D;
+  const float* base = qkv + (size_t)b * n * ld3 + h * FA_D;
   const long qi = q0 + row < n ? q0 + row : n - 1;
   uint4 qb[2];
   {
     float x[16];
     f16_b_row(base + (size_t)qi * ld3, hh, qb, x);
   }
-  f16_f32x16 o = f16_zero();
-  float m = F16_NEG, l = 0.f;
+  f32x16 o = mfma16_zero();
+  float m = FA_NEG, l = 0.f;
   F16Raw rk = f16_fetch(base + hidden, 0, n, ld3, tid), rv = f16_fetch(base + 2 * hidden, 0, n, ld3, tid);
-  for (long j0 = 0; j0 < n; j0 += F16_T) {                  // (uniform: the barriers, the shuffles and the MFMAs)
+  for (long j0 = 0; j0 < n; j0 += FA_T) {                   // (uniform: the barriers, the shuffles and the MFMAs)
     __syncthreads();
     f16_put_rows(s_k, rk, tid);
     f16_put_cols(s_vt, rv, tid);
     __syncthreads();
-    if (j0 + F16_T < n) {                                   // the next tile's requests fly over the products
-      rk = f16_fetch(base + hidden, j0 + F16_T, n, ld3, tid);
-      rv = f16_fetch(base + 2 * hidden, j0 + F16_T, n, ld3, tid);
+    if (j0 + FA_T < n) {                                    // the next tile's requests fly over the products
+      rk = f16_fetch(base + hidden, j0 + FA_T, n, ld3, tid);
+      rv = f16_fetch(base + 2 * hidden, j0 + FA_T, n, ld3, tid);
     }
-    f16_f32x16 sa = f16_mfma(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], f16_zero());
-    sa = f16_mfma(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
+    f32x16 sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
+    sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
     const long key0 = j0 + 32 * kh;
-    float s[16], tmax = F16_NEG;
+    float s[16], tmax = FA_NEG;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const float a = sa[i] * F16_SCALE;
-      s[i] = key0 + f16_row(i, hh) < n ? a : F16_NEG;
+      const float a = sa[i] * FA_SCALE;
+      s[i] = key0 + f16_row(i, hh) < n ? a : FA_NEG;
       tmax = fmaxf(tmax, s[i]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float mn = fmaxf(m, tmax);
-    const float alpha = f16_exp(m - mn);                    // (both -1e30 while the wave has seen no valid key: 1, on l = o = 0)
+    const float alpha = fa_exp(m - mn);                     // (both -1e30 while the wave has seen no valid key: 1, on l = o = 0)
     m = mn;
     float p[16], ps = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      p[i] = key0 + f16_row(i, hh) < n ? f16_exp(s[i] - m) : 0.f;
+      p[i] = key0 + f16_row(i, hh) < n ? fa_exp(s[i] - m) : 0.f;
       ps += p[i];
     }
     ps += __shfl_xor(ps, 32);                               // (the same bits in both lanes of a query)
     l = l * alpha + ps;
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[i] *= alpha;
-    o = f16_mfma(f16_a_cols(s_vt, r, hh, kh, 0), f16_b_acc(p, 0), o);
-    o = f16_mfma(f16_a_cols(s_vt, r, hh, kh, 1), f16_b_acc(p, 1), o);
+    o = mfma16(f16_a_cols(s_vt, r, hh, kh, 0), f16_b_acc(p, 0), o);
+    o = mfma16(f16_a_cols(s_vt, r, hh, kh, 1), f16_b_acc(p, 1), o);
   }
   // the two waves of a query meet, rescaled to the common maximum, in wave order
   float ov[16];
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(F16_BS) void fa16_forward_kernel(const float* __res
   if (kh == 0) {
     const float m1 = s_m[row], l1 = s_l[row];
     const float M = fmaxf(m, m1);
-    const float f0 = f16_exp(m - M), f1 = f16_exp(m1 - M);  // (a wave without a valid key: exp2(-huge) = 0, on l = o = 0)
+    const float f0 = fa_exp(m - M), f1 = fa_exp(m1 - M);    // (a wave without a valid key: exp2(-huge) = 0, on l = o = 0)
     const float L = l * f0 + l1 * f1;
     const float inv = 1.0f / L;                             // (L >= 1: the wave that holds the maximum has f = 1 and l >= 1)
     float o1[16];
@@ -236,27 +208,27 @@ __global__ __launch_bounds__(F16_BS) void fa16_forward_kernel(const float* __res
     if (lse && hh == 0 && q0 + row < n) lse[((size_t)b * heads + h) * n + q0 + row] = M + logf(L);
   }
   __syncthreads();
-  f16_flush(s_o, orow + h * F16_D, q0, n, ldo, tid);
+  f16_flush(s_o, orow + h * FA_D, q0, n, ldo, tid);
 }
 
 // ================================================================================================ backward: rows (dq)
-__global__ __launch_bounds__(F16_BS) void fa16_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
+__global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
                                                          const float* __restrict__ dout, const float* __restrict__ lse,
                                                          float* __restrict__ delta, float* __restrict__ dqkv, long n, int heads,
                                                          int ld3, int ldo) {
   __shared__ __attribute__((aligned(16))) unsigned char s_k[F16_ROWS];      // K  [key][channel]
   __shared__ __attribute__((aligned(16))) unsigned char s_v[F16_ROWS];      // V  [key][channel]
   __shared__ __attribute__((aligned(16))) unsigned char s_kt[F16_COLS];     // K^T [channel][key]
-  __shared__ __attribute__((aligned(16))) float s_o[F16_T * F16_TS];
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * F16_D;
+  __shared__ __attribute__((aligned(16))) float s_o[FA_T * F16_TS];
+  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * FA_D;
   const int r = lane & 31, hh = lane >> 5, qh = wv & 1, kh = wv >> 1, row = 32 * qh + r;
-  const long q0 = (long)blockIdx.x * F16_T;
+  const long q0 = (long)blockIdx.x * FA_T;
   float* drow = dqkv + (size_t)b * n * ld3;
   if (h >= heads) {
-    f16_zero_cols(drow, q0, n, ld3, 3 * hidden + (h - heads) * F16_D, tid);
+    fa_zero_cols(drow, q0, n, ld3, 3 * hidden + (h - heads) * FA_D, tid);
     return;
   }
-  const float* base = qkv + (size_t)b * n * ld3 + h * F16_D;
+  const float* base = qkv + (size_t)b * n * ld3 + h * FA_D;
   const long qi = q0 + row < n ? q0 + row : n - 1;
   const size_t stat = ((size_t)b * heads + h) * n + qi;
   uint4 qb[2], gb[2];
@@ -265,8 +237,8 @@ __global__ __launch_bounds__(F16_BS) void fa16_dq_kernel(const float* __restrict
     float x[16], g[16], oo[16];
     uint4 unused[2];
     f16_b_row(base + (size_t)qi * ld3, hh, qb, x);
-    f16_b_row(dout + ((size_t)b * n + qi) * ldo + h * F16_D, hh, gb, g);
-    f16_b_row(out + ((size_t)b * n + qi) * ldo + h * F16_D, hh, unused, oo);
+    f16_b_row(dout + ((size_t)b * n + qi) * ldo + h * FA_D, hh, gb, g);
+    f16_b_row(out + ((size_t)b * n + qi) * ldo + h * FA_D, hh, unused, oo);
     dl = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) dl = fmaf(g[i], oo[i], dl);
@@ -274,31 +246,31 @@ __global__ __launch_bounds__(F16_BS) void fa16_dq_kernel(const float* __restrict
   }
   if (kh == 0 && hh == 0 && q0 + row < n) delta[stat] = dl;
   const float ls = lse[stat];
-  f16_f32x16 dq = f16_zero();
+  f32x16 dq = mfma16_zero();
   F16Raw rk = f16_fetch(base + hidden, 0, n, ld3, tid), rv = f16_fetch(base + 2 * hidden, 0, n, ld3, tid);
-  for (long j0 = 0; j0 < n; j0 += F16_T) {                  // (uniform: the barriers and the MFMAs)
+  for (long j0 = 0; j0 < n; j0 += FA_T) {                   // (uniform: the barriers and the MFMAs)
     __syncthreads();
     f16_put_rows(s_k, rk, tid);
     f16_put_cols(s_kt, rk, tid);
     f16_put_rows(s_v, rv, tid);
     __syncthreads();
-    if (j0 + F16_T < n) {
-      rk = f16_fetch(base + hidden, j0 + F16_T, n, ld3, tid);
-      rv = f16_fetch(base + 2 * hidden, j0 + F16_T, n, ld3, tid);
+    if (j0 + FA_T < n) {
+      rk = f16_fetch(base + hidden, j0 + FA_T, n, ld3, tid);
+      rv = f16_fetch(base + 2 * hidden, j0 + FA_T, n, ld3, tid);
     }
-    f16_f32x16 sa = f16_mfma(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], f16_zero());
-    sa = f16_mfma(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
-    f16_f32x16 dp = f16_mfma(f16_a_rows(s_v, 32 * kh + r, hh, 0), gb[0], f16_zero());
-    dp = f16_mfma(f16_a_rows(s_v, 32 * kh + r, hh, 1), gb[1], dp);
+    f32x16 sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
+    sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
+    f32x16 dp = mfma16(f16_a_rows(s_v, 32 * kh + r, hh, 0), gb[0], mfma16_zero());
+    dp = mfma16(f16_a_rows(s_v, 32 * kh + r, hh, 1), gb[1], dp);
     const long key0 = j0 + 32 * kh;
     float ds[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const float p = key0 + f16_row(i, hh) < n ? f16_exp(sa[i] * F16_SCALE - ls) : 0.f;
+      const float p = key0 + f16_row(i, hh) < n ? fa_exp(sa[i] * FA_SCALE - ls) : 0.f;
       ds[i] = p * (dp[i] - dl);
     }
-    dq = f16_mfma(f16_a_cols(s_kt, r, hh, kh, 0), f16_b_acc(ds, 0), dq);
-    dq = f16_mfma(f16_a_cols(s_kt, r, hh, kh, 1), f16_b_acc(ds, 1), dq);
+    dq = mfma16(f16_a_cols(s_kt, r, hh, kh, 0), f16_b_acc(ds, 0), dq);
+    dq = mfma16(f16_a_cols(s_kt, r, hh, kh, 1), f16_b_acc(ds, 1), dq);
   }
   float ov[16];
   if (kh == 1) {
@@ -311,28 +283,28 @@ __global__ __launch_bounds__(F16_BS) void fa16_dq_kernel(const float* __restrict
     float o1[16];
     f16_take(s_o, row, hh, o1);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) ov[i] = (dq[i] + o1[i]) * F16_SCALE;
+    for (int i = 0; i < 16; ++i) ov[i] = (dq[i] + o1[i]) * FA_SCALE;
     f16_give(s_o, row, hh, ov);
   }
   __syncthreads();
-  f16_flush(s_o, drow + h * F16_D, q0, n, ld3, tid);
+  f16_flush(s_o, drow + h * FA_D, q0, n, ld3, tid);
 }
 
 // ================================================================================================ backward: columns (dk, dv)
-__global__ __launch_bounds__(F16_BS) void fa16_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+__global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           float* __restrict__ dqkv, long n, int heads, int ld3, int ldo) {
   __shared__ __attribute__((aligned(16))) unsigned char s_q[F16_ROWS];      // Q   [query][channel]
   __shared__ __attribute__((aligned(16))) unsigned char s_g[F16_ROWS];      // dO  [query][channel]
   __shared__ __attribute__((aligned(16))) unsigned char s_qt[F16_COLS];     // Q^T  [channel][query]
   __shared__ __attribute__((aligned(16))) unsigned char s_gt[F16_COLS];     // dO^T [channel][query]
-  __shared__ __attribute__((aligned(16))) float s_ls[F16_T], s_dl[F16_T];
-  __shared__ __attribute__((aligned(16))) float s_o[2][F16_T * F16_TS];     // dk, dv
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * F16_D;
+  __shared__ __attribute__((aligned(16))) float s_ls[FA_T], s_dl[FA_T];
+  __shared__ __attribute__((aligned(16))) float s_o[2][FA_T * F16_TS];      // dk, dv
+  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hidden = heads * FA_D;
   const int r = lane & 31, hh = lane >> 5, kh = wv & 1, qh = wv >> 1, row = 32 * kh + r;
-  const long k0 = (long)blockIdx.x * F16_T;
-  const float* base = qkv + (size_t)b * n * ld3 + h * F16_D;
-  const float* gbase = dout + (size_t)b * n * ldo + h * F16_D;
+  const long k0 = (long)blockIdx.x * FA_T;
+  const float* base = qkv + (size_t)b * n * ld3 + h * FA_D;
+  const float* gbase = dout + (size_t)b * n * ldo + h * FA_D;
   const size_t stat = ((size_t)b * heads + h) * n;
   const long ki = k0 + row < n ? k0 + row : n - 1;
   uint4 kb[2], vb[2];
@@ -341,37 +313,37 @@ __global__ __launch_bounds__(F16_BS) void fa16_dkv_kernel(const float* __restric
     f16_b_row(base + hidden + (size_t)ki * ld3, hh, kb, x);
     f16_b_row(base + 2 * hidden + (size_t)ki * ld3, hh, vb, x);
   }
-  f16_f32x16 dk = f16_zero(), dv = f16_zero();
+  f32x16 dk = mfma16_zero(), dv = mfma16_zero();
   F16Raw rq = f16_fetch(base, 0, n, ld3, tid), rg = f16_fetch(gbase, 0, n, ldo, tid);
   float rls = 0.f, rdl = 0.f;
-  if (tid < F16_T && tid < n) {
+  if (tid < FA_T && tid < n) {
     rls = lse[stat + tid];
     rdl = delta[stat + tid];
   }
-  for (long i0 = 0; i0 < n; i0 += F16_T) {                  // (uniform: the barriers and the MFMAs)
+  for (long i0 = 0; i0 < n; i0 += FA_T) {                   // (uniform: the barriers and the MFMAs)
     __syncthreads();
     f16_put_rows(s_q, rq, tid);
     f16_put_cols(s_qt, rq, tid);
     f16_put_rows(s_g, rg, tid);
     f16_put_cols(s_gt, rg, tid);
-    if (tid < F16_T) {
+    if (tid < FA_T) {
       s_ls[tid] = rls;
       s_dl[tid] = rdl;
     }
     __syncthreads();
-    if (i0 + F16_T < n) {
-      rq = f16_fetch(base, i0 + F16_T, n, ld3, tid);
-      rg = f16_fetch(gbase, i0 + F16_T, n, ldo, tid);
-      if (tid < F16_T) {
-        const bool ok = i0 + F16_T + tid < n;
-        rls = ok ? lse[stat + i0 + F16_T + tid] : 0.f;
-        rdl = ok ? delta[stat + i0 + F16_T + tid] : 0.f;
+    if (i0 + FA_T < n) {
+      rq = f16_fetch(base, i0 + FA_T, n, ld3, tid);
+      rg = f16_fetch(gbase, i0 + FA_T, n, ldo, tid);
+      if (tid < FA_T) {
+        const bool ok = i0 + FA_T + tid < n;
+        rls = ok ? lse[stat + i0 + FA_T + tid] : 0.f;
+        rdl = ok ? delta[stat + i0 + FA_T + tid] : 0.f;
       }
     }
-    f16_f32x16 sa = f16_mfma(f16_a_rows(s_q, 32 * qh + r, hh, 0), kb[0], f16_zero());
-    sa = f16_mfma(f16_a_rows(s_q, 32 * qh + r, hh, 1), kb[1], sa);
-    f16_f32x16 dp = f16_mfma(f16_a_rows(s_g, 32 * qh + r, hh, 0), vb[0], f16_zero());
-    dp = f16_mfma(f16_a_rows(s_g, 32 * qh + r, hh, 1), vb[1], dp);
+    f32x16 sa = mfma16(f16_a_rows(s_q, 32 * qh + r, hh, 0), kb[0], mfma16_zero());
+    sa = mfma16(f16_a_rows(s_q, 32 * qh + r, hh, 1), kb[1], sa);
+    f32x16 dp = mfma16(f16_a_rows(s_g, 32 * qh + r, hh, 0), vb[0], mfma16_zero());
+    dp = mfma16(f16_a_rows(s_g, 32 * qh + r, hh, 1), vb[1], dp);
     const long qq0 = i0 + 32 * qh;
     float p[16], ds[16];
 #pragma unroll
@@ -382,14 +354,14 @@ __global__ __launch_bounds__(F16_BS) void fa16_dkv_kernel(const float* __restric
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int i = 4 * g + j;
-        p[i] = qq0 + f16_row(i, hh) < n ? f16_exp(sa[i] * F16_SCALE - lsv[j]) : 0.f;
+        p[i] = qq0 + f16_row(i, hh) < n ? fa_exp(sa[i] * FA_SCALE - lsv[j]) : 0.f;
         ds[i] = p[i] * (dp[i] - dlv[j]);
       }
     }
-    dv = f16_mfma(f16_a_cols(s_gt, r, hh, qh, 0), f16_b_acc(p, 0), dv);
-    dv = f16_mfma(f16_a_cols(s_gt, r, hh, qh, 1), f16_b_acc(p, 1), dv);
-    dk = f16_mfma(f16_a_cols(s_qt, r, hh, qh, 0), f16_b_acc(ds, 0), dk);
-    dk = f16_mfma(f16_a_cols(s_qt, r, hh, qh, 1), f16_b_acc(ds, 1), dk);
+    dv = mfma16(f16_a_cols(s_gt, r, hh, qh, 0), f16_b_acc(p, 0), dv);
+    dv = mfma16(f16_a_cols(s_gt, r, hh, qh, 1), f16_b_acc(p, 1), dv);
+    dk = mfma16(f16_a_cols(s_qt, r, hh, qh, 0), f16_b_acc(ds, 0), dk);
+    dk = mfma16(f16_a_cols(s_qt, r, hh, qh, 1), f16_b_acc(ds, 1), dk);
   }
   float xk[16], xv[16];
   if (qh == 1) {
@@ -406,7 +378,7 @@ __global__ __launch_bounds__(F16_BS) void fa16_dkv_kernel(const float* __restric
     float o1[16];
     f16_take(s_o[0], row, hh, o1);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) xk[i] = (dk[i] + o1[i]) * F16_SCALE;
+    for (int i = 0; i < 16; ++i) xk[i] = (dk[i] + o1[i]) * FA_SCALE;
     f16_give(s_o[0], row, hh, xk);
     f16_take(s_o[1], row, hh, o1);
 #pragma unroll
@@ -414,34 +386,26 @@ __global__ __launch_bounds__(F16_BS) void fa16_dkv_kernel(const float* __restric
     f16_give(s_o[1], row, hh, xv);
   }
   __syncthreads();
-  float* dst = dqkv + (size_t)b * n * ld3 + h * F16_D;
+  float* dst = dqkv + (size_t)b * n * ld3 + h * FA_D;
   f16_flush(s_o[0], dst + hidden, k0, n, ld3, tid);
   f16_flush(s_o[1], dst + 2 * hidden, k0, n, ld3, tid);
 }
 
 // ================================================================================================ host side
-inline bool f16_shape_ok(int B, int H, int W, int heads) {
-  return B > 0 && B <= 65535 && H > 0 && W > 0 && (long)H * W <= F16_MAX_N && heads >= 1 && heads <= 16384;
-}
-inline bool f16_strides_ok(int heads, int ld3, int ldo) {
-  return ld3 >= 3 * heads * F16_D && ld3 % 4 == 0 && ldo >= heads * F16_D && ldo % 4 == 0;
-}
-// workgroup columns: one per head and one per 32 channels of padding behind `used`
-inline int f16_slots(int heads, int ld, int used) { return heads + (ld - used + F16_D - 1) / F16_D; }
 }  // namespace
 
 extern "C" int ld_dn_fa_forward16(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo,
                                   void* stream) {
-  LD_REQUIRE(f16_shape_ok(B, H, W, heads) && f16_strides_ok(heads, ld3, ldo),
+  LD_REQUIRE(fa_shape_ok(B, H, W, heads) && fa_strides_ok(heads, ld3, ldo),
              "ld_dn_fa_forward16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of "
              "4)", B, H, W, heads, ld3, ldo);
   LD_REQUIRE(qkv && out, "ld_dn_fa_forward16: null pointer");
   LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(out) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
              "ld_dn_fa_forward16: a pointer is not aligned (qkv, out: 16 bytes)");
-  const int slots = f16_slots(heads, ldo, heads * F16_D);
+  const int slots = fa_slots(heads, ldo, heads * FA_D);
   LD_REQUIRE(slots <= 65535, "ld_dn_fa_forward16: ldo %d", ldo);
   const long n = (long)H * W;
-  LD_LAUNCH(fa16_forward_kernel, dim3((unsigned)((n + F16_T - 1) / F16_T), (unsigned)slots, (unsigned)B), dim3(F16_BS), 0,
+  LD_LAUNCH(fa16_forward_kernel, dim3((unsigned)((n + FA_T - 1) / FA_T), (unsigned)slots, (unsigned)B), dim3(FA_BS), 0,
             dn_st(stream), qkv, out, lse, n, heads, ld3, ldo);
   LD_LAUNCH_CHECK("dn_fa_forward16");
   return LD_OK;
@@ -449,22 +413,22 @@ extern "C" int ld_dn_fa_forward16(const float* qkv, float* out, float* lse, int 
 
 extern "C" int ld_dn_fa_backward16(const float* qkv, const float* out, const float* dout, const float* lse, void* work,
                                    float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
-  LD_REQUIRE(f16_shape_ok(B, H, W, heads) && f16_strides_ok(heads, ld3, ldo),
+  LD_REQUIRE(fa_shape_ok(B, H, W, heads) && fa_strides_ok(heads, ld3, ldo),
              "ld_dn_fa_backward16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples "
              "of 4)", B, H, W, heads, ld3, ldo);
   LD_REQUIRE(qkv && out && dout && lse && work && dqkv, "ld_dn_fa_backward16: null pointer");
   LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(out) && dn_aligned16(dout) && dn_aligned16(dqkv) &&
                  (reinterpret_cast<uintptr_t>(lse) & 3) == 0 && (reinterpret_cast<uintptr_t>(work) & 3) == 0,
              "ld_dn_fa_backward16: a pointer is not aligned (qkv, out, dout, dqkv: 16 bytes)");
-  const int slots = f16_slots(heads, ld3, 3 * heads * F16_D);
+  const int slots = fa_slots(heads, ld3, 3 * heads * FA_D);
   LD_REQUIRE(slots <= 65535, "ld_dn_fa_backward16: ld3 %d", ld3);
   const long n = (long)H * W;
-  const unsigned tiles = (unsigned)((n + F16_T - 1) / F16_T);
+  const unsigned tiles = (unsigned)((n + FA_T - 1) / FA_T);
   hipStream_t st = dn_st(stream);
   float* delta = static_cast<float*>(work);                // [B, heads, n]: ld_dn_fa_work_bytes
-  LD_LAUNCH(fa16_dq_kernel, dim3(tiles, (unsigned)slots, (unsigned)B), dim3(F16_BS), 0, st, qkv, out, dout, lse, delta, dqkv, n,
+  LD_LAUNCH(fa16_dq_kernel, dim3(tiles, (unsigned)slots, (unsigned)B), dim3(FA_BS), 0, st, qkv, out, dout, lse, delta, dqkv, n,
             heads, ld3, ldo);
-  LD_LAUNCH(fa16_dkv_kernel, dim3(tiles, (unsigned)heads, (unsigned)B), dim3(F16_BS), 0, st, qkv, dout, lse, (const float*)delta,
+  LD_LAUNCH(fa16_dkv_kernel, dim3(tiles, (unsigned)heads, (unsigned)B), dim3(FA_BS), 0, st, qkv, dout, lse, (const float*)delta,
             dqkv, n, heads, ld3, ldo);
   LD_LAUNCH_CHECK("dn_fa_backward16");
   return LD_OK;

@@ -5,13 +5,12 @@
 // fp64 part format in `work` and the two merge kernels are the fp32 path's (la_common.hip.h).  No floating-point atomics,
 // every sum in one order, nothing allocates.
 //
-// Lane map of the MFMA, lane l with r = l & 31, hh = l >> 5: the lane holds A[r][8 hh + j] and B[8 hh + j][r], j = 0..7,
-// and D[(reg & 3) + 8 (reg >> 2) + 4 hh][r] in its 16 accumulator registers.
+// The MFMA and its lane map (lane l: r = l & 31, hh = l >> 5) are mfma16.hip.h's.
 //
 //   * The two reductions over pixels (context; dctx of the backward): D[d][e] = sum_n P[n][d] V[n][e], K is the pixel axis.
 //     The loader is the fp32 kernel's (8 lanes per (pixel, head), 16-byte loads, the same 8-lane softmax), a thread taking
 //     the same four channels of two neighbouring pixels.  It stores the pair of each channel as one dword into an image
-//     [channel][64 pixels] bf16 with 128-byte rows whose 16-byte groups are XOR-swizzled by the row (l16_off): the stores
+//     [channel][64 pixels] bf16 with 128-byte rows whose 16-byte groups are XOR-swizzled by the row (mfma16_off): the stores
 //     of a half-wave fall on 32 different banks, and a lane's fragment (8 consecutive pixels of channel r) is one
 //     ds_read_b128 whose four 16-lane groups each cover all 64 banks.  A tile is 64 pixels = four K-steps, one per wave;
 //     two images alternate, so a tile costs one barrier.  A wave's fp32 accumulator holds at most L16_RUN tiles (16 x 16 =
@@ -29,10 +28,9 @@
 #include "common.hip.h"
 #include "dn_common.hip.h"
 #include "la_common.hip.h"
+#include "mfma16.hip.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float l16_f32x16;
 
 constexpr int L16_RUN = 16;        // tiles of 64 pixels per fp32 run of the reductions
 constexpr int L16_IMG = LA_D * LA_TP * 2;      // bytes of one [32 channels][64 pixels] bf16 image
@@ -40,20 +38,8 @@ constexpr int L16_IMG = LA_D * LA_TP * 2;      // bytes of one [32 channels][64 
 __device__ __forceinline__ bf16x8 l16_frag(unsigned a, unsigned b, unsigned c, unsigned d) {
   return __builtin_bit_cast(bf16x8, make_uint4(a, b, c, d));
 }
-__device__ __forceinline__ l16_f32x16 l16_mfma(bf16x8 a, bf16x8 b, l16_f32x16 acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ l16_f32x16 l16_zero() {
-  l16_f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-  return z;
-}
 
 // ================================================================================================ reductions
-// byte offset of pixels 8 grp .. 8 grp + 7 of channel c in an image: 128-byte rows, the 16-byte groups swizzled by the row
-__device__ __forceinline__ int l16_off(int c, int grp) { return c * 128 + 16 * (grp ^ (((c >> 2) ^ ((c >> 1) & 1)) & 7)); }
-
 // part (b, head, s) of pixels [s ppp, (s + 1) ppp).  CTX: (m, Z, ctx Z) with P = exp(k - m_part), V = v; otherwise
 // sum of softmax_d(q)[d] dO[e].
 template <bool CTX>
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restr
     __syncthreads();
     mk = *reinterpret_cast<const float4*>(sm + 4 * l);
   }
-  l16_f32x16 acc = l16_zero();
+  f32x16 acc = mfma16_zero();
   double dacc[16], z[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 16; ++i) dacc[i] = 0.0;
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restr
     unsigned char* img = &sT[it & 1][0][0];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int at = l16_off(4 * l + i, rr >> 2) + 4 * (rr & 3);
+      const int at = mfma16_off(4 * l + i, rr >> 2) + 4 * (rr & 3);
       *reinterpret_cast<unsigned*>(img + at) = pack_bf16x2(pv[0][i], pv[1][i]);
       *reinterpret_cast<unsigned*>(img + L16_IMG + at) = pack_bf16x2(vv[0][i], vv[1][i]);
     }
@@ -137,14 +123,14 @@ __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restr
     }
     __syncthreads();
     {                                                     // K-step `wave` of the tile: pixels 16 wave + 8 hh .. + 7
-      const int at = l16_off(r, 2 * wave + hh);
+      const int at = mfma16_off(r, 2 * wave + hh);
       const uint4 a = *reinterpret_cast<const uint4*>(img + at), bb = *reinterpret_cast<const uint4*>(img + L16_IMG + at);
-      acc = l16_mfma(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), acc);
+      acc = mfma16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), acc);
     }
     if ((it & (L16_RUN - 1)) == L16_RUN - 1) {            // the end of a run: fp32 -> fp64
 #pragma unroll
       for (int i = 0; i < 16; ++i) dacc[i] += (double)acc[i];
-      acc = l16_zero();
+      acc = mfma16_zero();
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         z[i] += (double)zz[i];
@@ -325,8 +311,8 @@ __global__ __launch_bounds__(LA_BS) void la16_out_kernel(const float* __restrict
     const L16Vec qv = l16_take(tile, r, hh);
     if (base + 128 < p1) raw = l16_fetch(Q, ld3, base + 128, p1, lane);
     const L16Vec p = l16_softmax(qv);
-    l16_f32x16 o = l16_mfma(a0, l16_b(p, 0), l16_zero());
-    o = l16_mfma(a1, l16_b(p, 1), o);
+    f32x16 o = mfma16(a0, l16_b(p, 0), mfma16_zero());
+    o = mfma16(a1, l16_b(p, 1), o);
     L16Vec ov;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -401,10 +387,10 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
       rk4 = l16_fetch(Q + hidden, ld3, base + 128, p1, lane);
       rv = l16_fetch(Q + 2 * hidden, ld3, base + 128, p1, lane);
     }
-    l16_f32x16 s = l16_mfma(c0, l16_b(dov, 0), l16_zero());
-    s = l16_mfma(c1, l16_b(dov, 1), s);
-    l16_f32x16 tk = l16_mfma(d0, l16_b(vv, 0), l16_zero());
-    tk = l16_mfma(d1, l16_b(vv, 1), tk);
+    f32x16 s = mfma16(c0, l16_b(dov, 0), mfma16_zero());
+    s = mfma16(c1, l16_b(dov, 1), s);
+    f32x16 tk = mfma16(d0, l16_b(vv, 0), mfma16_zero());
+    tk = mfma16(d1, l16_b(vv, 1), tk);
     L16Vec ks;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -415,8 +401,8 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
       ks.v[g][2] = la_exp(kv.v[g][2] - mk.z) * iz.z;
       ks.v[g][3] = la_exp(kv.v[g][3] - mk.w) * iz.w;
     }
-    l16_f32x16 dv = l16_mfma(e0, l16_b(ks, 0), l16_zero());
-    dv = l16_mfma(e1, l16_b(ks, 1), dv);
+    f32x16 dv = mfma16(e0, l16_b(ks, 0), mfma16_zero());
+    dv = mfma16(e1, l16_b(ks, 1), dv);
     const L16Vec p = l16_softmax(qv);
     float dot = 0.0f;
 #pragma unroll

@@ -42,8 +42,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import (check_act_storage, check_act_storage_precision, check_attn_precision, check_conv_precision,
-                        check_full_attn_precision, stream)
+from .trainable import SWITCHES, check_act_storage_precision, check_switch, stream
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -169,10 +168,10 @@ class DenoiserTrainer:
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
                  conv_precision="fp32", act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
-        check_conv_precision("DenoiserTrainer", conv_precision)
-        check_full_attn_precision("DenoiserTrainer", full_attn_precision)
-        check_attn_precision("DenoiserTrainer", attn_precision)
-        check_act_storage("DenoiserTrainer", act_storage)
+        switches = dict(conv_precision=conv_precision, act_storage=act_storage, attn_precision=attn_precision,
+                        full_attn_precision=full_attn_precision)
+        for switch in SWITCHES:
+            check_switch("DenoiserTrainer", switch, switches[switch])
         check_act_storage_precision("DenoiserTrainer", act_storage, conv_precision)
         if group is not None and comm is not None:
             raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
@@ -195,10 +194,8 @@ class DenoiserTrainer:
             if not isinstance(v, int) or isinstance(v, bool) or v < lo:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
         # (raises ValueError for what it cannot train)
-        online = TrainableUnet(**online_kwargs(model), conv_precision=conv_precision, act_storage=act_storage,
-                               attn_precision=attn_precision, full_attn_precision=full_attn_precision)
-        self.conv_precision, self.act_storage, self.attn_precision = conv_precision, act_storage, attn_precision
-        self.full_attn_precision = full_attn_precision
+        online = TrainableUnet(**online_kwargs(model), **switches)
+        vars(self).update(switches)                   # (what the trainer was built with: self.conv_precision and so on)
         dev = diffusion.device
         if dev.type != "cuda":
             raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")

@@ -25,7 +25,7 @@ import torch
 from torch import nn
 
 from . import _cabi as cabi
-from .trainable import Run, TrainableModule, check_attn_precision, ones_zeros, pack_conv, pack_vec, pad64, stream
+from .trainable import Run, TrainableModule, ones_zeros, pack_conv, pack_vec, pad64, stream
 
 DIM_HEAD = 32
 
@@ -142,20 +142,7 @@ class _Run(RMSNormRun):
         return dxp[..., :m.dim].permute(0, 3, 1, 2), (), g
 
 
-class AttnPrecision:
-    """Mixin of the two attention modules: ``attn_precision``, the arithmetic of the attention core's products, validated on
-    assignment against the class's ``ATTN_PRECISIONS`` (a refused value leaves the old one in place)."""
-
-    attn_precision = "fp32"
-    ATTN_PRECISIONS = ("fp32",)
-
-    def __setattr__(self, name, value):
-        if name == "attn_precision":
-            check_attn_precision(type(self).__name__, value, self.ATTN_PRECISIONS)
-        super().__setattr__(name, value)
-
-
-class LinearAttention(AttnPrecision, TrainableModule):
+class LinearAttention(TrainableModule):
     """``LinearAttention(dim, heads=4, dim_head=32)`` of ddpm.py:214-251, forward and backward in HIP (fp32).
 
     ``forward(x)``: ``x`` [B, dim, H, W] fp32 on the GPU (``channels_last`` with ``dim`` a multiple of 64 is read in place);
@@ -169,6 +156,7 @@ class LinearAttention(AttnPrecision, TrainableModule):
     has none), and it is independent of ``conv_precision``."""
 
     Run = _Run
+    attn_precision = "fp32"
     ATTN_PRECISIONS = ("fp32", "bf16")
 
     def __init__(self, dim, heads=4, dim_head=32):

@@ -8,17 +8,20 @@ parameter's ``data_ptr`` and ``_version`` (``PackedWeights``).  A module's forwa
 ``autograd.Function``; each half is a sequence of launches that the module's ``Run`` subclass writes down, out of the launches
 every module uses (``Run``: buffers, the NHWC repack, ``ld_pc_conv``, the weight and bias gradients) and its own.
 
-``TrainableModule.conv_precision`` (``"fp32"``, the default, or ``"bf16"``) is the one switch of the convolutions' arithmetic:
-``pack_conv``, ``Run.conv`` and ``Run.wgrad_packed`` route on it.  At ``"bf16"`` the kernel-layout weights are bf16 and the
-convolution, its data gradient and its weight gradient run on ``csrc/conv16.hip`` (operands rounded to bf16, products on the
-bf16 matrix cores, fp32 accumulation); what sits in memory, and every other launch, is the same.
-
-``TrainableModule.act_storage`` (``"fp32"``, the default, or ``"bf16"``) says how a module keeps the activations that only its
-convolutions read.  At ``conv_precision="bf16"`` every convolution launch rounds such a tensor to bf16 on its way into LDS, so
-storing it as bf16 in the first place (``Run.nhwc(dtype=)``, a producer's ``_to16`` launch) changes no bit of any result and
-halves what the producer writes, what the convolutions read and what autograd keeps.  ``Run.conv`` and ``Run.wgrad_packed``
-pick the ``_from16`` entry point from the dtype of the activation they are handed.  A module accepts the values it implements
-(``ACT_STORAGES``): ``"bf16"`` on ``ResnetBlock`` only so far.
+The training precision switches (``SWITCHES``).  Each is ``"fp32"``, the default, or ``"bf16"``.  A module has a switch when its
+class defines the default and the tuple of the values it implements (``conv_precision`` / ``CONV_PRECISIONS``); the value is a
+class attribute until it is set, is validated on assignment (``check_switch``: a refused value leaves the old one in place), is
+read at every call, and is no part of the ``state_dict``.  ``TrainableUnet`` hands a value to the sub-modules whose class lists
+more than one, and ``DenoiserTrainer`` passes it through.
+  ``conv_precision``       every module: ``pack_conv``, ``Run.conv`` and ``Run.wgrad_packed`` route on it.  The kernel-layout
+                           weights are bf16 (it is in their cache key) and the convolution and its two gradients run on
+                           ``csrc/conv16.hip``: operands rounded to bf16, fp32 accumulation; what sits in memory stays fp32.
+  ``act_storage``          ``ResnetBlock`` only so far: the activations that only its convolutions read are stored as bf16
+                           (``Run.nhwc(dtype=)``, a producer's ``_to16`` launch; ``Run.conv`` and ``Run.wgrad_packed`` pick the
+                           ``_from16`` entry point from the dtype they are handed).  Needs ``conv_precision = "bf16"``, whose
+                           launches round such a tensor anyway, so no bit of any result changes (``check_act_storage_precision``).
+  ``attn_precision``       ``LinearAttention``: the four passes of its core on ``csrc/linattn16.hip`` (a placeholder on ``Attention``).
+  ``full_attn_precision``  ``Attention``: the three passes of its core on ``csrc/attention16.hip``.
 """
 import ctypes as C
 
@@ -63,37 +66,20 @@ class PackedWeights:
 
 
 # ---------------------------------------------------------------------------------------------------- packing
-CONV_PRECISIONS = ("fp32", "bf16")
+# switch -> the class attribute that lists the values a module implements (the module docstring)
+SWITCHES = {"conv_precision": "CONV_PRECISIONS", "act_storage": "ACT_STORAGES", "attn_precision": "ATTN_PRECISIONS",
+            "full_attn_precision": "FULL_ATTN_PRECISIONS"}
 
 
-def check_conv_precision(name, value):
-    if value not in CONV_PRECISIONS:
-        raise ValueError(f"{name}: conv_precision {value!r} is not one of {', '.join(repr(v) for v in CONV_PRECISIONS)}")
-    return value
-
-
-ATTN_PRECISIONS = ("fp32", "bf16")
-
-
-def check_attn_precision(name, value, allowed=ATTN_PRECISIONS):
+def check_switch(owner, switch, value, allowed=("fp32", "bf16")):
     if not isinstance(value, str) or value not in allowed:
-        raise ValueError(f"{name}: attn_precision {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
-    return value
-
-
-FULL_ATTN_PRECISIONS = ("fp32", "bf16")
-
-
-def check_full_attn_precision(name, value, allowed=FULL_ATTN_PRECISIONS):
-    if not isinstance(value, str) or value not in allowed:
-        raise ValueError(f"{name}: full_attn_precision {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
+        raise ValueError(f"{owner}: {switch} {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
     return value
 
 
 def check_act_storage(name, value, allowed=("fp32", "bf16")):
-    if not isinstance(value, str) or value not in allowed:
-        raise ValueError(f"{name}: act_storage {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
-    return value
+    """``check_switch`` under the one earlier name that ``tests/test_act_storage.py`` imports."""
+    return check_switch(name, "act_storage", value, allowed)
 
 
 def check_act_storage_precision(name, act_storage, conv_precision):
@@ -278,14 +264,13 @@ class TrainableModule(PackedWeights, nn.Module):
     #                          multiplied on the bf16 matrix cores with fp32 accumulation; everything else stays fp32
     act_storage = "fp32"     # or "bf16" where the module has it (ACT_STORAGES): the activations that only its convolutions read
     #                          are written, read and saved as bf16; at conv_precision "bf16" only, where no result changes
+    CONV_PRECISIONS = ("fp32", "bf16")
     ACT_STORAGES = ("fp32",)
     Run = None
 
     def __setattr__(self, name, value):
-        if name == "conv_precision":
-            check_conv_precision(type(self).__name__, value)
-        elif name == "act_storage":
-            check_act_storage(type(self).__name__, value, self.ACT_STORAGES)
+        if name in SWITCHES and hasattr(type(self), name):
+            check_switch(type(self).__name__, name, value, getattr(self, SWITCHES[name]))
         super().__setattr__(name, value)
 
     def _run(self, x):

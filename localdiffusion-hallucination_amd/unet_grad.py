@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import check_act_storage, check_attn_precision, check_conv_precision, check_full_attn_precision, pad64, stream
+from .trainable import SWITCHES, check_switch, pad64, stream
 from .weights import UnetConfig
 
 
@@ -174,6 +174,21 @@ def _check_join(name, a, other):
 
 
 # ---------------------------------------------------------------------------------------------------- the Unet
+def _switch(name, doc):
+    """``TrainableUnet``'s property for a switch of ``trainable.SWITCHES``: the setter checks the value, stores it and hands it
+    to every sub-module whose class lists more than one value for the switch.  A refused value changes nothing, and no
+    switch touches another: none needs another but ``act_storage`` (``check_act_storage_precision``, at the block's call)."""
+    def get(self):
+        return getattr(self, "_" + name)
+
+    def hand_down(self, value):
+        setattr(self, "_" + name, check_switch("TrainableUnet", name, value))
+        for m in self.modules():
+            if len(getattr(type(m), SWITCHES[name], ())) > 1:
+                setattr(m, name, value)
+    return property(get, hand_down, doc=doc)
+
+
 class TrainableUnet(nn.Module):
     """``Unet`` of ddpm.py:286-451 (the constructor arguments of ``ldh.Unet`` minus ``compute_dtype`` and ``tuning``), forward
     and backward in HIP (fp32), under ``torch.autograd``.  The ``state_dict`` is the reference's.
@@ -192,10 +207,10 @@ class TrainableUnet(nn.Module):
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
                  act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
         super().__init__()
-        check_full_attn_precision("TrainableUnet", full_attn_precision)
-        check_conv_precision("TrainableUnet", conv_precision)
-        check_act_storage("TrainableUnet", act_storage)
-        check_attn_precision("TrainableUnet", attn_precision)
+        switches = dict(conv_precision=conv_precision, act_storage=act_storage, attn_precision=attn_precision,
+                     full_attn_precision=full_attn_precision)
+        for switch in SWITCHES:
+            check_switch("TrainableUnet", switch, switches[switch])
         for flag, what in ((self_condition, "self_condition"), (learned_variance, "learned_variance"),
                            (learned_sinusoidal_cond, "learned_sinusoidal_cond"), (random_fourier_features, "random_fourier_features")):
             if flag:
@@ -251,18 +266,10 @@ class TrainableUnet(nn.Module):
                                            Upsample(cout, cin) if j < n - 1 else Conv2d(cout, cin, 3, padding=1)]))
         self.final_res_block = block(2 * dim, dim)
         self.final_conv = Conv2d(dim, self.out_dim, 1)
-        self._conv_precision = "fp32"
-        if conv_precision != "fp32":                 # (the default is the modules' class attribute: nothing to hand down)
-            self.conv_precision = conv_precision
-        self._act_storage = "fp32"
-        if act_storage != "fp32":
-            self.act_storage = act_storage
-        self._attn_precision = "fp32"
-        if attn_precision != "fp32":
-            self.attn_precision = attn_precision
-        self._full_attn_precision = "fp32"
-        if full_attn_precision != "fp32":
-            self.full_attn_precision = full_attn_precision
+        for switch, value in switches.items():
+            setattr(self, "_" + switch, "fp32")
+            if value != "fp32":                      # (the default is the modules' class attribute: nothing to hand down)
+                setattr(self, switch, value)
 
     @property
     def downsample_factor(self):
@@ -280,61 +287,18 @@ class TrainableUnet(nn.Module):
             if m is not self and hasattr(type(m), "debug_fill"):
                 m.debug_fill = value
 
-    @property
-    def conv_precision(self):
-        return self._conv_precision
-
-    @conv_precision.setter
-    def conv_precision(self, value):
-        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every convolution of every sub-module, and both of its gradients, round
-        their operands to bf16 and multiply on the bf16 matrix cores with fp32 accumulation (``TrainableModule``); activations,
-        parameters, gradients, the norms, the attention cores, the head and the time MLP stay fp32."""
-        self._conv_precision = check_conv_precision("TrainableUnet", value)
-        for m in self.modules():
-            if m is not self and hasattr(type(m), "conv_precision"):
-                m.conv_precision = value
-
-    @property
-    def act_storage(self):
-        return self._act_storage
-
-    @act_storage.setter
-    def act_storage(self, value):
-        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``ResnetBlock`` keeps the activations that only its convolutions read
-        as bf16 (``ResnetBlock``); that needs ``conv_precision = "bf16"``, where it changes no bit of any result.  The other
-        modules have no such storage yet and stay fp32."""
-        self._act_storage = check_act_storage("TrainableUnet", value)
-        for m in self.modules():
-            if isinstance(m, ResnetBlock):
-                m.act_storage = value
-
-    @property
-    def attn_precision(self):
-        return self._attn_precision
-
-    @attn_precision.setter
-    def attn_precision(self, value):
-        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``LinearAttention`` runs the four passes of its attention core on the
-        bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention`` modules have a switch of their own
-        (``full_attn_precision``) and are not touched; ``conv_precision`` and ``act_storage`` are not touched, and neither needs the other."""
-        self._attn_precision = check_attn_precision("TrainableUnet", value)
-        for m in self.modules():
-            if isinstance(m, LinearAttention):
-                m.attn_precision = value
-
-    @property
-    def full_attn_precision(self):
-        return self._full_attn_precision
-
-    @full_attn_precision.setter
-    def full_attn_precision(self, value):
-        """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every full-softmax ``Attention`` runs the three passes of its core on the
-        bf16 matrix cores (``Attention.full_attn_precision``).  Nothing else is touched: the ``LinearAttention`` modules and
-        their ``attn_precision``, ``conv_precision`` and ``act_storage`` stay as they are, and none needs another."""
-        self._full_attn_precision = check_full_attn_precision("TrainableUnet", value)
-        for m in self.modules():
-            if isinstance(m, Attention):
-                m.full_attn_precision = value
+    conv_precision = _switch("conv_precision", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every convolution of every
+        sub-module, and both of its gradients, round their operands to bf16 and multiply on the bf16 matrix cores with fp32
+        accumulation (``TrainableModule``); activations, parameters, gradients, the norms, the attention cores, the head and the
+        time MLP stay fp32.""")
+    act_storage = _switch("act_storage", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``ResnetBlock`` keeps the activations
+        that only its convolutions read as bf16 (``ResnetBlock``); that needs ``conv_precision = "bf16"``, where it changes no
+        bit of any result.  The other modules have no such storage yet and stay fp32.""")
+    attn_precision = _switch("attn_precision", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``LinearAttention`` runs the four
+        passes of its attention core on the bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention``
+        modules have a switch of their own (``full_attn_precision``) and are not touched.""")
+    full_attn_precision = _switch("full_attn_precision", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every full-softmax
+        ``Attention`` runs the three passes of its core on the bf16 matrix cores (``Attention.full_attn_precision``).""")
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

@@ -41,6 +41,39 @@ def test_packed_weights_repack_exactly_when_a_parameter_may_have_changed():
     assert toy._packed_for(dev)[0] == 5 and toy.packs == 5
 
 
+# ------------------------------------------------------------------------------------------------ 1b. the switches
+MODULES = {"ResnetBlock": lambda: ldh.ResnetBlock(32, 64), "LinearAttention": lambda: ldh.LinearAttention(32),
+           "Attention": lambda: ldh.Attention(32), "Downsample": lambda: ldh.Downsample(32, 64),
+           "Upsample": lambda: ldh.Upsample(64, 32), "Conv2d": lambda: ldh.Conv2d(32, 32, 3, padding=1),
+           "BasicBlock": lambda: ldh.BasicBlock(32, 32, 64)}
+
+
+@pytest.mark.parametrize("cls", MODULES)
+@pytest.mark.parametrize("switch", trainable.SWITCHES)
+def test_every_switch_refuses_what_its_class_does_not_list(switch, cls):
+    """A module has a switch exactly when its class defines the default and the tuple; a value outside the tuple is a
+    ``ValueError`` with one text, and the old value stays."""
+    mod = MODULES[cls]()
+    assert type(mod).__name__ == cls and isinstance(mod, trainable.TrainableModule)
+    has = hasattr(type(mod), switch)
+    assert has == hasattr(type(mod), trainable.SWITCHES[switch])
+    assert has or switch in ("attn_precision", "full_attn_precision")          # (every module has the first two)
+    if not has:
+        return
+    allowed = getattr(type(mod), trainable.SWITCHES[switch])
+    assert getattr(mod, switch) == "fp32" and allowed[0] == "fp32" and set(allowed) <= {"fp32", "bf16"}
+    for value in allowed[::-1]:
+        setattr(mod, switch, value)                                             # (ends at "fp32")
+        assert getattr(mod, switch) == value
+    bad = [v for v in ("fp32", "bf16", "fp16", "BF16", "", None, 16, ("bf16",)) if v not in allowed]
+    for value in bad:
+        with pytest.raises(ValueError) as e:
+            setattr(mod, switch, value)
+        assert str(e.value) == f"{cls}: {switch} {value!r} is not one of " + ", ".join(repr(v) for v in allowed)
+        assert getattr(mod, switch) == "fp32"
+    assert switch not in "".join(mod.state_dict())
+
+
 # ------------------------------------------------------------------------------------------------ 2. the input check
 @pytest.mark.parametrize("make", [lambda: ldh.ResnetBlock(32, 64), lambda: ldh.LinearAttention(32, heads=1),
                                   lambda: ldh.Attention(32, heads=1)], ids=["ResnetBlock", "LinearAttention", "Attention"])

@@ -96,4 +96,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "128:32,256:32", run_case, report, heads=True, full_attn_precision=True))
+    sys.exit(grad_bench.main(__file__, "128:32,256:32", run_case, report, heads=True, switches=("full_attn_precision",)))

@@ -39,8 +39,7 @@ def run_case(data, H, B, a):
     inf = ldh.Unet(dim=32, init_dim=32, **U.KWARGS[data])
     gd = ldh.GaussianDiffusion(dict(OPTS, data=data), inf, image_size=H, timesteps=1000, objective="pred_v").cuda()
     tr = ldh.DenoiserTrainer(gd, train_lr=LR, adam_betas=BETAS, max_grad_norm=MAX_NORM, ema_update_every=1, ema_update_after_step=0,
-                             conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision,
-                             full_attn_precision=a.full_attn_precision)
+                             **grad_bench.switch_values(a, U.SWITCHES))
     tr.ema_initted = True                                         # (every call lerps)
     cfg = tr.online_model.cfg
     hr = torch.rand(B, cfg.channels, H, H, device="cuda")
@@ -64,7 +63,8 @@ def run_case(data, H, B, a):
     hip_kern = sorted(kern)[2]
     n_all = sum(p.numel() for p in tr.online_model.parameters())
     nbytes = 4 * 10 * n_all
-    row = dict(data=data, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision, full_attn_precision=a.full_attn_precision, peak_mb=peak / 2 ** 20, hip_ms=hip, hip_opt_ms=hip_opt, hip_opt_kernels_ms=hip_kern, params=n_all, tensors=len(tr.names),
+    row = dict(data=data, H=H, B=B, **grad_bench.switch_values(a, U.SWITCHES), peak_mb=peak / 2 ** 20, hip_ms=hip, hip_opt_ms=hip_opt,
+               hip_opt_kernels_ms=hip_kern, params=n_all, tensors=len(tr.names),
                opt_bytes=nbytes, opt_gbs=nbytes / (hip_kern * 1e-3) / 1e9, eager_ms=None, eager_opt_ms=None, eager_over_hip=None,
                eager_opt_over_hip=None)
     if a.no_eager:
@@ -112,4 +112,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, U.CASES, run_case, report, conv_precision=True, attn_precision=True, full_attn_precision=True))
+    sys.exit(grad_bench.main(__file__, U.CASES, run_case, report, switches=U.SWITCHES))

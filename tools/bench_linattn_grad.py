@@ -92,4 +92,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64", run_case, report, heads=True, attn_precision=True))
+    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64", run_case, report, heads=True, switches=("attn_precision",)))

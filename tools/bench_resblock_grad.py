@@ -46,13 +46,17 @@ def gn_bytes(dim, B, H):
     """two GroupNorms x (dout and y read by each of the two passes: the real channels; dy written: the padded pixel)"""
     return 2 * (4 * dim + (dim + 63) // 64 * 64) * B * H * H * 4
 
+SWITCHES = ("conv_precision", "act_storage")
+
 
 def run_case(dim, H, a):
     ldh.configure_runtime()
     B = a.batch
     torch.manual_seed(0)
     blk = ldh.ResnetBlock(dim, dim, time_emb_dim=TIME_DIM).cuda()
-    blk.conv_precision, blk.act_storage = a.conv_precision, a.act_storage
+    switches = grad_bench.switch_values(a, SWITCHES)
+    for s, v in switches.items():
+        setattr(blk, s, v)
     x = torch.randn(B, dim, H, H, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
     temb = torch.randn(B, TIME_DIM, device="cuda").requires_grad_(True)
     dout = (torch.randn(B, dim, H, H, device="cuda") / (B * H * H)).contiguous(memory_format=torch.channels_last)
@@ -71,7 +75,7 @@ def run_case(dim, H, a):
     gn_pass_ms = sum((ms[0] + ms[2] for label, ms in calls if label == "dn_gn_backward" and len(ms) == 3), 0.0)
     eager = {} if a.no_eager else grad_bench.eager_ms(blk, eager_block, x, [temb], dout, a.iters, a.warmup)
     best = min(eager.values()) if eager else None
-    return dict(dim=dim, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(dim=dim, H=H, B=B, **switches, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), kernels_ms=sum(v[0] for v in split.values()),
                 gn_backward_passes_ms=gn_pass_ms,
                 gn_backward_gbs=(gn_bytes(dim, B, H) / (gn_pass_ms * 1e6) if gn_pass_ms else None),
@@ -93,4 +97,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report, conv_precision=True))
+    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report, switches=SWITCHES))

@@ -40,6 +40,7 @@ FAMILIES = (("dn_pack_nhwc", "dn_pack_nhwc (boundary repacks)"), ("dn_join", "dn
             ("dn_wgrad16", "convolutions, weight gradient"), ("dn_pack_conv16", "weight packing (bf16)"),
             ("dn_colsum", "bias gradients"), ("dn_gn", "GroupNorm"), ("dn_la_", "linear attention"), ("dn_fa_", "full attention"),
             ("dn_rms_", "RMSNorm"), ("dn_head_", "head"), ("seg_pool", "max pool"))
+SWITCHES = tuple(grad_bench.SWITCH_HELP)            # every training precision switch: all are TrainableUnet arguments
 
 
 # ---------------------------------------------------------------------------------------------------- the net in eager PyTorch
@@ -164,8 +165,7 @@ def families(split):
 def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
-    net = ldh.TrainableUnet(dim=32, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision,
-                            full_attn_precision=a.full_attn_precision, **KWARGS[data]).cuda()
+    net = ldh.TrainableUnet(dim=32, **grad_bench.switch_values(a, SWITCHES), **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -190,7 +190,8 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, conv_precision=a.conv_precision, act_storage=a.act_storage, attn_precision=a.attn_precision, full_attn_precision=a.full_attn_precision, peak_mb=peak / 2 ** 20, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(data=data, H=H, B=B, **grad_bench.switch_values(a, SWITCHES), peak_mb=peak / 2 ** 20, hip_ms=hip, eager_nchw_ms=eager.get("nchw"),
+                eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
                 kernels_ms=sum(v[0] for v in split.values()), launches=sum(v[1] for v in split.values()), split=fam)
 
@@ -206,4 +207,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, CASES, run_case, report, conv_precision=True, attn_precision=True, full_attn_precision=True))
+    sys.exit(grad_bench.main(__file__, CASES, run_case, report, switches=SWITCHES))

@@ -109,29 +109,38 @@ def print_split(split, kernels_ms):
         print(f"      {k:28s} {v['ms']:9.3f} ms  {100 * v['ms'] / kernels_ms:5.1f} %  ({v['launches']} launches)")
 
 
-def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_precision=False, full_attn_precision=False):
+# what "bf16" means at each training precision switch a bench tool exposes (the HIP side's; the eager side stays fp32)
+SWITCH_HELP = {
+    "conv_precision": "the HIP side's convolutions: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
+    "act_storage": "bf16 (with --conv-precision bf16): the HIP side keeps the activations only convolutions read as bf16",
+    "attn_precision": "the HIP side's LinearAttention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
+    "full_attn_precision": "the HIP side's full-softmax Attention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
+}
+
+
+def add_switch_flags(ap, helps):
+    """``--conv-precision {fp32,bf16}`` and its like (default fp32, ``args.conv_precision``) for every switch in ``helps``,
+    {switch: help text}."""
+    for switch, text in helps.items():
+        ap.add_argument("--" + switch.replace("_", "-"), default="fp32", choices=["fp32", "bf16"], help=text)
+
+
+def switch_values(a, switches):
+    """{switch: its flag's value}: the keyword arguments of a model that takes them, and the entries of a JSON row."""
+    return {s: getattr(a, s) for s in switches}
+
+
+def main(tool, cases, run_case, report, heads=False, switches=()):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
-    returns the case's JSON row and ``report(row)`` prints it.  ``conv_precision``: the tool takes ``--conv-precision {fp32,bf16}``
-    and ``--act-storage {fp32,bf16}`` (``args.conv_precision``, ``args.act_storage``; the eager side stays fp32); ``attn_precision``: it takes ``--attn-precision {fp32,bf16}``
-    (``args.attn_precision``); ``full_attn_precision``: it takes ``--full-attn-precision {fp32,bf16}``
-    (``args.full_attn_precision``).  Every case runs in a child process (``tool --child``) under
-    ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is started on the GPU after
-    it."""
+    returns the case's JSON row and ``report(row)`` prints it.  ``switches``: the training precision switches the tool takes
+    a flag for, e.g. ``("conv_precision", "act_storage")`` (``add_switch_flags``).  Every case runs in a child process
+    (``tool --child``) under ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is
+    started on the GPU after it."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     if heads:
         ap.add_argument("--heads", type=int, default=4)
-    if conv_precision:
-        ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "bf16"],
-                        help="the HIP side's convolutions: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
-        ap.add_argument("--act-storage", default="fp32", choices=["fp32", "bf16"],
-                        help="bf16 (with --conv-precision bf16): the HIP side keeps the activations only convolutions read as bf16")
-    if attn_precision:
-        ap.add_argument("--attn-precision", default="fp32", choices=["fp32", "bf16"],
-                        help="the HIP side's LinearAttention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
-    if full_attn_precision:
-        ap.add_argument("--full-attn-precision", default="fp32", choices=["fp32", "bf16"],
-                        help="the HIP side's full-softmax Attention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)")
+    add_switch_flags(ap, {s: SWITCH_HELP[s] for s in switches})
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -144,8 +153,7 @@ def main(tool, cases, run_case, report, heads=False, conv_precision=False, attn_
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "conv_precision", "act_storage", "attn_precision", "full_attn_precision")
-                 if hasattr(a, k)
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup") + tuple(switches) if hasattr(a, k)
                  for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:

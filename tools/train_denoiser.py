@@ -30,12 +30,19 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import grad_bench                                                                # noqa: E402
 import localdiffusion_hallucination_amd as ldh                                   # noqa: E402
 from localdiffusion_hallucination_amd import checkpoint, weights                # noqa: E402
 
 KWARGS = {"mri": dict(mode="mri"), "mnist": dict(dim_mults=(1, 2, 4), full_attn=(False, False, True), mode="mnist"),
           "mvtec": dict(channels=3, out_dim=3, mode="mvtec")}
+SWITCH_HELP = {
+    "conv_precision": "bf16: the convolutions and their gradients on the bf16 matrix cores (operands rounded, fp32 accumulation)",
+    "act_storage": "bf16 (with --conv-precision bf16): activations that only convolutions read are kept as bf16; same results",
+    "attn_precision": "bf16: the LinearAttention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)",
+    "full_attn_precision": "bf16: the full-softmax Attention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)",
+}
 
 
 def parse(argv=None):
@@ -48,14 +55,7 @@ def parse(argv=None):
     ap.add_argument("--timesteps", type=int, default=250)
     ap.add_argument("--objective", default="pred_v", choices=["pred_noise", "pred_x0", "pred_v"])
     ap.add_argument("--train-lr", type=float, default=1e-4)
-    ap.add_argument("--conv-precision", default="fp32", choices=["fp32", "bf16"],
-                    help="bf16: the convolutions and their gradients on the bf16 matrix cores (operands rounded, fp32 accumulation)")
-    ap.add_argument("--act-storage", default="fp32", choices=["fp32", "bf16"],
-                    help="bf16 (with --conv-precision bf16): activations that only convolutions read are kept as bf16; same results")
-    ap.add_argument("--attn-precision", default="fp32", choices=["fp32", "bf16"],
-                    help="bf16: the LinearAttention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)")
-    ap.add_argument("--full-attn-precision", default="fp32", choices=["fp32", "bf16"],
-                    help="bf16: the full-softmax Attention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)")
+    grad_bench.add_switch_flags(ap, SWITCH_HELP)
     ap.add_argument("--save-every", type=int, default=100)
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
@@ -98,8 +98,7 @@ def setup(a, **trainer_kw):
     if a.init:
         print("init:", checkpoint.load_reference_checkpoint(a.init, gd))
     trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr,
-                                  conv_precision=a.conv_precision, act_storage=a.act_storage,
-                                  attn_precision=a.attn_precision, full_attn_precision=a.full_attn_precision, **trainer_kw)
+                                  **grad_bench.switch_values(a, SWITCH_HELP), **trainer_kw)
     return trainer, batches(tr_idx), batches(va_idx)
 
 
