@@ -766,6 +766,20 @@ int ld_dn_gn_forward_to16(const float* y, const float* gamma, const float* beta,
 int ld_dn_gn_backward(const float* dout, const float* y, const float* stat, const float* gamma, const float* beta,
                       const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B, int H,
                       int W, int C, int ldc, int groups, void* stream);
+/* The three GroupNorm entry points on a y that is bf16 in memory (conv_out_storage = "bf16": the output of a convolution's
+ * _to16 launch), [B, H, W, ldc] at the same pixel stride in elements, 16-byte aligned, its padding never read.  A bf16
+ * widens to fp32 exactly, and thread map and the order of every sum are those of the fp32 kernels: the results are bit
+ * for bit what the fp32 entry point gives on the widened tensor.  Everything else -- stat, residual, dout, dy (may be
+ * dout), the gradients -- stays fp32; _from16_to16 writes out as ld_dn_gn_forward_to16 does (residual cannot be out). */
+int ld_dn_gn_forward_from16(const void* y_bf16, const float* gamma, const float* beta, const float* film, const float* residual,
+                            double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups,
+                            void* stream);
+int ld_dn_gn_forward_from16_to16(const void* y_bf16, const float* gamma, const float* beta, const float* film,
+                                 const float* residual, double* work, float* stat, void* out_bf16, int B, int H, int W, int C,
+                                 int ldc, int groups, void* stream);
+int ld_dn_gn_backward_from16(const float* dout, const void* y_bf16, const float* stat, const float* gamma, const float* beta,
+                             const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B, int H,
+                             int W, int C, int ldc, int groups, void* stream);
 /* out [C] = the sum of x [B, H, W, ldc] over batch and pixels, channels 0..C-1 (the bias gradient of a convolution from
  * the gradient of its output; ld_seg_colsum's sibling with a pixel stride, B x runs workgroups per 256 channels instead
  * of one column of workgroups per 64).  work: ld_dn_gn_work_bytes(B, H, W, C) bytes.  C, ldc multiples of 4. */
@@ -1049,6 +1063,12 @@ int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B
 int ld_dn_conv16_from16(const ld_pc_conv_args* args, const void* weight_bf16, void* stream);
 int ld_dn_wgrad16_from16(const float* dy, const void* a_bf16, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
                          int ksize, int splits, void* stream);
+/* ld_dn_conv16 and ld_dn_conv16_from16 with the OUTPUT in bf16 (conv_out_storage = "bf16"): args->out points at a bf16 NHWC
+ * tensor [B, Ho, Wo, Cout], 4-byte aligned.  The epilogue's fp32 value (scale, shift, the optional fp32 residual, relu) is
+ * computed by the same code and rounded to nearest even on its way out, so the result is the fp32 entry point's, rounded.
+ * Same shapes and refusals; the fp32 residual cannot be out. */
+int ld_dn_conv16_to16(const ld_pc_conv_args* args, const void* weight_bf16, void* stream);
+int ld_dn_conv16_from16_to16(const ld_pc_conv_args* args, const void* weight_bf16, void* stream);
 /* An OIHW fp32 parameter [co][ci][k][k] to the two bf16 kernel layouts in one launch: fwd [cop][k * k][cip] and dgr
  * [cip][k * k, flipped][cop] (dgr[c][k * k - 1 - t][o] = w[o][c][t]), zero in the padded channels.  k 1 or 3; cop >= co and
  * cip >= ci, both even. */

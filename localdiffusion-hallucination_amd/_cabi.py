@@ -265,6 +265,13 @@ _SIGS = {
     "ld_dn_wgrad16_from16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_gn_forward_to16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_pack_nhwc_to16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, C.c_int, vp]),
+    "ld_dn_conv16_to16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
+    "ld_dn_conv16_from16_to16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
+    "ld_dn_gn_forward_from16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_gn_forward_from16_to16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               vp]),
+    "ld_dn_gn_backward_from16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, vp]),
     "ld_dn_pack_conv16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),

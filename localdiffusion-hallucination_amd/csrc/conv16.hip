@@ -24,6 +24,14 @@
 // threads a pixel's 32-channel chunk, and stores them with one ds_write_b128 (the weight tile's shape); the weight gradient's
 // keeps its thread map (four channels of two neighbouring pixels, now two 8-byte loads) and pairs the halves of the two
 // pixels' dwords for the same four transposed ds_write_b32.
+//
+// The _to16 entry points (conv_out_storage = "bf16") run the convolution with a bf16 OUTPUT (same NHWC shape, same pixel
+// stride in elements): loader, LDS image, MFMA order and the epilogue's fp32 arithmetic are the same code, and the value is
+// rounded to nearest even on its way out (pack_bf16x2), so the result is the fp32 kernel's, rounded.  In the 32x32x16 C/D
+// layout a lane holds one channel of 16 pixels and its neighbour lane ^ 1 the next channel of the same pixels; the two swap
+// eight values (one DPP quad_perm move each), so that the even lane holds both channels of its even rows and the odd lane
+// both channels of its odd rows, and each stores eight dwords: half the store instructions of sixteen 2-byte stores, 64
+// contiguous bytes per pixel row and half-wave parity either way.
 #include <type_traits>
 
 #include "common.hip.h"
@@ -42,7 +50,8 @@ __device__ __forceinline__ bf16x8 cv_frag(const cv_bf16 (*img)[CV_LD], int row, 
 
 // ------------------------------------------------------------------------------------------------ convolution
 // A16: a.src points at bf16 (8 per thread and chunk, one row) instead of fp32 (4 per thread and chunk, two rows)
-template <bool A16>
+// O16: a.out points at bf16; the epilogue's fp32 value is rounded to nearest even
+template <bool A16, bool O16>
 __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const cv_bf16* __restrict__ w) {
   __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [pixel][k]
   __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [output channel][k]
@@ -117,14 +126,34 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
   // C/D layout of 32x32x16: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int co = n0 + wn * 32 + c;
   const float sc = a.scale[co], t = a.shift[co];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const long p = p0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-    if (p >= M) continue;
+  auto epi = [&](int r, long p) {                     // (p < M)
     float v = acc[r] * sc + t;
     if (a.residual) v += a.residual[p * a.Cout + co];
     if (a.relu) v = fmaxf(v, 0.0f);
-    a.out[p * a.Cout + co] = v;
+    return v;
+  };
+  if constexpr (O16) {
+    // rows 2 j and 2 j + 1 are neighbouring pixels: the even lane keeps 2 j, the odd lane 2 j + 1, each gets the other's
+    // value of the row it keeps (every lane takes part in the exchange; only the loads and stores look at p < M)
+    cv_bf16* out16 = reinterpret_cast<cv_bf16*>(a.out);
+    const int odd = c & 1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long pe = p0 + wm * 32 + ((2 * j) & 3) + 8 * (j >> 1) + 4 * kh;      // row 2 j's pixel; row 2 j + 1's is pe + 1
+      const float ve = pe < M ? epi(2 * j, pe) : 0.0f, vo = pe + 1 < M ? epi(2 * j + 1, pe + 1) : 0.0f;
+      const float mine = odd ? vo : ve;
+      const float theirs = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(odd ? ve : vo), 0xB1, 0xF, 0xF, true));
+      const long p = pe + odd;
+      if (p < M)
+        *reinterpret_cast<unsigned*>(out16 + p * a.Cout + (co & ~1)) = odd ? pack_bf16x2(theirs, mine) : pack_bf16x2(mine, theirs);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long p = p0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+      if (p >= M) continue;
+      a.out[p * a.Cout + co] = epi(r, p);
+    }
   }
 }
 
@@ -240,8 +269,9 @@ __global__ void dn_pack_conv16_kernel(const float* __restrict__ w, unsigned* fwd
 }  // namespace
 
 namespace {
-// ld_dn_conv16 and ld_dn_conv16_from16: `name` is the entry point's, `a16` says what args->src points at
-int cv_conv(const char* name, bool a16, const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+// ld_dn_conv16 and its _from16 / _to16 forms: `name` is the entry point's, `a16` says what args->src points at, `o16` what
+// args->out does
+int cv_conv(const char* name, bool a16, bool o16, const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
   LD_REQUIRE(a, "%s: null args", name);
   LD_REQUIRE(a->ksize == 1 || a->ksize == 3, "%s: ksize %d (1 or 3)", name, a->ksize);
   LD_REQUIRE(a->stride == 1, "%s: stride %d (1 only)", name, a->stride);
@@ -253,17 +283,27 @@ int cv_conv(const char* name, bool a16, const ld_pc_conv_args* a, const void* we
   LD_REQUIRE(a->src && weight_bf16 && a->scale && a->shift && a->out, "%s: null pointer", name);
   LD_REQUIRE(((uintptr_t)a->src | (uintptr_t)weight_bf16) % 16 == 0, "%s: src%s and weight must be 16-byte aligned", name,
              a16 ? " (bf16)" : "");
+  if (o16) {                                          // the epilogue stores pairs of channels, and reads the residual after
+    LD_REQUIRE((uintptr_t)a->out % 4 == 0, "%s: out (bf16) must be 4-byte aligned", name);
+    LD_REQUIRE(static_cast<const void*>(a->residual) != static_cast<const void*>(a->out),
+               "%s: residual (fp32) cannot alias out (bf16)", name);
+  }
   const long M = (long)a->B * a->Ho * a->Wo;
   LD_REQUIRE((M + CV_T - 1) / CV_T < (1L << 31), "%s: %ld pixels", name, M);
   LD_REQUIRE((long)a->ksize * a->ksize * a->Cin < (1L << 31), "%s: K %ld", name, (long)a->ksize * a->ksize * a->Cin);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((M + CV_T - 1) / CV_T), (unsigned)(a->Cout / CV_T));
-  if (a16) {
-    LD_LAUNCH(dn_conv16_kernel<true>, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
+  const cv_bf16* w = reinterpret_cast<const cv_bf16*>(weight_bf16);
+  if (a16 && o16) {
+    LD_LAUNCH((dn_conv16_kernel<true, true>), grid, dim3(256), 0, st, *a, w);
+  } else if (a16) {
+    LD_LAUNCH((dn_conv16_kernel<true, false>), grid, dim3(256), 0, st, *a, w);
+  } else if (o16) {
+    LD_LAUNCH((dn_conv16_kernel<false, true>), grid, dim3(256), 0, st, *a, w);
   } else {
-    LD_LAUNCH(dn_conv16_kernel<false>, grid, dim3(256), 0, st, *a, reinterpret_cast<const cv_bf16*>(weight_bf16));
+    LD_LAUNCH((dn_conv16_kernel<false, false>), grid, dim3(256), 0, st, *a, w);
   }
-  LD_LAUNCH_CHECK(a16 ? "dn_conv16_from16" : "dn_conv16");
+  LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
 }
 
@@ -296,11 +336,19 @@ int cv_wgrad(const char* name, bool a16, const float* dy, const void* a, float* 
 }  // namespace
 
 extern "C" int ld_dn_conv16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16", false, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16", false, false, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_conv16_from16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16_from16", true, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16_from16", true, false, a, weight_bf16, stream);
+}
+
+extern "C" int ld_dn_conv16_to16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  return cv_conv("ld_dn_conv16_to16", false, true, a, weight_bf16, stream);
+}
+
+extern "C" int ld_dn_conv16_from16_to16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+  return cv_conv("ld_dn_conv16_from16_to16", true, true, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,

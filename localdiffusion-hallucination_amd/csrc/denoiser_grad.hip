@@ -17,6 +17,11 @@
 // ld_dn_gn_forward_to16 and ld_dn_pack_nhwc_to16 (act_storage = "bf16") are the same passes writing bf16: the fp32 value is
 // computed by the same code and rounded to nearest even on its way out (pack_bf16x2, what the bf16 convolutions' loaders do
 // to an fp32 activation), so a convolution that reads the result computes what it computes from the fp32 tensor.
+//
+// The _from16 entry points (conv_out_storage = "bf16") are the four GroupNorm passes on a y that is bf16 in memory (same
+// pixel stride in elements): the kernels are templates over y's type, a thread's four channels are one 8-byte load widened
+// by a shift (exact: a bf16 is the upper half of an fp32), and the thread map and every sum's order are the same, so the
+// results are bit for bit those of the fp32 kernels on y.float().
 #include <type_traits>
 
 #include "common.hip.h"
@@ -29,23 +34,32 @@ __device__ __forceinline__ void st4(bf16* p, float a, float b, float c, float d)
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
 }
 
+// four consecutive channels of y: fp32, or bf16 widened to the fp32 values they are
+__device__ __forceinline__ float4 ld4y(const float* p) { return ld4(p); }
+__device__ __forceinline__ float4 ld4y(const bf16* p) {
+  const uint2 u = *reinterpret_cast<const uint2*>(p);
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+
 __device__ __forceinline__ float dn_sigmoid(float a) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * a));
 }
 
 // ---------------------------------------------------------------- GroupNorm statistics (forward, pass 1)
-// part [B][nchunk][C][2] = (sum, sum of squares) of each channel over the run
-__global__ __launch_bounds__(DN_BS) void dn_gn_stats_kernel(const float* __restrict__ y, double* __restrict__ part, long HW,
+// part [B][nchunk][C][2] = (sum, sum of squares) of each channel over the run.  TY: float or bf16 (here and below)
+template <typename TY>
+__global__ __launch_bounds__(DN_BS) void dn_gn_stats_kernel(const TY* __restrict__ y, double* __restrict__ part, long HW,
                                                             int C, int ldc, long ppc, int nchunk) {
   __shared__ double red[DN_BS * 8];
   const DnPos t = dn_pos(C / 4, HW, ppc);
   const int b = blockIdx.z;
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (t.active) {
-    const float* src = y + ((size_t)b * HW) * ldc + 4 * t.q;
+    const TY* src = y + ((size_t)b * HW) * ldc + 4 * t.q;
 #pragma unroll 4
     for (long p = t.p0 + t.r; p < t.p1; p += t.R) {
-      const float4 x = ld4(src + (size_t)p * ldc);
+      const float4 x = ld4y(src + (size_t)p * ldc);
       const double x0 = x.x, x1 = x.y, x2 = x.z, x3 = x.w;
       v[0] += x0; v[1] = fma(x0, x0, v[1]);
       v[2] += x1; v[3] = fma(x1, x1, v[3]);
@@ -113,8 +127,8 @@ __device__ __forceinline__ DnCoef dn_coef(const float* stat, const float* gamma,
 
 // ---------------------------------------------------------------- forward, pass 2: out = silu(a) (+ residual)
 // TO: float, or bf16 (out has the same pixel stride in elements)
-template <typename TO>
-__global__ __launch_bounds__(DN_BS) void dn_gn_apply_kernel(const float* __restrict__ y, const float* __restrict__ stat,
+template <typename TY, typename TO>
+__global__ __launch_bounds__(DN_BS) void dn_gn_apply_kernel(const TY* __restrict__ y, const float* __restrict__ stat,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ film, const float* residual, TO* out,
                                                             long HW, int C, int ldc, int G, long ppc) {
@@ -129,7 +143,7 @@ __global__ __launch_bounds__(DN_BS) void dn_gn_apply_kernel(const float* __restr
   const DnCoef k = dn_coef(stat, gamma, beta, film, b, c0, C, G);
   for (long p = t.p0 + t.r; p < t.p1; p += t.R) {
     const size_t at = base + (size_t)p * ldc;
-    const float4 x = ld4(y + at);
+    const float4 x = ld4y(y + at);
     float4 rs = make_float4(0.f, 0.f, 0.f, 0.f);
     if (residual) rs = ld4(residual + at);
     const float xv[4] = {x.x, x.y, x.z, x.w}, rv[4] = {rs.x, rs.y, rs.z, rs.w};
@@ -148,7 +162,8 @@ __device__ __forceinline__ float dn_da(float dout, float a) {
   const float s = dn_sigmoid(a);
   return dout * s * (1.0f + a * (1.0f - s));
 }
-__global__ __launch_bounds__(DN_BS) void dn_gn_bwd_sums_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+template <typename TY>
+__global__ __launch_bounds__(DN_BS) void dn_gn_bwd_sums_kernel(const float* __restrict__ dout, const TY* __restrict__ y,
                                                                const float* __restrict__ stat, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ film,
                                                                double* __restrict__ part, long HW, int C, int ldc, int G,
@@ -163,7 +178,7 @@ __global__ __launch_bounds__(DN_BS) void dn_gn_bwd_sums_kernel(const float* __re
 #pragma unroll 4
     for (long p = t.p0 + t.r; p < t.p1; p += t.R) {
       const size_t at = base + (size_t)p * ldc;
-      const float4 x = ld4(y + at), d = ld4(dout + at);
+      const float4 x = ld4y(y + at), d = ld4(dout + at);
       const float xv[4] = {x.x, x.y, x.z, x.w}, dv[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -220,7 +235,8 @@ __global__ __launch_bounds__(256) void dn_gn_bwd_final_kernel(const double* __re
 
 // ---------------------------------------------------------------- backward, pass 2: dy = rstd (gamma (1 + s) da - m1 - y^ m2)
 // The workgroups of run 0 of sample 0 also add S over the batch, in order: dbeta, dgamma.  dy may be dout.
-__global__ __launch_bounds__(DN_BS) void dn_gn_dy_kernel(const float* dout, const float* __restrict__ y,
+template <typename TY>
+__global__ __launch_bounds__(DN_BS) void dn_gn_dy_kernel(const float* dout, const TY* __restrict__ y,
                                                          const float* __restrict__ stat, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, const float* __restrict__ film,
                                                          const double* __restrict__ S, const double* __restrict__ m,
@@ -254,7 +270,7 @@ __global__ __launch_bounds__(DN_BS) void dn_gn_dy_kernel(const float* dout, cons
   for (int i = 0; i < 4; ++i) kd[i] = k.rstd * k.g[i] * k.s1[i];
   for (long p = t.p0 + t.r; p < t.p1; p += t.R) {
     const size_t at = base + (size_t)p * ldc;
-    const float4 x = ld4(y + at), d = ld4(dout + at);
+    const float4 x = ld4y(y + at), d = ld4(dout + at);
     const float xv[4] = {x.x, x.y, x.z, x.w}, dv[4] = {d.x, d.y, d.z, d.w};
     float o[4];
 #pragma unroll
@@ -452,9 +468,9 @@ extern "C" int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C) {
 }
 
 namespace {
-// ld_dn_gn_forward (TO = float) and ld_dn_gn_forward_to16 (TO = bf16)
-template <typename TO>
-int dn_gn_forward(const char* name, const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
+// ld_dn_gn_forward (TY = TO = float), ld_dn_gn_forward_to16 (TO = bf16) and the two _from16 forms (TY = bf16)
+template <typename TY, typename TO>
+int dn_gn_forward(const char* name, const TY* y, const float* gamma, const float* beta, const float* film, const float* residual,
                   double* work, float* stat, TO* out, int B, int H, int W, int C, int ldc, int groups, void* stream) {
   LD_REQUIRE(dn_gn_shape_ok(B, H, W, C, ldc, groups),
              "%s: B=%d H=%d W=%d C=%d ldc=%d groups=%d (C a multiple of 4 * groups, ldc >= C a multiple of 4)", name, B, H, W, C,
@@ -469,14 +485,14 @@ int dn_gn_forward(const char* name, const float* y, const float* gamma, const fl
   long ppc;
   int nchunk;
   dn_runs(B, HW, C / 4, ppc, nchunk);
-  LD_LAUNCH(dn_gn_stats_kernel, dim3((unsigned)nchunk, (unsigned)((C / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS), 0,
+  LD_LAUNCH(dn_gn_stats_kernel<TY>, dim3((unsigned)nchunk, (unsigned)((C / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS), 0,
             st, y, work, HW, C, ldc, ppc, nchunk);
   LD_LAUNCH(dn_gn_stats_final_kernel, dim3((unsigned)B), dim3(256), 2 * (size_t)C * sizeof(double), st, (const double*)work, stat,
             nchunk, C, groups, HW);
   long ppa;
   int na;
   dn_runs(B, HW, ldc / 4, ppa, na);
-  LD_LAUNCH(dn_gn_apply_kernel<TO>, dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS),
+  LD_LAUNCH((dn_gn_apply_kernel<TY, TO>), dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS),
             0, st, y, (const float*)stat, gamma, beta, film, residual, out, HW, C, ldc, groups, ppa);
   LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
@@ -486,26 +502,43 @@ int dn_gn_forward(const char* name, const float* y, const float* gamma, const fl
 extern "C" int ld_dn_gn_forward(const float* y, const float* gamma, const float* beta, const float* film, const float* residual,
                                 double* work, float* stat, float* out, int B, int H, int W, int C, int ldc, int groups,
                                 void* stream) {
-  return dn_gn_forward<float>("ld_dn_gn_forward", y, gamma, beta, film, residual, work, stat, out, B, H, W, C, ldc, groups, stream);
+  return dn_gn_forward<float, float>("ld_dn_gn_forward", y, gamma, beta, film, residual, work, stat, out, B, H, W, C, ldc, groups, stream);
 }
 
 extern "C" int ld_dn_gn_forward_to16(const float* y, const float* gamma, const float* beta, const float* film,
                                      const float* residual, double* work, float* stat, void* out_bf16, int B, int H, int W, int C,
                                      int ldc, int groups, void* stream) {
-  return dn_gn_forward<bf16>("ld_dn_gn_forward_to16", y, gamma, beta, film, residual, work, stat, static_cast<bf16*>(out_bf16), B, H,
-                             W, C, ldc, groups, stream);
+  return dn_gn_forward<float, bf16>("ld_dn_gn_forward_to16", y, gamma, beta, film, residual, work, stat,
+                                    static_cast<bf16*>(out_bf16), B, H, W, C, ldc, groups, stream);
 }
 
-extern "C" int ld_dn_gn_backward(const float* dout, const float* y, const float* stat, const float* gamma, const float* beta,
-                                 const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B,
-                                 int H, int W, int C, int ldc, int groups, void* stream) {
+extern "C" int ld_dn_gn_forward_from16(const void* y_bf16, const float* gamma, const float* beta, const float* film,
+                                       const float* residual, double* work, float* stat, float* out, int B, int H, int W, int C,
+                                       int ldc, int groups, void* stream) {
+  return dn_gn_forward<bf16, float>("ld_dn_gn_forward_from16", static_cast<const bf16*>(y_bf16), gamma, beta, film, residual, work,
+                                    stat, out, B, H, W, C, ldc, groups, stream);
+}
+
+extern "C" int ld_dn_gn_forward_from16_to16(const void* y_bf16, const float* gamma, const float* beta, const float* film,
+                                            const float* residual, double* work, float* stat, void* out_bf16, int B, int H, int W,
+                                            int C, int ldc, int groups, void* stream) {
+  return dn_gn_forward<bf16, bf16>("ld_dn_gn_forward_from16_to16", static_cast<const bf16*>(y_bf16), gamma, beta, film, residual,
+                                   work, stat, static_cast<bf16*>(out_bf16), B, H, W, C, ldc, groups, stream);
+}
+
+namespace {
+// ld_dn_gn_backward (TY = float) and ld_dn_gn_backward_from16 (TY = bf16)
+template <typename TY>
+int dn_gn_backward(const char* name, const float* dout, const TY* y, const float* stat, const float* gamma, const float* beta,
+                   const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B, int H, int W, int C,
+                   int ldc, int groups, void* stream) {
   LD_REQUIRE(dn_gn_shape_ok(B, H, W, C, ldc, groups),
-             "ld_dn_gn_backward: B=%d H=%d W=%d C=%d ldc=%d groups=%d (C a multiple of 4 * groups, ldc >= C a multiple of 4)", B,
-             H, W, C, ldc, groups);
-  LD_REQUIRE(dout && y && stat && gamma && beta && work && dgamma && dbeta && dy, "ld_dn_gn_backward: null pointer");
-  LD_REQUIRE((film == nullptr) == (dfilm == nullptr), "ld_dn_gn_backward: film and dfilm go together");
+             "%s: B=%d H=%d W=%d C=%d ldc=%d groups=%d (C a multiple of 4 * groups, ldc >= C a multiple of 4)", name, B, H, W, C,
+             ldc, groups);
+  LD_REQUIRE(dout && y && stat && gamma && beta && work && dgamma && dbeta && dy, "%s: null pointer", name);
+  LD_REQUIRE((film == nullptr) == (dfilm == nullptr), "%s: film and dfilm go together", name);
   LD_REQUIRE(dn_aligned16(dout) && dn_aligned16(y) && dn_aligned16(gamma) && dn_aligned16(beta) && dn_aligned16(film) &&
-                 dn_aligned16(dy), "ld_dn_gn_backward: a pointer is not 16-byte aligned");
+                 dn_aligned16(dy), "%s: a pointer is not 16-byte aligned", name);
   const long HW = (long)H * W;
   hipStream_t st = dn_st(stream);
   long ppc;
@@ -513,17 +546,32 @@ extern "C" int ld_dn_gn_backward(const float* dout, const float* y, const float*
   dn_runs(B, HW, C / 4, ppc, nchunk);
   double* S = work + (size_t)B * nchunk * C * 2;
   double* m = S + (size_t)B * C * 2;
-  LD_LAUNCH(dn_gn_bwd_sums_kernel, dim3((unsigned)nchunk, (unsigned)((C / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS),
+  LD_LAUNCH(dn_gn_bwd_sums_kernel<TY>, dim3((unsigned)nchunk, (unsigned)((C / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS),
             0, st, dout, y, stat, gamma, beta, film, work, HW, C, ldc, groups, ppc, nchunk);
   LD_LAUNCH(dn_gn_bwd_final_kernel, dim3((unsigned)B), dim3(256), 2 * (size_t)C * sizeof(double), st, (const double*)work, gamma,
             beta, film, dfilm, S, m, nchunk, C, groups, HW);
   long ppa;
   int na;
   dn_runs(B, HW, ldc / 4, ppa, na);
-  LD_LAUNCH(dn_gn_dy_kernel, dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS), 0, st,
+  LD_LAUNCH(dn_gn_dy_kernel<TY>, dim3((unsigned)na, (unsigned)((ldc / 4 + DN_LANES - 1) / DN_LANES), (unsigned)B), dim3(DN_BS), 0, st,
             dout, y, stat, gamma, beta, film, (const double*)S, (const double*)m, dgamma, dbeta, dy, B, HW, C, ldc, groups, ppa);
-  LD_LAUNCH_CHECK("dn_gn_backward");
+  LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
+}
+}  // namespace
+
+extern "C" int ld_dn_gn_backward(const float* dout, const float* y, const float* stat, const float* gamma, const float* beta,
+                                 const float* film, double* work, float* dgamma, float* dbeta, float* dfilm, float* dy, int B,
+                                 int H, int W, int C, int ldc, int groups, void* stream) {
+  return dn_gn_backward<float>("ld_dn_gn_backward", dout, y, stat, gamma, beta, film, work, dgamma, dbeta, dfilm, dy, B, H, W, C, ldc,
+                               groups, stream);
+}
+
+extern "C" int ld_dn_gn_backward_from16(const float* dout, const void* y_bf16, const float* stat, const float* gamma,
+                                        const float* beta, const float* film, double* work, float* dgamma, float* dbeta,
+                                        float* dfilm, float* dy, int B, int H, int W, int C, int ldc, int groups, void* stream) {
+  return dn_gn_backward<bf16>("ld_dn_gn_backward_from16", dout, static_cast<const bf16*>(y_bf16), stat, gamma, beta, film, work,
+                              dgamma, dbeta, dfilm, dy, B, H, W, C, ldc, groups, stream);
 }
 
 extern "C" int ld_dn_colsum(const float* x, double* work, float* out, int B, int H, int W, int C, int ldc, void* stream) {

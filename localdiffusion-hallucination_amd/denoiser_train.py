@@ -42,7 +42,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import SWITCHES, check_act_storage_precision, check_switch, stream
+from .trainable import SWITCHES, check_storage_precision, check_switch, stream
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -152,6 +152,12 @@ class DenoiserTrainer:
     that only convolutions read as bf16 (``TrainableUnet.act_storage``): less memory and traffic, the same bits in the loss,
     every gradient and every parameter -- so a data-parallel run needs nothing new and a checkpoint does not record it either.
 
+    ``conv_out_storage="bf16"`` (default ``"fp32"``; with ``conv_precision="bf16"`` only, refused otherwise; independent of
+    ``act_storage``) keeps the convolution outputs that a ``ResnetBlock``'s GroupNorms read as bf16
+    (``TrainableUnet.conv_out_storage``).  This one rounds values that were not rounded before, so the loss and the gradients
+    move, by about what the bf16 convolutions move them; the backward is the exact gradient of the rounded forward, the step
+    stays reproducible bit for bit, data-parallel replicas stay identical, and a checkpoint does not record it.
+
     ``attn_precision="bf16"`` (default ``"fp32"``; independent of ``conv_precision``) runs the attention cores of the online
     model's ``LinearAttention`` modules on the bf16 matrix cores (``TrainableUnet.attn_precision``): operands of the 32 x 32
     products rounded to bf16, fp32 accumulation, every sum in a fixed order, so the step stays reproducible bit for bit and
@@ -167,12 +173,14 @@ class DenoiserTrainer:
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
-                 conv_precision="fp32", act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
-        switches = dict(conv_precision=conv_precision, act_storage=act_storage, attn_precision=attn_precision,
-                        full_attn_precision=full_attn_precision)
+                 conv_precision="fp32", act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32",
+                 full_attn_precision="fp32"):
+        switches = dict(conv_precision=conv_precision, act_storage=act_storage, conv_out_storage=conv_out_storage,
+                        attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         for switch in SWITCHES:
             check_switch("DenoiserTrainer", switch, switches[switch])
-        check_act_storage_precision("DenoiserTrainer", act_storage, conv_precision)
+        for switch in ("act_storage", "conv_out_storage"):
+            check_storage_precision("DenoiserTrainer", switch, switches[switch], conv_precision)
         if group is not None and comm is not None:
             raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
         model = getattr(diffusion, "model", None)

@@ -21,14 +21,14 @@ the input checks are ``trainable.py``'s, shared with the two attention modules.
 NOT covered (follow-ups that build on this module's layout; linear attention and RMSNorm are in ``linattn_grad.py``, full
 attention is in ``attention_grad.py``, Down/Upsample, the 7x7 stem, the head and the plain 3x3 are in ``resample.py``, the
 ResUnet condition encoder is in ``condenc.py``, the time MLP in front of the blocks and ``TrainableUnet`` assembling the
-backward of its blocks are in ``unet_grad.py``): 16-bit storage beyond ``act_storage``'s conv-only activations (the
-convolution outputs ``y1`` / ``y2``, gradients).
+backward of its blocks are in ``unet_grad.py``): 16-bit storage beyond ``act_storage``'s conv-only activations and
+``conv_out_storage``'s convolution outputs ``y1`` / ``y2`` (gradients, the result).
 """
 import torch
 from torch import nn
 
 from . import _cabi as cabi
-from .trainable import Run, TrainableModule, check_act_storage_precision, ones_zeros, pack_conv, pack_vec, pad64, stream
+from .trainable import Run, TrainableModule, check_storage_precision, ones_zeros, pack_conv, pack_vec, pad64, stream
 
 
 class _Block(nn.Module):
@@ -69,8 +69,8 @@ class _Run(Run):
         blk = self.mod
         stat = self.empty(self.B, blk.groups, 2)
         out = self.empty(self.B, self.H, self.W, blk.cop, dtype=dtype) if out is None else out
-        to16 = out.dtype == torch.bfloat16
-        fn, what = (self.lib.ld_dn_gn_forward_to16, "dn_gn_forward_to16") if to16 else (self.lib.ld_dn_gn_forward, "dn_gn_forward")
+        what = "dn_gn_forward" + ("_from16" if y.dtype == torch.bfloat16 else "") + ("_to16" if out.dtype == torch.bfloat16 else "")
+        fn = getattr(self.lib, "ld_" + what)
         cabi.check(fn(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), cabi.ptr(film), cabi.ptr(residual), self.gn_work().data_ptr(),
                       stat.data_ptr(), out.data_ptr(), self.B, self.H, self.W, blk.dim_out, blk.cop, blk.groups, self.st), what)
         return out, stat
@@ -79,10 +79,11 @@ class _Run(Run):
         blk = self.mod
         dg, db = self.empty(blk.dim_out), self.empty(blk.dim_out)
         dfilm = None if film is None else self.empty(self.B, 2 * blk.dim_out)
-        cabi.check(self.lib.ld_dn_gn_backward(dout.data_ptr(), y.data_ptr(), stat.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                              cabi.ptr(film), self.gn_work().data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                              cabi.ptr(dfilm), dy.data_ptr(), self.B, self.H, self.W, blk.dim_out, blk.cop,
-                                              blk.groups, self.st), "dn_gn_backward")
+        what = "dn_gn_backward" + ("_from16" if y.dtype == torch.bfloat16 else "")
+        cabi.check(getattr(self.lib, "ld_" + what)(dout.data_ptr(), y.data_ptr(), stat.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                   cabi.ptr(film), self.gn_work().data_ptr(), dg.data_ptr(), db.data_ptr(),
+                                                   cabi.ptr(dfilm), dy.data_ptr(), self.B, self.H, self.W, blk.dim_out, blk.cop,
+                                                   blk.groups, self.st), what)
         return dg, db, dfilm
 
     # ------------------------------------------------------------------------------------------------ the two halves
@@ -92,6 +93,9 @@ class _Run(Run):
         # act_storage "bf16": what only the convolutions read is bf16 -- h1 always; the block's own copy of x where a res_conv
         # reads it (without one it is also the fp32 residual of the second GroupNorm; an x read in place is no copy)
         a16 = torch.bfloat16 if self.act16 else torch.float32
+        # conv_out_storage "bf16": y1 and y2, which the GroupNorm launches (forward and backward) read, are bf16 -- written
+        # rounded by their convolutions; res_conv's output, the second GroupNorm's residual and output buffer, stays fp32
+        y16 = torch.bfloat16 if self.y16 else torch.float32
         xp = self.nhwc(x, ci, cip, dtype=a16 if blk.has_res_conv else torch.float32)
         film = None
         if temb is not None:
@@ -100,9 +104,9 @@ class _Run(Run):
             film = self.empty(self.B, 2 * co)
             cabi.check(lib.ld_dn_time_proj(temb.data_ptr(), w.data_ptr(), b.data_ptr(), film.data_ptr(), self.B, temb.shape[1],
                                            2 * co, self.st), "dn_time_proj")
-        y1 = self.conv(xp, p.w1f, p.b1, cip, cop, 3)
+        y1 = self.conv(xp, p.w1f, p.b1, cip, cop, 3, out_dtype=y16)
         h1, stat1 = self.gn_forward(y1, p.g1, p.be1, film, None, dtype=a16)
-        y2 = self.conv(h1, p.w2f, p.b2, cop, cop, 3)
+        y2 = self.conv(h1, p.w2f, p.b2, cop, cop, 3, out_dtype=y16)
         res = self.conv(xp, p.wrf, p.br, cip, cop, 1) if blk.has_res_conv else xp
         out, stat2 = self.gn_forward(y2, p.g2, p.be2, None, res, out=res if blk.has_res_conv else None)
         return out, (xp, y1, y2, stat1, stat2, h1, film, temb)
@@ -147,10 +151,18 @@ class ResnetBlock(TrainableModule):
     ``act_storage = "bf16"`` (with ``conv_precision = "bf16"``; refused with ``ValueError`` otherwise): block1's GroupNorm ->
     FiLM -> SiLU output, and the block's padded NHWC copy of ``x`` when it has a ``res_conv`` and makes one, are written, read
     and saved for the backward as bf16 -- what every convolution that reads them rounds them to anyway, so the output and
-    every gradient keep their bits.  The convolution outputs, the statistics, all gradients and the result stay fp32."""
+    every gradient keep their bits.
+
+    ``conv_out_storage = "bf16"`` (with ``conv_precision = "bf16"`` as well, independent of ``act_storage``): the outputs
+    ``y1`` / ``y2`` of the two 3x3 convolutions are written as bf16 -- the fp32 epilogue value rounded to nearest even --, and
+    GroupNorm's statistics, its apply pass and both passes of its backward read that tensor, which is also what autograd keeps.
+    The backward is the exact gradient of the forward that was computed (it uses the stored ``y``; the rounding is passed
+    through as the identity), so the output and the gradients move by about what the bf16 convolutions move them, and a
+    step stays reproducible bit for bit.  ``res_conv``'s output, the statistics, all gradients and the result stay fp32."""
 
     Run = _Run
     ACT_STORAGES = ("fp32", "bf16")
+    CONV_OUT_STORAGES = ("fp32", "bf16")
 
     def __init__(self, dim, dim_out, *, time_emb_dim=None, groups=8):
         super().__init__()
@@ -178,5 +190,6 @@ class ResnetBlock(TrainableModule):
                 raise ValueError(f"ResnetBlock: time_emb must be float32 [{x.shape[0]}, {self.time_emb_dim}] on {x.device}")
 
     def forward(self, x, time_emb=None):
-        check_act_storage_precision("ResnetBlock", self.act_storage, self.conv_precision)
+        for switch in ("act_storage", "conv_out_storage"):
+            check_storage_precision("ResnetBlock", switch, getattr(self, switch), self.conv_precision)
         return super().forward(x, time_emb)

@@ -2,8 +2,8 @@
 (``linattn_grad.py``), ``Attention`` (``attention_grad.py``) and ``Downsample`` / ``Upsample`` / ``Conv2d`` (``resample.py``)
 are each a ``TrainableModule`` with a ``Run`` of their own.
 
-The common layout: activations are fp32 NHWC with a pixel stride of ``pad64(channels)`` floats, the upper part zero; the
-kernel-layout copies of the weights (``pack_conv``, ``pack_vec``) are zero there too and are cached per device, keyed on every
+The common layout: activations are fp32 NHWC (bf16 where a storage switch below says so) with a pixel stride of
+``pad64(channels)`` elements, the upper part zero; the kernel-layout copies of the weights (``pack_conv``, ``pack_vec``) are zero there too and are cached per device, keyed on every
 parameter's ``data_ptr`` and ``_version`` (``PackedWeights``).  A module's forward and backward are the two halves of one
 ``autograd.Function``; each half is a sequence of launches that the module's ``Run`` subclass writes down, out of the launches
 every module uses (``Run``: buffers, the NHWC repack, ``ld_pc_conv``, the weight and bias gradients) and its own.
@@ -20,6 +20,11 @@ more than one, and ``DenoiserTrainer`` passes it through.
                            (``Run.nhwc(dtype=)``, a producer's ``_to16`` launch; ``Run.conv`` and ``Run.wgrad_packed`` pick the
                            ``_from16`` entry point from the dtype they are handed).  Needs ``conv_precision = "bf16"``, whose
                            launches round such a tensor anyway, so no bit of any result changes (``check_act_storage_precision``).
+  ``conv_out_storage``     ``ResnetBlock`` only so far: the outputs ``y1`` / ``y2`` of its two 3x3 convolutions, which GroupNorm reads
+                           four times each, are written (``Run.conv(out_dtype=)``: a ``_to16`` launch rounds the fp32 epilogue
+                           value to nearest even), read and saved as bf16; the backward is the exact gradient of that forward, the
+                           rounding passed through as the identity.  Needs ``conv_precision = "bf16"`` (``check_storage_precision``).
+                           Unlike ``act_storage`` it moves results, by about what the bf16 convolutions themselves do.
   ``attn_precision``       ``LinearAttention``: the four passes of its core on ``csrc/linattn16.hip`` (a placeholder on ``Attention``).
   ``full_attn_precision``  ``Attention``: the three passes of its core on ``csrc/attention16.hip``.
 """
@@ -67,8 +72,8 @@ class PackedWeights:
 
 # ---------------------------------------------------------------------------------------------------- packing
 # switch -> the class attribute that lists the values a module implements (the module docstring)
-SWITCHES = {"conv_precision": "CONV_PRECISIONS", "act_storage": "ACT_STORAGES", "attn_precision": "ATTN_PRECISIONS",
-            "full_attn_precision": "FULL_ATTN_PRECISIONS"}
+SWITCHES = {"conv_precision": "CONV_PRECISIONS", "act_storage": "ACT_STORAGES", "conv_out_storage": "CONV_OUT_STORAGES",
+            "attn_precision": "ATTN_PRECISIONS", "full_attn_precision": "FULL_ATTN_PRECISIONS"}
 
 
 def check_switch(owner, switch, value, allowed=("fp32", "bf16")):
@@ -82,11 +87,22 @@ def check_act_storage(name, value, allowed=("fp32", "bf16")):
     return check_switch(name, "act_storage", value, allowed)
 
 
+_WHY_BF16_CONVS = {
+    "act_storage": "the fp32 convolutions do not round their activations: the rounding would change results",
+    "conv_out_storage": "only the bf16 convolutions have a launch that writes a bf16 output",
+}
+
+
+def check_storage_precision(name, switch, storage, conv_precision):
+    """The two storage switches (``act_storage``, ``conv_out_storage``) are built on the bf16 convolutions only."""
+    if storage == "bf16" and conv_precision != "bf16":
+        raise ValueError(f"{name}: {switch} 'bf16' needs conv_precision 'bf16' ({_WHY_BF16_CONVS[switch]})")
+
+
 def check_act_storage_precision(name, act_storage, conv_precision):
-    """bf16 storage of the conv-only activations is exact only where the convolutions round them to bf16 anyway."""
-    if act_storage == "bf16" and conv_precision != "bf16":
-        raise ValueError(f"{name}: act_storage 'bf16' needs conv_precision 'bf16' (the fp32 convolutions do not round their "
-                         "activations: the rounding would change results)")
+    """bf16 storage of the conv-only activations is exact only where the convolutions round them to bf16 anyway
+    (``check_storage_precision`` under the earlier name that ``tests/test_act_storage.py`` imports)."""
+    check_storage_precision(name, "act_storage", act_storage, conv_precision)
 
 
 def pack_conv(lib, st, w, co, cop, ci, cip, k, precision="fp32"):
@@ -136,6 +152,7 @@ class Run:
         self.fill = mod.debug_fill
         self.bf16 = getattr(mod, "conv_precision", "fp32") == "bf16"      # (the precision ``packed`` was made at)
         self.act16 = getattr(mod, "act_storage", "fp32") == "bf16"        # conv-only activations are kept as bf16
+        self.y16 = getattr(mod, "conv_out_storage", "fp32") == "bf16"     # the convolution outputs GroupNorm reads, too
 
     def empty(self, *shape, dtype=torch.float32):
         t = torch.empty(*shape, dtype=dtype, device=self.dev)
@@ -175,9 +192,15 @@ class Run:
                                "convolutions read 16-bit storage)")
         return True
 
-    def conv(self, src, weight, shift, cin, cout, k, residual=None, hw=None):
+    def conv(self, src, weight, shift, cin, cout, k, residual=None, hw=None, out_dtype=torch.float32):
+        """``out_dtype``: ``torch.bfloat16`` for an output that is stored rounded (the ``_to16`` entry points; bf16
+        convolutions only)."""
         H, W = self.hw(hw)
-        out = self.empty(self.B, H, W, cout)
+        to16 = out_dtype == torch.bfloat16
+        if to16 and not self.bf16:
+            raise RuntimeError(f"{type(self.mod).__name__}: a bfloat16 convolution output at conv_precision 'fp32' (only the "
+                               "bf16 convolutions write 16-bit storage)")
+        out = self.empty(self.B, H, W, cout, dtype=out_dtype)
         a = cabi.PcConvArgs()
         a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
         a.residual, a.out = cabi.ptr(residual), out.data_ptr()
@@ -185,12 +208,10 @@ class Run:
         if (weight.dtype == torch.bfloat16) != self.bf16:
             raise RuntimeError(f"{type(self.mod).__name__}: a {weight.dtype} kernel-layout weight at conv_precision "
                                f"{'bf16' if self.bf16 else 'fp32'} (the module's _pack does not pass the precision on)")
-        if self.from16(src):
+        if self.from16(src) or self.bf16:
+            what = "dn_conv16" + ("_from16" if src.dtype == torch.bfloat16 else "") + ("_to16" if to16 else "")
             a.weight = None
-            cabi.check(self.lib.ld_dn_conv16_from16(C.byref(a), weight.data_ptr(), self.st), "dn_conv16_from16")
-        elif self.bf16:
-            a.weight = None
-            cabi.check(self.lib.ld_dn_conv16(C.byref(a), weight.data_ptr(), self.st), "dn_conv16")
+            cabi.check(getattr(self.lib, "ld_" + what)(C.byref(a), weight.data_ptr(), self.st), what)
         else:
             cabi.check(self.lib.ld_pc_conv(C.byref(a), self.st), "pc_conv")
         return out
@@ -264,8 +285,11 @@ class TrainableModule(PackedWeights, nn.Module):
     #                          multiplied on the bf16 matrix cores with fp32 accumulation; everything else stays fp32
     act_storage = "fp32"     # or "bf16" where the module has it (ACT_STORAGES): the activations that only its convolutions read
     #                          are written, read and saved as bf16; at conv_precision "bf16" only, where no result changes
+    conv_out_storage = "fp32"  # or "bf16" where the module has it (CONV_OUT_STORAGES): the convolution outputs that GroupNorm
+    #                            reads are written rounded to bf16, read and saved as that; at conv_precision "bf16" only
     CONV_PRECISIONS = ("fp32", "bf16")
     ACT_STORAGES = ("fp32",)
+    CONV_OUT_STORAGES = ("fp32",)
     Run = None
 
     def __setattr__(self, name, value):

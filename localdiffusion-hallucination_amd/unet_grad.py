@@ -20,7 +20,7 @@ The modules still exchange [B, C, H, W] views (``Run.nhwc``'s contract): where a
 (32 and 96 channels) the next module repacks it (``ld_dn_pack_nhwc``).
 
 The fused clipped-Adam / EMA step and the trainer around this module are ``denoiser_train.py`` (``torch.optim.Adam`` trains
-it as it is, too).  NOT covered: 16-bit storage.
+it as it is, too).  NOT covered: 16-bit storage outside the ``ResnetBlock``s (``act_storage``, ``conv_out_storage``).
 """
 import math
 
@@ -177,7 +177,8 @@ def _check_join(name, a, other):
 def _switch(name, doc):
     """``TrainableUnet``'s property for a switch of ``trainable.SWITCHES``: the setter checks the value, stores it and hands it
     to every sub-module whose class lists more than one value for the switch.  A refused value changes nothing, and no
-    switch touches another: none needs another but ``act_storage`` (``check_act_storage_precision``, at the block's call)."""
+    switch touches another: none needs another but the two storage switches (``check_storage_precision``, at the block's
+    call)."""
     def get(self):
         return getattr(self, "_" + name)
 
@@ -205,10 +206,10 @@ class TrainableUnet(nn.Module):
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
-                 act_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
+                 act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
         super().__init__()
-        switches = dict(conv_precision=conv_precision, act_storage=act_storage, attn_precision=attn_precision,
-                     full_attn_precision=full_attn_precision)
+        switches = dict(conv_precision=conv_precision, act_storage=act_storage, conv_out_storage=conv_out_storage,
+                        attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         for switch in SWITCHES:
             check_switch("TrainableUnet", switch, switches[switch])
         for flag, what in ((self_condition, "self_condition"), (learned_variance, "learned_variance"),
@@ -294,6 +295,10 @@ class TrainableUnet(nn.Module):
     act_storage = _switch("act_storage", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``ResnetBlock`` keeps the activations
         that only its convolutions read as bf16 (``ResnetBlock``); that needs ``conv_precision = "bf16"``, where it changes no
         bit of any result.  The other modules have no such storage yet and stay fp32.""")
+    conv_out_storage = _switch("conv_out_storage", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``ResnetBlock`` writes the
+        outputs of its two 3x3 convolutions rounded to bf16, and its GroupNorms read and autograd keeps that tensor
+        (``ResnetBlock``); that needs ``conv_precision = "bf16"`` and, unlike ``act_storage``, moves results.  The other modules
+        have no such storage and stay fp32.""")
     attn_precision = _switch("attn_precision", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every ``LinearAttention`` runs the four
         passes of its attention core on the bf16 matrix cores (``LinearAttention.attn_precision``).  The full ``Attention``
         modules have a switch of their own (``full_attn_precision``) and are not touched.""")

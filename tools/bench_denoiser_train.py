@@ -7,6 +7,7 @@ default mode and a per-tensor ``lerp_`` EMA.  fp32, ms per step.
   python tools/bench_denoiser_train.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300]
                                        [--conv-precision fp32|bf16]   (the HIP trainer's convolutions; eager stays fp32)
                                        [--act-storage fp32|bf16]      (bf16 storage of conv-only activations; peak_mb shows it)
+                                       [--conv-out-storage fp32|bf16] (bf16 storage of the convolution outputs GroupNorm reads)
 A case is data:H = W:batch; the default cases are those of tools/bench_unet_grad.py (cfg3 = mvtec 3 x 256^2 B = 8, mri 256^2
 B = 8, mnist 28^2 B = 64).  Every case runs in a child process of its own under ``--timeout``, and the first case that fails
 or runs out of time ends the run.  Per case: 3 warm-up steps, then the median of 20.  The EMA lerps at every step on both
@@ -105,7 +106,7 @@ def report(r):
     if r["eager_ms"] is not None:
         eg = (f"; eager PyTorch step {r['eager_ms']:9.3f} ms ({r['eager_over_hip']:.2f} x), clip + Adam + EMA "
               f"{r['eager_opt_ms']:8.3f} ms ({r['eager_opt_over_hip']:.1f} x)")
-    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / attn {r['attn_precision']} / full attn {r['full_attn_precision']}: HIP step {r['hip_ms']:9.3f} ms, peak "
+    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']} / attn {r['attn_precision']} / full attn {r['full_attn_precision']}: HIP step {r['hip_ms']:9.3f} ms, peak "
           f"{r['peak_mb']:8.1f} MiB, apply() {r['hip_opt_ms']:7.3f} ms (its 3 "
           f"launches {1e3 * r['hip_opt_kernels_ms']:6.1f} us) over {r['tensors']} tensors / {r['params'] / 1e6:.1f} M floats = "
           f"{r['opt_gbs']:7.1f} GB/s ({100 * r['opt_gbs'] / grad_bench.HBM_PEAK_GBS:.1f} % of {grad_bench.HBM_PEAK_GBS:.0f}){eg}")

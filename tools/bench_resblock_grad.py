@@ -4,6 +4,7 @@ restated in eager PyTorch (autograd, MIOpen convolutions) on the same GPU in one
 
   python tools/bench_resblock_grad.py [--batch 8] [--iters 20] [--warmup 3] [--cases 32:256,64:128,128:64,256:32]
                                       [--timeout 300] [--conv-precision fp32|bf16] [--act-storage fp32|bf16]
+                                      [--conv-out-storage fp32|bf16]
 The default cases are cfg3's four levels (dim -> dim at H = W).  Every case runs in a child process of its own under a time
 limit (``--timeout`` seconds; the HIP and the eager block share that process), and the first case that fails or runs out of
 time ends the run: nothing more is started on the GPU after it.  Per case: 3 warm-up calls, then the median of 20 calls
@@ -42,11 +43,12 @@ def eager_block(p, x, temb, groups=8):
     return h + x
 
 
-def gn_bytes(dim, B, H):
-    """two GroupNorms x (dout and y read by each of the two passes: the real channels; dy written: the padded pixel)"""
-    return 2 * (4 * dim + (dim + 63) // 64 * 64) * B * H * H * 4
+def gn_bytes(dim, B, H, y_bytes=4):
+    """two GroupNorms x (dout and y read by each of the two passes: the real channels; dy written: the padded pixel); y has
+    ``y_bytes`` bytes per element (2 at ``--conv-out-storage bf16``)"""
+    return 2 * ((2 * 4 + 2 * y_bytes) * dim + (dim + 63) // 64 * 64 * 4) * B * H * H
 
-SWITCHES = ("conv_precision", "act_storage")
+SWITCHES = ("conv_precision", "act_storage", "conv_out_storage")
 
 
 def run_case(dim, H, a):
@@ -72,13 +74,16 @@ def run_case(dim, H, a):
     hip = grad_bench.time_ms(hip_step, a.iters, a.warmup)
     split, calls = grad_bench.kernel_split(hip_step)
     # the three launches of ld_dn_gn_backward are sums, finalisation, dy: the two passes are the first and the last
-    gn_pass_ms = sum((ms[0] + ms[2] for label, ms in calls if label == "dn_gn_backward" and len(ms) == 3), 0.0)
+    gn_pass_ms = sum((ms[0] + ms[2] for label, ms in calls if label.startswith("dn_gn_backward") and len(ms) == 3), 0.0)
+    y_bytes = 2 if a.conv_out_storage == "bf16" else 4
+    # every GroupNorm call's launches in order (forward: statistics, finalisation, apply), by entry point
+    gn_launches = [(label, ms) for label, ms in calls if label.startswith("dn_gn_")]
     eager = {} if a.no_eager else grad_bench.eager_ms(blk, eager_block, x, [temb], dout, a.iters, a.warmup)
     best = min(eager.values()) if eager else None
     return dict(dim=dim, H=H, B=B, **switches, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), kernels_ms=sum(v[0] for v in split.values()),
-                gn_backward_passes_ms=gn_pass_ms,
-                gn_backward_gbs=(gn_bytes(dim, B, H) / (gn_pass_ms * 1e6) if gn_pass_ms else None),
+                gn_backward_passes_ms=gn_pass_ms, gn_backward_mb=gn_bytes(dim, B, H, y_bytes) / 1e6, gn_launches_ms=gn_launches,
+                gn_backward_gbs=(gn_bytes(dim, B, H, y_bytes) / (gn_pass_ms * 1e6) if gn_pass_ms else None),
                 split={k: dict(ms=v[0], launches=v[1]) for k, v in split.items()})
 
 
@@ -87,11 +92,13 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:8.3f} ms, channels_last {r['eager_nhwc_ms']:8.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f})")
-    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']} {r['conv_precision']} / act {r['act_storage']}: HIP {r['hip_ms']:8.3f} ms   "
+    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']}: HIP {r['hip_ms']:8.3f} ms   "
           f"{eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
     if r["gn_backward_gbs"]:
-        print(f"      GroupNorm backward passes: {gn_bytes(r['dim'], r['B'], r['H']) / 1e6:.1f} MB in {r['gn_backward_passes_ms']:.3f} ms = "
+        for label, ms in r["gn_launches_ms"]:
+            print(f"      {label:28s} launches: " + "  ".join(f"{v:.4f}" for v in ms) + " ms")
+        print(f"      GroupNorm backward passes: {r['gn_backward_mb']:.1f} MB in {r['gn_backward_passes_ms']:.3f} ms = "
               f"{r['gn_backward_gbs']:.0f} GB/s ({100 * r['gn_backward_gbs'] / HBM_PEAK_GBS:.0f} % of "
               f"{HBM_PEAK_GBS / 1000:.0f} TB/s)")
 

@@ -46,7 +46,7 @@ class TimedLib:
 
         def wrapped(*args):
             label = name[3:]
-            if name in ("ld_pc_conv", "ld_dn_conv16", "ld_dn_conv16_from16"):
+            if name == "ld_pc_conv" or name.startswith("ld_dn_conv16"):
                 label += " (forward)" if self.phase == "forward" else " (data gradient)"
             if name in ("ld_dn_pack_nhwc", "ld_dn_pack_nhwc_to16"):
                 label += f" ({self.phase})"
@@ -113,6 +113,7 @@ def print_split(split, kernels_ms):
 SWITCH_HELP = {
     "conv_precision": "the HIP side's convolutions: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
     "act_storage": "bf16 (with --conv-precision bf16): the HIP side keeps the activations only convolutions read as bf16",
+    "conv_out_storage": "bf16 (with --conv-precision bf16): the HIP side's ResnetBlocks keep the convolution outputs GroupNorm reads as bf16",
     "attn_precision": "the HIP side's LinearAttention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
     "full_attn_precision": "the HIP side's full-softmax Attention cores: fp32, or bf16 operands on the bf16 matrix cores (fp32 accumulation)",
 }

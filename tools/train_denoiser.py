@@ -40,6 +40,8 @@ KWARGS = {"mri": dict(mode="mri"), "mnist": dict(dim_mults=(1, 2, 4), full_attn=
 SWITCH_HELP = {
     "conv_precision": "bf16: the convolutions and their gradients on the bf16 matrix cores (operands rounded, fp32 accumulation)",
     "act_storage": "bf16 (with --conv-precision bf16): activations that only convolutions read are kept as bf16; same results",
+    "conv_out_storage": "bf16 (with --conv-precision bf16): the convolution outputs GroupNorm reads are kept as bf16; results move "
+                        "by about what the bf16 convolutions move them",
     "attn_precision": "bf16: the LinearAttention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)",
     "full_attn_precision": "bf16: the full-softmax Attention cores on the bf16 matrix cores (operands rounded, fp32 accumulation)",
 }
