@@ -32,7 +32,8 @@ C32_SHAPE = (2, 32, 32, 32, 32)                                # the smallest ma
 CONV1_SHAPES = [(1, 384, 256, 8, 8), (1, 96, 64, 14, 14), (1, 32, 384, 28, 28)]
 IMAGE_CASES = [(cin, ks, H, W) for cin in (1, 3) for ks in (3, 7) for (H, W) in ((20, 12), (28, 28))]
 STEM_SHAPES = [(3, 40, 33), (1, 28, 28)]                       # cin, H, W
-FINAL_CASES = [(32, 1), (32, 3), (64, 1), (64, 3)]             # cin, cout at 9 x 11
+FINAL_CASES = [(32, 1), (32, 3), (64, 1), (64, 3),             # cin, cout at 9 x 11
+               (8, 2), (8, 4), (24, 4), (40, 3)]               # ... a partial pass of the 4 x 16 B channel loop, cout 2 and 4
 ATTN_SIZES = [49, 324, 400, 1024, 4096]
 LINATTN_SHAPES = [(32, 28, 28), (64, 14, 14), (32, 64, 96)]    # C, H, W
 
