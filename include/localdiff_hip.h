@@ -618,6 +618,31 @@ int ld_pc_knn(const float* q, const float* qn, int N, const float* bank, const f
  * distances): d2 [N, M] fp32 scratch, dist [N, k] = sqrt(d2), idx [N, k] int32.  k <= M. */
 int ld_pc_knn_topk(const float* q, const float* qn, int N, const float* bank, const float* bn, int64_t M, int D, int k,
                    float* d2, float* dist, int32_t* idx, void* stream);
+/* ---- the same search with the fp16 matrix cores as a screen (PatchCore.knn_precision = "fp16"), csrc/knn16.hip ----
+ * The result is an fp32 search's: the screen only selects the rows that an exact fp32 re-rank looks at, inside a
+ * window that its worst-case error bound certifies; what cannot be certified is searched by ld_pc_knn's kernel. */
+#define LD_PC_KNN16_CAND 64   /* candidate rows kept per query; more inside the window: that query falls back */
+/* Once per bank: bank [M, D] -> bank_hi = fp16(bank), bank_lo = fp16(bank - bank_hi), both fp16 [M, D] (4 M D bytes in
+ * all, on top of the fp32 bank, which the re-rank and ld_pc_score* keep using), and info [2] fp32: the largest of
+ * bn [M] (the |m|^2 of ld_pc_row_norms), and 1.0 when every element is finite in fp16 (|x| <= 65504), else 0.0 -- such a
+ * bank must not be given to ld_pc_knn16.  bank, bank_hi, bank_lo 16-byte aligned, D a multiple of 32, M < 2^31. */
+int ld_pc_pack_bank16(const float* bank, const float* bn, int64_t M, int D, void* bank_hi, void* bank_lo, float* info,
+                      void* stream);
+/* Bytes of scratch for N queries of D elements (their fp16 split, keys, windows, candidate segments). */
+int64_t ld_pc_knn16_work_bytes(int N, int D);
+/* ld_pc_knn's contract and refusals.  For every query, idx is the argmin (lowest index on ties) and dist the square
+ * root of the minimum over ALL M rows of r = max((qn - 2 dot32) + bn, 0), dot32 the fp32 dot product in the re-rank's
+ * fixed order; for a query that could not be certified (more than LD_PC_KNN16_CAND rows inside its window, a non-finite
+ * window or norm, an element beyond 65504) exactly what ld_pc_knn returns.  No host synchronisation.  work:
+ * ld_pc_knn16_work_bytes(N, D) bytes, 16-byte aligned, as q.  stats: NULL or int32 [4] = queries certified, fallen back
+ * (they sum to N), bank rows inside all the windows together, the most inside one (the sum can wrap past 2^31). */
+int ld_pc_knn16(const float* q, const float* qn, int N, const float* bank, const void* bank_hi, const void* bank_lo,
+                const float* bn, const float* info, int64_t M, int D, void* work, float* dist, int32_t* idx,
+                int32_t* stats, void* stream);
+/* Test instrument, not a production path: the screened distances s [N, M] themselves, for small N x M (the hardware
+ * check of the error bound that the window rests on). */
+int ld_pc_knn16_screen(const float* q, const float* qn, int N, const void* bank_hi, const void* bank_lo, const float* bn,
+                       int64_t M, int D, void* work, float* s_out, void* stream);
 /* Image score, part 1 (models.py:241-246): per image the first argmax p* of its P patch scores, and bank row m* = loc[p*]
  * copied to q [B, D] with its norm to qn [B] (the query of the support search).  argmax [B] int32. */
 int ld_pc_score_prepare(const float* patch_scores, const int32_t* loc, const float* bank, const float* bn, int B, int P,

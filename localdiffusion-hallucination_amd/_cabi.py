@@ -193,6 +193,10 @@ _SIGS = {
     "ld_pc_row_norms": (C.c_int, [vp, vp, i64, C.c_int, vp]),
     "ld_pc_knn": (C.c_int, [vp, vp, C.c_int, vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "ld_pc_knn_topk": (C.c_int, [vp, vp, C.c_int, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ld_pc_pack_bank16": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
+    "ld_pc_knn16_work_bytes": (i64, [C.c_int, C.c_int]),
+    "ld_pc_knn16": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, i64, C.c_int, vp, vp, vp, vp, vp]),
+    "ld_pc_knn16_screen": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, i64, C.c_int, vp, vp, vp]),
     "ld_pc_score_prepare": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "ld_pc_score": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ld_pc_anomaly_map": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

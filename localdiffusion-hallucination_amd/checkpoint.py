@@ -154,7 +154,7 @@ def save_patchcore_bank(model, path):
     np.save(path, np.ascontiguousarray(bank))
 
 
-def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
+def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False, knn_precision=None):
     """Load a ``PatchCore``: the ``wide_resnet50_2`` weights and the memory bank (test.py:157-175).
 
     ``backbone_sd`` is a state_dict (or a file holding one) of torchvision's / timm's ``wide_resnet50_2``, bare or under
@@ -162,6 +162,7 @@ def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
     dropped (layers 2 and 3 do not use them), and so is a ``memory_bank`` entry when ``memory_bank_npy`` is given.
     ``memory_bank_npy`` is a ``.npy`` path (``np.load``ed as test.py:169-175 does) or an array [M, 1536], or None to take
     the state_dict's ``memory_bank``.  Names and shapes of the trunk must match exactly (RuntimeError otherwise).
+    ``knn_precision`` (``"fp32"`` / ``"fp16"``, None: leave the model's) is set on the model before the bank is.
     Returns {'n_tensors', 'bank_rows'}."""
     import numpy as np
     data = _read(backbone_sd, trust_pickle)
@@ -188,6 +189,8 @@ def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
                            f"unexpected {unexpected[:5]}")
     model.feature_extractor.load_state_dict({k: torch.as_tensor(v).to(own[k].dtype) for k, v in sd.items()})
     model.invalidate()
+    if knn_precision is not None:
+        model.knn_precision = knn_precision
     if memory_bank_npy is not None:
         bank = np.load(memory_bank_npy) if isinstance(memory_bank_npy, (str, bytes)) or hasattr(memory_bank_npy, "__fspath__") \
             else memory_bank_npy
@@ -198,16 +201,17 @@ def load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=False):
 
 
 def load_patchcore_classifier(backbone_sd, memory_bank_npy, config, obj, threshold=None, calibration=None, device="cuda",
-                              return_map=True, trust_pickle=False):
+                              return_map=True, trust_pickle=False, knn_precision="fp32"):
     """Build the hallucination gate (models.py:257-294): a ``PatchCore`` of the mode's input size (84 x 84 for mnist,
     224 x 224 otherwise, ``num_neighbors=9``), loaded by ``load_patchcore`` and moved to ``device`` in ``eval()``, inside
     a ``PatchCoreClassifier``.  ``memory_bank_npy=None`` takes the ``memory_bank`` entry of ``backbone_sd``, the form of
     the reference's mnist checkpoint (a whole-module state_dict, models.py:279); its mvtec / mri banks are ``.npy`` files
-    (:281-287).  ``threshold`` / ``calibration`` as in ``PatchCoreClassifier``."""
+    (:281-287).  ``threshold`` / ``calibration`` as in ``PatchCoreClassifier``; ``knn_precision`` as ``PatchCore``'s."""
     from .classifier import PatchCoreClassifier, gate_input_size
     from .patchcore import PatchCore
     S = gate_input_size(str(config["data"]))
-    model = PatchCore((S, S), layers=("layer2", "layer3"), backbone="wide_resnet50_2", num_neighbors=9)
+    model = PatchCore((S, S), layers=("layer2", "layer3"), backbone="wide_resnet50_2", num_neighbors=9,
+                      knn_precision=knn_precision)
     load_patchcore(backbone_sd, memory_bank_npy, model, trust_pickle=trust_pickle)
     model = model.to(device).eval()
     return PatchCoreClassifier(config, obj, model, threshold=threshold, calibration=calibration, return_map=return_map)

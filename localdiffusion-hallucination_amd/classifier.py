@@ -75,7 +75,8 @@ class PatchCoreClassifier(nn.Module):
     (``obj == 'flair'``) or ``mean_t1`` / ``std_t1`` from ``config``.  ``patchcore`` is a prepared ``PatchCore`` (weights
     and memory bank loaded, on the GPU, in ``eval()``) whose square ``input_size`` is the mode's (84 for mnist, 224
     otherwise).  ``threshold``, or ``calibration=(images, labels)`` for ``calc_threshold``: one of the two is required
-    (the reference would read its authors' test set from a fixed path).
+    (the reference would read its authors' test set from a fixed path).  ``knn_precision`` (``"fp32"`` / ``"fp16"``) is
+    set on ``patchcore`` (see ``PatchCore.knn_precision``; also readable and assignable here afterwards).
 
     ``classifier(x0)`` returns the reference's triple ``(decision, anomaly_map, pred_score)``: a Python int 1 / 0
     (``pred_score > threshold``), the map [B, 1, H, W] on the device (``None`` with ``return_map=False``: then neither the
@@ -86,8 +87,10 @@ class PatchCoreClassifier(nn.Module):
     ``calc_threshold`` sets (to the width of the calibration images), so with a threshold passed in it raises
     ``AttributeError``; x0's size is what ``calc_threshold`` would have found for a data set of that size."""
 
-    def __init__(self, config, obj, patchcore, threshold=None, calibration=None, return_map=True):
+    def __init__(self, config, obj, patchcore, threshold=None, calibration=None, return_map=True, knn_precision=None):
         super().__init__()
+        if knn_precision is not None:                  # passed through to PatchCore, which checks it; None: leave its own
+            patchcore.knn_precision = knn_precision
         self.config, self.mode, self.obj = config, str(config["data"]), obj
         self.halve = ("mvtec" in self.mode) or ("mnist" in self.mode)
         if not self.halve:
@@ -114,6 +117,14 @@ class PatchCoreClassifier(nn.Module):
         self.threshold = None if threshold is None else float(threshold)
         if threshold is None:
             self.calc_threshold(*calibration)
+
+    @property
+    def knn_precision(self):
+        return self.patchcore.knn_precision
+
+    @knn_precision.setter
+    def knn_precision(self, value):
+        self.patchcore.knn_precision = value
 
     # ------------------------------------------------------------------ buffers
     def _plan(self, B, H, W, dev):

@@ -16,6 +16,7 @@
 // in registers while the current one is multiplied.  Both operands are K-contiguous rows (activations / query rows and
 // OHWI weights / bank rows), so one loader shape serves both.
 #include "common.hip.h"
+#include "pc_knn.hip.h"
 
 namespace {
 constexpr int PC_TN = 64;   // output columns per workgroup (output channels / bank rows)
@@ -142,23 +143,24 @@ struct PcKnnDev {
   unsigned long long* keys;   // MODE 0: [N] running minimum
   float* d2;                  // MODE 1: [N, M] all distances
   long M; int N, D, tiles_per_split;
+  const int32_t* list; const int32_t* count;   // MODE 2 only
 };
 
-__device__ __forceinline__ unsigned long long pc_key(float d2, unsigned idx) {
-  return ((unsigned long long)(__float_as_uint(d2) & 0x7fffffffu) << 32) | idx;   // (d2 >= 0: drops a -0's sign)
-}
-__device__ __forceinline__ unsigned long long pc_shfl_xor64(unsigned long long v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // MODE 0: min / argmin per query over this workgroup's bank tiles, merged by atomicMin.  MODE 1: d2 matrix (top-k).
+// MODE 2: MODE 0 for the *a.count queries whose row numbers are in a.list (the exact search of the queries that the
+// fp16 screen of knn16.hip could not certify); the grid is sized for N, surplus workgroups leave on the count.
 template <int MODE>
 __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
   __shared__ __attribute__((aligned(16))) PcSmem<PC_KNN_TM> sm;
   constexpr int NB = PC_KNN_TM / 64;
   const int tid = threadIdx.x, lr = tid >> 3, lk = (tid & 7) * 4;
   const int row0 = blockIdx.x * PC_KNN_TM;
+  int nrows = a.N;
+  if constexpr (MODE == 2) {
+    nrows = *a.count;
+    if (row0 >= nrows) return;
+  }
+  auto src = [&](int i) { if constexpr (MODE == 2) return (int)a.list[i]; else return i; };   // row i of the tile space
   const long ntiles = (a.M + PC_TN - 1) / PC_TN;
   const long t0 = (long)blockIdx.y * a.tiles_per_split;
   const long t1 = t0 + a.tiles_per_split < ntiles ? t0 + a.tiles_per_split : ntiles;
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
 #pragma unroll
   for (int u = 0; u < PC_KNN_TM / 32; ++u) {
     const int r = row0 + lr + 32 * u;
-    qrow[u] = a.q + (long)(r < a.N ? r : a.N - 1) * a.D + lk;          // padding rows read a real row, never stored
+    qrow[u] = a.q + (long)src(r < nrows ? r : nrows - 1) * a.D + lk;   // padding rows read a real row, never stored
   }
   float qn[NB][16];
 #pragma unroll
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = row0 + pc_acc_row<PC_KNN_TM>(m, r);
-      qn[m][r] = a.qn[i < a.N ? i : a.N - 1];
+      qn[m][r] = a.qn[src(i < nrows ? i : nrows - 1)];
     }
   float best[NB][16];
   unsigned bidx[NB][16];
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float d2 = fmaxf((qn[m][r] - 2.0f * acc[m][r]) + bnj, 0.0f);     // euclidean_dist's order (models.py:194)
-        if constexpr (MODE == 0) {
+        if constexpr (MODE != 1) {
           if (d2 < best[m][r]) { best[m][r] = d2; bidx[m][r] = (unsigned)j; }   // columns rise: the first index stays
         } else {
           const int i = row0 + pc_acc_row<PC_KNN_TM>(m, r);
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
         }
       }
   }
-  if constexpr (MODE == 0) {
+  if constexpr (MODE != 1) {
 #pragma unroll
     for (int m = 0; m < NB; ++m)
 #pragma unroll
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(256) void pc_knn_kernel(PcKnnDev a) {
           k = k2 < k ? k2 : k;
         }
         const int i = row0 + pc_acc_row<PC_KNN_TM>(m, r);
-        if ((threadIdx.x & 31) == 0 && i < a.N && k != ~0ull) atomicMin(a.keys + i, k);
+        if ((threadIdx.x & 31) == 0 && i < nrows && k != ~0ull) atomicMin(a.keys + src(i), k);
       }
   }
 }
@@ -547,7 +549,8 @@ __global__ void pc_blur_y_kernel(const float* __restrict__ tmp, const float* __r
 }
 
 int pc_knn_launch(int mode, const float* q, const float* qn, int N, const float* bank, const float* bn, long M, int D,
-                  unsigned long long* keys, float* d2, hipStream_t st) {
+                  unsigned long long* keys, float* d2, hipStream_t st, const int32_t* list = nullptr,
+                  const int32_t* count = nullptr) {
   const long ntiles = (M + PC_TN - 1) / PC_TN;
   const int rtiles = (N + PC_KNN_TM - 1) / PC_KNN_TM;
   long splits = 1024 / rtiles;                          // about four workgroups per CU in all
@@ -555,15 +558,22 @@ int pc_knn_launch(int mode, const float* q, const float* qn, int N, const float*
   if (splits > ntiles) splits = ntiles;
   const long per = (ntiles + splits - 1) / splits;
   splits = (ntiles + per - 1) / per;
-  PcKnnDev d{q, qn, bank, bn, keys, d2, M, N, D, (int)per};
+  PcKnnDev d{q, qn, bank, bn, keys, d2, M, N, D, (int)per, list, count};
   const dim3 grid((unsigned)rtiles, (unsigned)splits);
   if (mode == 0)
     LD_LAUNCH(pc_knn_kernel<0>, grid, dim3(256), 0, st, d);
-  else
+  else if (mode == 1)
     LD_LAUNCH(pc_knn_kernel<1>, grid, dim3(256), 0, st, d);
+  else
+    LD_LAUNCH(pc_knn_kernel<2>, grid, dim3(256), 0, st, d);
   return 0;
 }
 }  // namespace
+
+void pc_knn_exact_listed(const float* q, const float* qn, int N, const float* bank, const float* bn, long M, int D,
+                         unsigned long long* keys, const int32_t* list, const int32_t* count, hipStream_t st) {
+  pc_knn_launch(2, q, qn, N, bank, bn, M, D, keys, nullptr, st, list, count);
+}
 
 extern "C" int ld_pc_conv(const ld_pc_conv_args* a, void* stream) {
   LD_REQUIRE(a, "ld_pc_conv: null args");

@@ -13,7 +13,14 @@ layer1..3; what anomalib's attribute holds) plus the ``memory_bank`` buffer.  Th
 * the image score of models.py:222-254 (argmax patch, the ``num_neighbors`` bank rows nearest to its neighbour, softmax);
 * the anomaly map: nearest upsample to ``input_size`` and the 33x33 Gaussian blur (sigma 4, reflect padding).
 
-All fp32.  BatchNorm always uses the running statistics: the module must be in ``eval()`` mode.  No CPU fallback.
+All fp32 by default.  ``knn_precision = "fp16"`` runs the nearest-neighbour search of ``nearest`` (and through it
+``score``, ``forward`` and the gate) on ``csrc/knn16.hip``: the fp16 matrix cores screen the bank, an fp32 re-rank of the
+rows inside a certified window gives the answer, and a query that cannot be certified is searched by the fp32 kernel.
+The re-rank sums in the fp32 kernel's own order, so distances and indices are ``"fp32"``'s to the bit (``knn_stats()``
+counts the certified and the fallen-back queries).  It keeps an fp16 (hi, lo) copy of the bank beside the fp32 one,
+``4 * M * 1536`` bytes more, and refuses a bank with an element beyond fp16's range (``ValueError``).  ``topk`` and the
+image score stay fp32.  BatchNorm always uses the running statistics: the module must be in ``eval()`` mode.  No CPU
+fallback.
 A memory bank is built with ``build_memory_bank`` / ``subsample_embedding`` (anomaly_model_train.py:339-385): the
 training embeddings, then anomalib's KCenterGreedy coreset on the kernels of ``csrc/coreset.hip`` (``coreset.py``).
 Not covered: other backbones or layers, the tiler, training the trunk.
@@ -30,6 +37,7 @@ from .weights import PC_STAGES
 BN_EPS = 1e-5
 EMBED_DIM = 1536           # 512 (layer2) + 1024 (layer3)
 BLUR_SIGMA = 4.0
+KNN_PRECISIONS = ("fp32", "fp16")
 
 
 def gaussian_kernel1d(sigma=BLUR_SIGMA):
@@ -92,8 +100,12 @@ def _bn_affine(bn):
 
 
 class PatchCore(nn.Module):
-    def __init__(self, input_size, layers=("layer2", "layer3"), backbone="wide_resnet50_2", num_neighbors=9, tiler=None):
+    def __init__(self, input_size, layers=("layer2", "layer3"), backbone="wide_resnet50_2", num_neighbors=9, tiler=None,
+                 knn_precision="fp32"):
         super().__init__()
+        self._bank16 = None          # (hi, lo, info) of the bank on the device, knn_precision "fp16" only
+        self._knn_stats = None       # int32 [4] on the device: certified, fell back, candidate rows, the most per query
+        self.knn_precision = knn_precision
         if backbone != "wide_resnet50_2":
             raise ValueError(f"PatchCore: backbone {backbone!r}; only wide_resnet50_2 (test.py:159) has HIP kernels")
         if tuple(layers) != ("layer2", "layer3"):
@@ -115,14 +127,39 @@ class PatchCore(nn.Module):
         self._plans = {}             # (B, H, W, device) -> activation buffers
 
     # ------------------------------------------------------------------ cache control
+    @property
+    def knn_precision(self):
+        """``"fp32"`` (default): ``nearest`` is ``ld_pc_knn``.  ``"fp16"``: ``ld_pc_knn16``, the fp16 screen with the exact
+        fp32 re-rank.  Checked on assignment; no part of the ``state_dict``.  Switching to ``"fp16"`` with a bank already
+        on the device packs it and raises ``ValueError`` when the bank does not fit fp16's range."""
+        return self._knn_precision
+
+    @knn_precision.setter
+    def knn_precision(self, value):
+        if value not in KNN_PRECISIONS:
+            raise ValueError(f"PatchCore: knn_precision {value!r}; one of {KNN_PRECISIONS}")
+        old = self.__dict__.get("_knn_precision", "fp32")
+        self._knn_precision = value
+        bank = self._buffers.get("memory_bank") if "_buffers" in self.__dict__ else None
+        if value == "fp16" and bank is not None and bank.is_cuda and bank.numel() > 0:
+            try:
+                self._bank16_dev(bank.device)
+            except ValueError:
+                self._knn_precision = old                 # the bank is refused: the mode stays what it was
+                raise
+
     def invalidate(self):
         self._prep = None
         self._bank = None
+        self._bank16 = None
         self._plans = {}
 
     def _apply(self, fn, *args, **kwargs):
         self.invalidate()
-        return super()._apply(fn, *args, **kwargs)
+        out = super()._apply(fn, *args, **kwargs)
+        if self.knn_precision == "fp16" and self.memory_bank.is_cuda and self.memory_bank.numel() > 0:
+            self._bank16_dev(self.memory_bank.device)         # a bank beyond fp16's range is refused when it arrives
+        return out
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
         self.invalidate()
@@ -139,6 +176,9 @@ class PatchCore(nn.Module):
             raise ValueError(f"PatchCore: memory bank {tuple(t.shape)}, expected [M >= 1, {EMBED_DIM}]")
         self.memory_bank = t.to(self.memory_bank.device).contiguous()
         self._bank = None
+        self._bank16 = None
+        if self.knn_precision == "fp16" and self.memory_bank.is_cuda:
+            self._bank16_dev(self.memory_bank.device)         # ValueError now, not at the first search
 
     # ------------------------------------------------------------------ weights in kernel layout
     def _prepare(self, dev):
@@ -174,6 +214,39 @@ class PatchCore(nn.Module):
                                                   torch.cuda.current_stream(dev).cuda_stream), "pc_row_norms")
             self._bank = (bank, norms)
         return self._bank
+
+    def _bank16_dev(self, dev):
+        """The bank's fp16 split (hi, lo) [M, 1536] and info [2] (largest |m|^2, fp16-finite flag) on the device, packed
+        once per bank.  ValueError (one 4-byte read per bank) when an element is beyond fp16's range."""
+        if self._bank16 is None:
+            bank, bn = self._bank_dev(dev)
+            hi = torch.empty(bank.shape, dtype=torch.float16, device=dev)
+            lo = torch.empty(bank.shape, dtype=torch.float16, device=dev)
+            info = torch.empty(2, dtype=torch.float32, device=dev)
+            cabi.check(cabi.lib().ld_pc_pack_bank16(bank.data_ptr(), bn.data_ptr(), bank.shape[0], bank.shape[1],
+                                                    hi.data_ptr(), lo.data_ptr(), info.data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream), "pc_pack_bank16")
+            if float(info[1].item()) != 1.0:
+                raise ValueError("PatchCore: knn_precision 'fp16' needs every bank element finite in fp16 "
+                                 "(|x| <= 65504); this bank has one that is not: use knn_precision 'fp32'")
+            self._bank16 = (hi, lo, info)
+        return self._bank16
+
+    def knn_stats(self):
+        """(certified, fell back) query counts of the last ``nearest`` at ``knn_precision = "fp16"`` (they sum to its N),
+        read from the device on demand; None before the first such search."""
+        if self._knn_stats is None:
+            return None
+        c, f = self._knn_stats.tolist()[:2]
+        return int(c), int(f)
+
+    def knn_candidates(self):
+        """(bank rows inside all the windows of the last fp16 search together, the most inside one window): what the
+        re-rank looked at; a window with more than 64 rows sends its query to the fp32 kernel.  None as ``knn_stats``."""
+        if self._knn_stats is None:
+            return None
+        t, m = self._knn_stats.tolist()[2:]
+        return int(t), int(m)
 
     # ------------------------------------------------------------------ launches
     def _plan(self, B, H, W, dev):
@@ -280,9 +353,18 @@ class PatchCore(nn.Module):
         if norms is None:
             norms = torch.empty(N, dtype=torch.float32, device=dev)
             cabi.check(lib.ld_pc_row_norms(rows.data_ptr(), norms.data_ptr(), N, EMBED_DIM, st), "pc_row_norms")
-        work = torch.empty(N, dtype=torch.int64, device=dev)
         dist = torch.empty(N, dtype=torch.float32, device=dev)
         idx = torch.empty(N, dtype=torch.int32, device=dev)
+        if self.knn_precision == "fp16":
+            hi, lo, info = self._bank16_dev(dev)
+            work = torch.empty(int(lib.ld_pc_knn16_work_bytes(N, EMBED_DIM)), dtype=torch.uint8, device=dev)
+            stats = torch.empty(4, dtype=torch.int32, device=dev)
+            cabi.check(lib.ld_pc_knn16(rows.data_ptr(), norms.data_ptr(), N, bank.data_ptr(), hi.data_ptr(), lo.data_ptr(),
+                                       bn.data_ptr(), info.data_ptr(), bank.shape[0], EMBED_DIM, work.data_ptr(),
+                                       dist.data_ptr(), idx.data_ptr(), stats.data_ptr(), st), "pc_knn16")
+            self._knn_stats = stats
+            return dist, idx
+        work = torch.empty(N, dtype=torch.int64, device=dev)
         cabi.check(lib.ld_pc_knn(rows.data_ptr(), norms.data_ptr(), N, bank.data_ptr(), bn.data_ptr(), bank.shape[0],
                                  EMBED_DIM, work.data_ptr(), dist.data_ptr(), idx.data_ptr(), st), "pc_knn")
         return dist, idx

@@ -10,7 +10,9 @@ anomaly map, against the same call composed in eager PyTorch around the SAME HIP
 so the difference is what csrc/classifier.hip replaces.  Also one denoiser evaluation (`Unet` forward) of the matching
 size timed the same way, and the gate's share of a gated joint step, gate / (gate + step).
 
-  python tools/bench_classifier.py [--iters 20] [--warmup 5] [--bank 16384]
+  python tools/bench_classifier.py [--iters 20] [--warmup 5] [--bank-rows 16384] [--knn-precision fp32|fp16] [--cases 0,1,2]
+``--bank-rows`` (``--bank``) takes the table at a reference-size bank (the reference's MVTec bank has 784k rows),
+``--knn-precision fp16`` with PatchCore's search on the fp16 screen of csrc/knn16.hip.
 Wall-clock ms per call between device synchronisations (a gate call ends with a host read, so the host side belongs to
 it), median of --iters after --warmup.  Weights are procedural, the bank random (timing does not depend on values).
 Prints one JSON line per case, then the README table.
@@ -84,7 +86,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--bank", type=int, default=16384)
+    ap.add_argument("--bank-rows", "--bank", dest="bank", type=int, default=16384)
+    ap.add_argument("--knn-precision", choices=("fp32", "fp16"), default="fp32")
+    ap.add_argument("--cases", default="0,1,2", help="indices into the three cases")
     args = ap.parse_args()
     ldh.configure_runtime()
     dev = "cuda"
@@ -92,10 +96,10 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     bank = torch.randn(args.bank, EMBED_DIM, device=dev, generator=g)
     pcs, rows = {}, []
-    for name, config, obj, C, H, unet_kw in CASES:
+    for name, config, obj, C, H, unet_kw in [CASES[int(c)] for c in args.cases.split(",")]:
         S = 84 if "mnist" in config["data"] else 224
         if S not in pcs:
-            pc = ldh.PatchCore((S, S))
+            pc = ldh.PatchCore((S, S), knn_precision=args.knn_precision)
             pc.feature_extractor.load_state_dict(sd)
             pc.set_memory_bank(bank)
             pcs[S] = pc.to(dev).eval()
@@ -113,7 +117,8 @@ def main():
                 t_hip = timed(lambda: clf(x0), args.iters, args.warmup)
                 t_eager = timed(lambda: eager_gate(clf, x0, want_map), args.iters, args.warmup)
                 t_pc = timed(lambda: pcs[S].score(clf._plan(1, H, H, x0.device)["x"]), args.iters, args.warmup)
-                r = dict(case=name, return_map=want_map, bank_rows=args.bank, gate_hip_ms=round(t_hip, 4),
+                r = dict(case=name, return_map=want_map, bank_rows=args.bank, knn_precision=args.knn_precision,
+                         knn_stats=pcs[S].knn_stats(), gate_hip_ms=round(t_hip, 4),
                          gate_eager_ms=round(t_eager, 4), speedup=round(t_eager / t_hip, 3), patchcore_score_ms=round(t_pc, 4),
                          unet_step_ms=round(t_step, 4), gate_share_of_gated_step=round(t_hip / (t_hip + t_step), 3))
                 print(json.dumps(r), flush=True)

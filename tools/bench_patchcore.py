@@ -7,6 +7,11 @@
   against the MI355X fp32 roofline (8.0 TB/s HBM, 157.3 TFLOPS f32 matrix).
 
   python tools/bench_patchcore.py [--sizes 84,224] [--batches 1,8] [--banks 16384,100000,700000] [--iters 5] [--warmup 2]
+                                 [--knn-precision fp32|fp16] [--clustered-bank M] [--skip-backbone] [--skip-eager]
+``--knn-precision fp16`` adds the fp16-screen search (csrc/knn16.hip) to every kNN row: ``ld_pc_knn`` and ``ld_pc_knn16``
+timed alternately, twice each, on the same queries and bank (the yardstick is the fp32 kernel of the same run), with the
+certified / fallen-back split and the bank rows inside the windows per query.  ``--clustered-bank M`` adds one bank of M
+non-negative clustered rows with queries drawn the same way (what post-ReLU features look like: the window is exercised).
 The eager legs are F.conv2d / F.batch_norm / F.avg_pool2d / F.interpolate, and euclidean_dist on torch.matmul with
 torch's min(1) (the bank in chunks of 65536 rows, so the N x M distance matrix fits in memory).  Weights are
 procedural, the bank random (timing does not depend on values).  Prints one line per case and a JSON list at the end.
@@ -86,6 +91,10 @@ def main():
     ap.add_argument("--banks", default="16384,100000,700000")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--knn-precision", choices=("fp32", "fp16"), default="fp32")
+    ap.add_argument("--clustered-bank", type=int, default=0)
+    ap.add_argument("--skip-backbone", action="store_true")
+    ap.add_argument("--skip-eager", action="store_true")
     args = ap.parse_args()
     ldh.configure_runtime()
     dev = "cuda"
@@ -98,29 +107,58 @@ def main():
         m = m.to(dev).eval()
         for B in (int(b) for b in args.batches.split(",")):
             x = torch.randn(B, 3, H, H, device=dev, generator=g)
-            with torch.no_grad():
-                t_hip = timed(lambda: m.embed(x), args.iters, args.warmup)
-                t_eager = timed(lambda: eager_embed(sd, x), args.iters, args.warmup)
-            r = dict(part="backbone", size=H, B=B, hip_ms_per_image=t_hip / B, eager_ms_per_image=t_eager / B,
-                     speedup=t_eager / t_hip)
-            print(json.dumps(r), flush=True)
-            results.append(r)
-            q = m.embed(x)
-            N = q.shape[0]
-            for M in (int(v) for v in args.banks.split(",")):
-                bank = torch.randn(M, EMBED_DIM, device=dev, generator=g)
+            if not args.skip_backbone:
+                with torch.no_grad():
+                    t_hip = timed(lambda: m.embed(x), args.iters, args.warmup)
+                    t_eager = timed(lambda: eager_embed(sd, x), args.iters, args.warmup)
+                r = dict(part="backbone", size=H, B=B, hip_ms_per_image=t_hip / B, eager_ms_per_image=t_eager / B,
+                         speedup=t_eager / t_hip)
+                print(json.dumps(r), flush=True)
+                results.append(r)
+            q_emb = m.embed(x)
+            N = q_emb.shape[0]
+            cases = [("gauss", int(v)) for v in args.banks.split(",") if v]
+            if args.clustered_bank:
+                cases.append(("clustered", args.clustered_bank))
+            for kind, M in cases:
+                q = q_emb
+                if kind == "gauss":
+                    bank = torch.randn(M, EMBED_DIM, device=dev, generator=g)
+                else:
+                    centres = torch.randn(64, EMBED_DIM, device=dev, generator=g).abs() * 2.0
+                    bank = torch.randn(M, EMBED_DIM, device=dev, generator=g).mul_(0.28)
+                    bank.add_(centres[torch.arange(M, device=dev) % 64]).abs_()
+                    q = (centres[torch.arange(N, device=dev) % 64]
+                         + 0.28 * torch.randn(N, EMBED_DIM, device=dev, generator=g)).abs()
+                m.knn_precision = "fp32"
                 m.set_memory_bank(bank)
                 bank_norm = bank.pow(2).sum(-1)
                 with torch.no_grad():
                     t_hip = timed(lambda: m.nearest(q), args.iters, args.warmup)
-                    t_eager = timed(lambda: eager_knn(q, bank, bank_norm), args.iters, args.warmup)
+                    t_eager = float("nan") if args.skip_eager else timed(lambda: eager_knn(q, bank, bank_norm), args.iters,
+                                                                         args.warmup)
                 passes = (N + 127) // 128
                 gbs = M * EMBED_DIM * 4 * passes / (t_hip * 1e-3) / 1e9
                 tflops = 2.0 * N * M * EMBED_DIM / (t_hip * 1e-3) / 1e12
-                r = dict(part="knn", size=H, B=B, N=N, M=M, hip_ms_per_image=t_hip / B, eager_ms_per_image=t_eager / B,
+                r = dict(part="knn", bank=kind, size=H, B=B, N=N, M=M, hip_ms_per_image=t_hip / B, eager_ms_per_image=t_eager / B,
                          speedup=t_eager / t_hip, bank_stream_GBs=round(gbs, 1),
                          bank_stream_frac_hbm=round(gbs / (HBM_TBS * 1e3), 3), tflops=round(tflops, 2),
                          frac_f32_peak=round(tflops / F32_TFLOPS, 3))
+                if args.knn_precision == "fp16":
+                    runs = {"fp32": [], "fp16": []}
+                    with torch.no_grad():
+                        d32, i32 = m.nearest(q)
+                        for _ in range(2):                         # alternating, each twice: the spread shows
+                            for mode in ("fp32", "fp16"):
+                                m.knn_precision = mode
+                                runs[mode].append(timed(lambda: m.nearest(q), args.iters, args.warmup))
+                        d16, i16 = m.nearest(q)
+                    (cert, fell), (rows_in, rows_max) = m.knn_stats(), m.knn_candidates()
+                    r.update(fp32_ms=[round(t, 4) for t in runs["fp32"]], fp16_ms=[round(t, 4) for t in runs["fp16"]],
+                             fp16_speedup=round(min(runs["fp32"]) / min(runs["fp16"]), 3), certified=cert, fell_back=fell,
+                             candidates_per_query=round(rows_in / N, 2), candidates_max=rows_max,
+                             same_bits=bool(torch.equal(d16, d32) and torch.equal(i16, i32)))
+                    m.knn_precision = "fp32"
                 print(json.dumps(r), flush=True)
                 results.append(r)
                 del bank, bank_norm
