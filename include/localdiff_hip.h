@@ -302,7 +302,13 @@ int ld_linattn_ctxfold(const float* ctx_part, int nchunks, const float* w_out /*
  *   ld_linattn_out:   x -> out = RMSNorm(to_out(ctx^T softmax_d(q)*scale)) + x  (:242,245,249,251,425);
  *        wq_packed = the 128 q rows packed the same way, mfold from ld_linattn_fold / _ctxfold (perm=1);
  *        qshift (optional, [4] fp32): per head an upper bound of q over its 32 channels (max_d of the same
- *        Cauchy-Schwarz norm, <= 40), used as the softmax_d shift instead of the per-pixel maximum. */
+ *        Cauchy-Schwarz norm, <= 40), used as the softmax_d shift instead of the per-pixel maximum.
+ *        ld_linattn_out / ld_linattn_out_terms are BUILT FOR hidden = 128 (four heads of 32) and take no head count:
+ *        they read 128 rows of wq_packed, C x 128 elements of mfold per batch and four floats of qshift whatever the
+ *        caller packed, and CANNOT CHECK it.  A caller with another head count must take the unfused route
+ *        (ld_conv1x1 LD_EPI_QKV_LINEAR, ld_linattn_ctx, ld_linattn_ctxfold, ld_conv1x1 LD_EPI_RMS_RES), as Unet does.
+ *        ld_linattn_kvctx takes any head count in its two-sweep, one-term form (a workgroup per head); kshift and
+ *        weight_terms = 2 need heads == 4 and are refused (-1, nothing written) otherwise. */
 int ld_linattn_kvctx(const void* x, const void* wkv_packed, const float* kshift, float* ctx_part, int B,
                      int n, int C, int heads, int dim_head, int nchunks, int dtype, void* stream);
 int ld_linattn_out(const void* x, const void* wq_packed, const float* qshift, const void* mfold,

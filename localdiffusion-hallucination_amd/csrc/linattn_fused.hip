@@ -631,6 +631,7 @@ int kvctx_launch(const KvCtxArgs& a, int B, hipStream_t st) {
   dim3 grid(nchunks, heads, B);
   const size_t lds = (size_t)nch * 4 * KTN * 16 + 2 * KTN * PROW + KTN * sizeof(float) + 128 * sizeof(float);
   if (nch == 1) {
+    LD_HIP(ld_allow_lds((kvctx_kernel<T, 1>), lds));      // 65.5 KiB with the P / V tiles: past the default limit even at C = 32
     LD_LAUNCH((kvctx_kernel<T, 1>), grid, dim3(256), lds, st, KVCTX_ARGS(a));
   } else if (nch == 2) {
     LD_HIP(ld_allow_lds((kvctx_kernel<T, 2>), lds));
@@ -651,7 +652,10 @@ int linout_launch(const LinOutArgs& a, int B, hipStream_t st) {
   if (a.wsplit) {
     LD_REQUIRE(nch <= 2, "ld_linattn_out: two-term weights are built for C = 32 / 64 (got %d)", a.C);
     if (nch == 1) LD_LAUNCH((linout_kernel<T, 1, 1>), grid, dim3(256), lds, st, LINOUT_ARGS(a));
-    else LD_LAUNCH((linout_kernel<T, 2, 1>), grid, dim3(256), lds, st, LINOUT_ARGS(a));
+    else {
+      LD_HIP(ld_allow_lds((linout_kernel<T, 2, 1>), lds));   // 64.5 KiB: the doubled W_q tile puts C = 64 past the default limit
+      LD_LAUNCH((linout_kernel<T, 2, 1>), grid, dim3(256), lds, st, LINOUT_ARGS(a));
+    }
   } else if (nch == 1) {
     LD_LAUNCH((linout_kernel<T, 1>), grid, dim3(256), lds, st, LINOUT_ARGS(a));
   } else if (nch == 2) {

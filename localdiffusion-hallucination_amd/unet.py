@@ -63,6 +63,9 @@ class Unet(nn.Module):
                              "(unet_model.py:100) and is concatenated with the 8*dim bottleneck")
         if attn_dim_head != 32:
             raise ValueError("attn_dim_head must be 32 (MFMA tile of the attention kernels)")
+        if attn_heads < 1 or (attn_heads * attn_dim_head) % 64:
+            raise ValueError(f"attn_heads must be even (got {attn_heads}): the to_qkv epilogues of ld_conv1x1 work on "
+                             "64-channel tiles of hidden = attn_heads * attn_dim_head")
         if compute_dtype not in _TORCH_DT:
             raise ValueError(f"compute_dtype {compute_dtype!r} (fp32 | bf16 | fp16)")
         full_attn = tuple(full_attn) if isinstance(full_attn, (tuple, list)) else (full_attn,) * len(dim_mults)
@@ -207,7 +210,9 @@ class Unet(nn.Module):
             else:
                 pack(name, k)
         P["wq"], P["wkv"], P["kshift"], P["qshift"] = {}, {}, {}, {}
-        if self.compute_dtype in _LOWP:
+        # the fused route (csrc/linattn_fused.hip) is built for hidden = 128: ld_linattn_out cannot check the head count
+        # it was packed for, so any other one takes the unfused route (linear_attention) at every storage type
+        if self.compute_dtype in _LOWP and self.cfg.attn_heads == 4:
             hid, heads = self.cfg.hidden, self.cfg.attn_heads
             for name, w in sd.items():
                 if not name.endswith(".to_qkv.weight") or (name[:-len(".to_qkv.weight")] + ".to_out.1.g") not in sd:
@@ -219,7 +224,7 @@ class Unet(nn.Module):
                 if c not in (32, 64, 128):
                     continue
 
-                terms = 2 if (c in (32, 64) and heads == 4 and self._layer_level(name) < self.weight_split_levels) else 1
+                terms = 2 if (c in (32, 64) and self._layer_level(name) < self.weight_split_levels) else 1
 
                 def pack_rows(rows, terms=terms):
                     out = torch.empty(terms * rows.numel(), dtype=tdt, device=dev)
@@ -834,20 +839,21 @@ class _Plan:
         # ... at up to 8 patches per launch; 64 patches per GPU measured 0.8 % slower with it and keep 1024)
         rule = self.tn.chunk_rule(B)                      # n >= 65536, n >= 16384, smaller
         chunk_px = rule[0] if n >= 65536 else (rule[1] if n >= 16384 else rule[2])
-        nchunks = max(1, min(128, n // chunk_px)) if heads == 4 else max(1, min(32, n // 256))
+        assert heads == 4, "the fused kernels are built for four heads (packed() leaves every other count unfused)"
+        nchunks = max(1, min(128, n // chunk_px))
         # one or two large images per launch (cfg5: 512^2 maps at B = 1): 128 chunks of 2,048 pixels are 128 workgroups on
         # 256 CUs.  Chunks shrink (down to one 256-pixel tile) until the launch has two workgroups per CU; ctxfold
         # combines up to 512 partials.  cfg3 / cfg4 (B >= 4 at 256^2) are untouched: 512 workgroups already.
-        if heads == 4 and self.tn.linattn_chunk_px is None:
+        if self.tn.linattn_chunk_px is None:
             while B * nchunks < 512 and nchunks < 512 and n // (2 * nchunks) >= 256:
                 nchunks *= 2
         ctx = self._tracked(torch.empty(int(lib.ld_linattn_ctx_part_floats(B, heads, 32, nchunks)), dtype=torch.float32, device=self.dev))
         wfold = self._tracked(torch.empty(B, c * hid, dtype=self.tdt, device=self.dev))
         wout = f[p + ".to_out.0.weight"].reshape(c, hid).contiguous()
         wq, wkv = self.P["wq"][p], self.P["wkv"][p]
-        kshift = self.P["kshift"].get(p) if heads == 4 else None
+        kshift = self.P["kshift"].get(p)
         ksp = kshift.data_ptr() if kshift is not None else None
-        qshift = self.P["qshift"].get(p) if heads == 4 else None
+        qshift = self.P["qshift"].get(p)
         qsp = qshift.data_ptr() if qshift is not None else None
         bias, g2 = f[p + ".to_out.0.bias"], self.P["g2"][p + ".to_out.1.g"]
         out = self.buf(h, w, c)

@@ -36,6 +36,10 @@ FINAL_CASES = [(32, 1), (32, 3), (64, 1), (64, 3),             # cin, cout at 9 
                (8, 2), (8, 4), (24, 4), (40, 3)]               # ... a partial pass of the 4 x 16 B channel loop, cout 2 and 4
 ATTN_SIZES = [49, 324, 400, 1024, 4096]
 LINATTN_SHAPES = [(32, 28, 28), (64, 14, 14), (32, 64, 96)]    # C, H, W
+# ---- the shapes of tests/test_hip_attention_heads.py (head counts other than the model's default of 4)
+OTHER_HEADS = [1, 2, 8]
+ATTN_HEADS_SIZES = [49, 324]                                   # one ragged key tile; three tiles, two key groups
+KVCTX_HEADS_SHAPES = [(32, 28, 28), (64, 14, 14), (128, 7, 7)] # C, H, W: 3 pixel chunks; one ragged tile; 49 pixels, four K-chunks
 
 
 def ints(shape, key, lo, hi):
@@ -244,38 +248,41 @@ HID = HEADS * DH
 
 def _pack_qkv(q, k, v):
     """[B, heads, n, 32] x 3 -> the kernels' NHWC qkv tensor [B, n, 3 * hidden] (q | k | v, head-major channels)."""
-    B, _, n, _ = q.shape
-    return torch.cat([t.permute(0, 2, 1, 3).reshape(B, n, HID) for t in (q, k, v)], dim=-1).contiguous()
+    B, heads, n, _ = q.shape
+    return torch.cat([t.permute(0, 2, 1, 3).reshape(B, n, heads * DH) for t in (q, k, v)], dim=-1).contiguous()
 
 
 def _unpack_out(o):
     """[B, heads, n, 32] -> [B, n, hidden]."""
-    B, _, n, _ = o.shape
-    return o.permute(0, 2, 1, 3).reshape(B, n, HID).contiguous()
+    B, heads, n, _ = o.shape
+    return o.permute(0, 2, 1, 3).reshape(B, n, heads * DH).contiguous()
 
 
 def attention_torch(qkv, dtype=torch.float32):
-    """softmax(q k^T) v per (batch, head) in plain torch (q pre-scaled), qkv and result in the kernels' layout."""
-    B, n, _ = qkv.shape
-    q, k, v = [t.reshape(B, n, HEADS, DH).permute(0, 2, 1, 3).to(dtype) for t in qkv.chunk(3, dim=-1)]
+    """softmax(q k^T) v per (batch, head) in plain torch (q pre-scaled), qkv and result in the kernels' layout (the head
+    count is the tensor's: 3 * heads * 32 channels)."""
+    B, n, c3 = qkv.shape
+    heads = c3 // (3 * DH)
+    q, k, v = [t.reshape(B, n, heads, DH).permute(0, 2, 1, 3).to(dtype) for t in qkv.chunk(3, dim=-1)]
     return _unpack_out((q @ k.transpose(-1, -2)).softmax(dim=-1) @ v)
 
 
 @functools.lru_cache(maxsize=None)
-def attention_onehot(n, B=2, key=4000):
+def attention_onehot(n, B=2, key=4000, heads=HEADS):
     """n distinct keys in {-1, +1}^32 per (batch, head), q_i = 64 k_pi(i) for a permutation pi, v integers in [-8, 8].
     The winning logit is 64 * 32 = 2048 and every other one at least 128 lower (2 * 64 per differing sign), so every
-    other exp() is zero in fp32 and the result is the gather v[pi(i)], exactly, whatever the tiling of the keys."""
+    other exp() is zero in fp32 and the result is the gather v[pi(i)], exactly, whatever the tiling of the keys.  Every
+    (batch, head) has its own keys, permutation and values: a head that reads another head's slice gathers other rows."""
     for attempt in range(8):
-        k = torch.from_numpy(np.where(rng.uniform((B, HEADS, n, DH), SEED, key + 10 * attempt) < 0.5, -1.0, 1.0).astype(np.float32))
+        k = torch.from_numpy(np.where(rng.uniform((B, heads, n, DH), SEED, key + 10 * attempt) < 0.5, -1.0, 1.0).astype(np.float32))
         top2 = (k @ k.transpose(-1, -2)).topk(2, dim=-1).values          # [.., 0] = 32 (itself), [.., 1] = the nearest other key
         if float(top2[..., 1].max()) < DH:
             break
     else:
         raise AssertionError("no draw of distinct keys")
-    pi = torch.from_numpy(np.argsort(rng.uniform((B, HEADS, n), SEED, key + 1), axis=-1))
+    pi = torch.from_numpy(np.argsort(rng.uniform((B, heads, n), SEED, key + 1), axis=-1))
     q = 64.0 * torch.gather(k, 2, pi[..., None].expand(-1, -1, -1, DH))
-    v = ints((B, HEADS, n, DH), key + 2, -8, 8)
+    v = ints((B, heads, n, DH), key + 2, -8, 8)
     gap = 64.0 * (DH - float(top2[..., 1].max()))
     assert gap >= 128.0, gap
     assert float(np.exp(np.float32(-gap))) == 0.0                         # exp of every losing logit is zero in fp32
@@ -285,28 +292,31 @@ def attention_onehot(n, B=2, key=4000):
     ref = _unpack_out(torch.gather(v, 2, pi[..., None].expand(-1, -1, -1, DH)))
     qkv = _pack_qkv(q, k, v)
     assert torch.equal(attention_torch(qkv), ref)                         # fp32 torch reproduces the gather bit for bit
+    if heads > 1:                                                         # no two heads of an image gather the same rows
+        per_head = ref.reshape(B, n, heads, DH)
+        assert all(not torch.equal(per_head[:, :, a], per_head[:, :, b]) for a in range(heads) for b in range(a))
     return NS(qkv=qkv, ref=ref, gap=gap)
 
 
 @functools.lru_cache(maxsize=None)
-def attention_uniform(n, B=2, key=4100):
+def attention_uniform(n, B=2, key=4100, heads=HEADS):
     """q = 0: every key weighs 1/n.  Even channels of v hold +-m pairs (4 <= m <= 8, one zero row if n is odd) in a
     shuffled order, so they sum to exactly zero over the keys; odd channels are the constant 1.  Expected: 0 on even
     channels, 1 on odd ones, for every query.  ``d_even`` (relative to max |v| = 8) and ``d_odd`` are fp32 torch's own
     distances from that fp64 value on this probe (it normalises P before the product)."""
-    k = torch.from_numpy(np.where(rng.uniform((B, HEADS, n, DH), SEED, key) < 0.5, -1.0, 1.0).astype(np.float32))
-    q = torch.zeros(B, HEADS, n, DH)
-    m = ints((B, HEADS, n // 2, DH), key + 1, 4, 8)
-    col = torch.cat([m, -m] + ([torch.zeros(B, HEADS, 1, DH)] if n % 2 else []), dim=2)
-    order = torch.from_numpy(np.argsort(rng.uniform((B, HEADS, n, DH), SEED, key + 2), axis=2))
+    k = torch.from_numpy(np.where(rng.uniform((B, heads, n, DH), SEED, key) < 0.5, -1.0, 1.0).astype(np.float32))
+    q = torch.zeros(B, heads, n, DH)
+    m = ints((B, heads, n // 2, DH), key + 1, 4, 8)
+    col = torch.cat([m, -m] + ([torch.zeros(B, heads, 1, DH)] if n % 2 else []), dim=2)
+    order = torch.from_numpy(np.argsort(rng.uniform((B, heads, n, DH), SEED, key + 2), axis=2))
     v = torch.gather(col, 2, order)
     v[..., 1::2] = 1.0
     assert bool((v[..., 0::2].double().sum(2) == 0).all())
     nz = v[..., 0::2].abs()
-    assert float(nz.max()) == 8.0 and float(nz[nz > 0].min()) == 4.0 and int((nz == 0).sum()) == (n % 2) * B * HEADS * (DH // 2)
+    assert float(nz.max()) == 8.0 and float(nz[nz > 0].min()) == 4.0 and int((nz == 0).sum()) == (n % 2) * B * heads * (DH // 2)
     for dt in ("bf16", "fp16"):
         check_representable(v, dt)
-    ref = torch.zeros(B, n, HID, dtype=torch.float64)
+    ref = torch.zeros(B, n, heads * DH, dtype=torch.float64)
     ref[..., 1::2] = 1.0
     qkv = _pack_qkv(q, k, v)
     assert float((attention_torch(qkv, torch.float64) - ref).abs().max()) < 1e-13     # (1/n) * (a sum that is exactly 0 or n)
@@ -318,19 +328,20 @@ def attention_uniform(n, B=2, key=4100):
 
 # --------------------------------------------------------------------------------------------- fused linear attention (1f)
 @functools.lru_cache(maxsize=None)
-def linattn_uniform(C, H, W, B=2, key=5000):
+def linattn_uniform(C, H, W, B=2, key=5000, heads=HEADS):
     """to_qkv with all k rows zero (the k softmax over the pixels is uniform, its maximum and any Cauchy-Schwarz
-    shift are 0) and v rows that each select ONE input channel.  x is +-1 on ``nnz`` channels per pixel (all 64 for
-    C = 64, the even ones for C = 32) and 0 elsewhere, so the pixel norm is sqrt(nnz) = 8 or 4, and with
-    g * sqrt(C) = ``scale`` = that power of two the RMS-normalised value, hence v, is +-1 up to the error of the
-    reciprocal norm.  Non-zero channel j is balanced (sums to zero over the pixels) for even j and constant (+1 for
-    j = 1 mod 4, -1 for j = 3 mod 4) for odd j; v row (h, e) selects non-zero channel (32 h + e) mod nnz, so even e are
-    balanced and odd e constant.  Expected: ctxn[b, h, d, e] = mean_n v_e, the same for every d: 0 or +-1."""
+    shift are 0) and v rows that each select ONE input channel.  x is +-1 on ``nnz`` channels per pixel (64 of them for
+    C >= 64 -- all of C = 64, the even ones of C = 128 -- and the 16 even ones for C = 32) and 0 elsewhere, so the
+    pixel norm is sqrt(nnz) = 8 or 4, and with g * sqrt(C) = ``scale`` = that power of two the RMS-normalised value,
+    hence v, is +-1 up to the error of the reciprocal norm.  Non-zero channel j is balanced for even j (sums to zero
+    over an even number of pixels, to +1 over an odd one: ceil(n / 2) pixels hold +1) and constant (+1 for j = 1 mod 4,
+    -1 for j = 3 mod 4) for odd j; v row (h, e) selects non-zero channel (32 h + e) mod nnz, so even e are balanced and
+    odd e constant.  Expected: ctxn[b, h, d, e] = mean_n v_e, the same for every d: 0 (1 / n for odd n) or +-1."""
     n = H * W
-    assert n % 2 == 0
-    nnz = 64 if C == 64 else 16
-    chans = torch.arange(C) if C == 64 else torch.arange(0, C, 2)
-    half = torch.cat([torch.ones(n // 2), -torch.ones(n // 2)])
+    hid = heads * DH
+    nnz = 64 if C >= 64 else 16
+    chans = torch.arange(0, C, C // nnz)
+    half = torch.cat([torch.ones(n - n // 2), -torch.ones(n // 2)])
     xs = torch.empty(B, nnz, n)
     order = torch.from_numpy(np.argsort(rng.uniform((B, nnz, n), SEED, key), axis=-1))
     xs[:] = half[order]
@@ -341,21 +352,194 @@ def linattn_uniform(C, H, W, B=2, key=5000):
     x = x.reshape(B, C, H, W)
     assert bool((x.double().pow(2).sum(1) == nnz).all())
     scale = float(nnz) ** 0.5                                              # g * sqrt(C): 8 or 4
-    w = torch.zeros(3 * HID, C)
-    sel = torch.tensor([[(DH * h + e) % nnz for e in range(DH)] for h in range(HEADS)])
-    for h in range(HEADS):
+    w = torch.zeros(3 * hid, C)
+    sel = torch.tensor([[(DH * h + e) % nnz for e in range(DH)] for h in range(heads)])
+    for h in range(heads):
         for e in range(DH):
-            w[2 * HID + DH * h + e, chans[sel[h, e]]] = 1.0
-    v64 = xs.double()[:, sel.flatten()].reshape(B, HEADS, DH, n)           # exact v: +-1
-    mean = v64.mean(-1)                                                    # [B, heads, e]
-    assert is_integer(mean) and bool((mean[..., 0::2] == 0).all()) and bool((mean[..., 1::2].abs() == 1).all())
-    ref = mean[:, :, None, :].expand(B, HEADS, DH, DH).contiguous()
+            w[2 * hid + DH * h + e, chans[sel[h, e]]] = 1.0
+    v64 = xs.double()[:, sel.flatten()].reshape(B, heads, DH, n)           # exact v: +-1
+    total = v64.sum(-1)                                                    # [B, heads, e]: an exact integer
+    assert bool((total[..., 0::2] == n % 2).all()) and bool((total[..., 1::2].abs() == n).all())
+    mean = total / n
+    ref = mean[:, :, None, :].expand(B, heads, DH, DH).contiguous()
     # fp32 torch on the same probe: F.normalize * scale, the 1x1 projection, softmax over the pixels, the context
     xn = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) * scale
-    kv = F.conv2d(xn, w[:, :, None, None]).reshape(B, 3, HEADS, DH, n)
+    kv = F.conv2d(xn, w[:, :, None, None]).reshape(B, 3, heads, DH, n)
     t32 = torch.einsum("bhdn,bhen->bhde", kv[:, 1].softmax(dim=-1), kv[:, 2]).double()
     d = float((t32 - ref).abs().max())                                     # relative to |v| = 1
     return NS(x=x, w=w[:, :, None, None].contiguous(), scale=torch.full((C,), scale), ref=ref, d=d)
+
+
+# --------------------------------------------------------------------------------------------- fused linear attention, output half (1g)
+LINOUT_CHANNELS = [32, 64, 128]
+LINOUT_SIZES = [49, 196, 784, 1024]         # one partial 128-pixel tile; a tile + a tail whose last 16-group holds 4 pixels;
+                                            # six tiles + a 16-pixel tail; full tiles only
+QWIN = 128.0                                # the winning q logit: exp(-128) is zero in fp32 (and exp2(-128 log2 e) on the device)
+
+
+def linout_contract(x, wq, ctxn, wout, bias, g2, q_scale=1.0, dtype=None):
+    """What ld_linattn_out computes, in fp64: out = RMSNorm(M_b (softmax_d(W_q x / |x|) * q_scale) + bias) * g2 + x with
+    M_b[c, 32 h + d] = sum_e W_out[c, 32 h + e] ctxn[b, h, d, e] (ld_linattn_fold).  x [B, C, n]; wq [128, C] with
+    g sqrt(C) folded in (the sum of the stored terms, or the unrounded product); ctxn [B, 4, 32, 32]; wout [C, 128]; g2 =
+    to_out.1.g * sqrt(C).  ``dtype``: the kernel's two internal rounding points -- M_b and the scaled softmax as storage
+    holds them (both are operands of the second matrix product) -- and the stored output; None: no rounding at all."""
+    B, C, n = x.shape
+    rnd = (lambda t: t) if dtype is None else (lambda t: t.float().to(TDT[dtype]).double())
+    x, wq, ctxn, wout, bias, g2 = (t.double() for t in (x, wq, ctxn, wout, bias, g2))
+    M = rnd(torch.einsum("che,bhde->bchd", wout.reshape(C, HEADS, DH), ctxn).reshape(B, C, HID))
+    xn = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    q = torch.einsum("kc,bcn->bkn", wq, xn).reshape(B, HEADS, DH, n)
+    q = rnd(q.softmax(dim=2) * q_scale).reshape(B, HID, n)
+    y = torch.einsum("bck,bkn->bcn", M, q) + bias[None, :, None]
+    return rnd(y / y.norm(dim=1, keepdim=True).clamp_min(1e-12) * g2[None, :, None] + x)
+
+
+def _linout_tail(C, key):
+    """The part both probes share: bias +-2, a target y in {-1, +1} per (channel, k-slot) reached by W_out = y - bias in
+    {-3, -1, 1, 3}, and the gain g2 = k_c sqrt(C) with k_c in +-{1..4}.  Every |y_c| is 1, so RMSNorm gives +-1 / sqrt(C)
+    and the block's value is y_c k_c + x: an integer, |.| <= 36, which 16-bit storage holds exactly although
+    fl(1 / sqrt(C)) * fl(k sqrt(C)) is only k (1 + 1e-7) for C = 32 and 128 -- as long as the sum does not cancel to 0,
+    where that 1e-7 would be all that is left: the probes' x is 0 or a multiple of 8, |k_c| <= 4."""
+    sign = lambda shape, k: torch.from_numpy(np.where(rng.uniform(shape, SEED, k) < 0.5, -1.0, 1.0).astype(np.float32))
+    bias = 2.0 * sign((C,), key)
+    target = sign((C, HID), key + 1)
+    gain = ints((C,), key + 2, 1, 4) * sign((C,), key + 3)
+    g2 = (gain.double() * float(C) ** 0.5).float()
+    return bias, target, gain, g2
+
+
+def _linout_check(p, integer_limit=36.0):
+    """Preconditions of a linout probe: the fp64 contract gives the stated integers (to 1e-12), with the kernel's
+    rounding points too, for both storage types; and an fp32 evaluation, stored once, gives them bit for bit."""
+    assert is_integer(p.ref) and 1.0 <= float(p.ref.abs().min()) and float(p.ref.abs().max()) <= integer_limit
+    for dt in ("bf16", "fp16"):
+        for t in (p.x, p.wq, p.wout, p.bias, p.ctxn):
+            check_representable(t, dt)
+        assert float((linout_contract(p.x, p.wq, p.ctxn, p.wout, p.bias, p.g2) - p.ref.double()).abs().max()) < 1e-6     # g2 is an fp32 value
+        assert torch.equal(linout_contract(p.x, p.wq, p.ctxn, p.wout, p.bias, p.g2, dtype=dt), p.ref.double())
+    B, C, n = p.x.shape
+    M = torch.einsum("che,bhde->bchd", p.wout.reshape(C, HEADS, DH), p.ctxn).reshape(B, C, HID)          # fp32 throughout
+    q = torch.einsum("kc,bcn->bkn", p.wq, p.x / p.x.norm(dim=1, keepdim=True).clamp_min(1e-12)).reshape(B, HEADS, DH, n)
+    y = torch.einsum("bck,bkn->bcn", M, q.softmax(dim=2).reshape(B, HID, n)) + p.bias[None, :, None]
+    out32 = y * torch.rsqrt((y * y).sum(1, keepdim=True)) * p.g2[None, :, None] + p.x
+    for dt in ("bf16", "fp16"):
+        assert torch.equal(stored(out32, dt), p.ref)
+
+
+def linout_sel(h, j):
+    """The q channel (within head h) that input channel j selects in the one-hot probe: all 32 for every head."""
+    return (j + 8 * h + j // DH) % DH
+
+
+@functools.lru_cache(maxsize=None)
+def linout_onehot(C, n, key=6000):
+    """ld_linattn_out with B = 4.  Every pixel of x has ONE non-zero channel j (a draw per pixel) holding 8, 16 or 32, so
+    the normalised pixel is the unit vector e_j whatever the reciprocal norm's last bit is; W_q[32 h + sel(h, j), j] =
+    128 and 0 elsewhere (scale = 1), so in every head the winning logit is 128 and the 31 others 0: every other exp is
+    zero and softmax_d(q) is exactly one-hot at d = sel(h, j) -- with the per-pixel maximum and with qshift = 128 alike.
+    ctxn[b] is the identity for head b mod 4 and zero for the others, so M_b is the head's block of W_out and
+    y_c = W_out[c, 32 (b mod 4) + sel(b mod 4, j)] + bias_c = +-1 (``_linout_tail``).  Expected: y_c k_c + x, integers.
+    A q channel in another k-slot or a head taken twice picks another column of W_out (another sign pattern over c), a
+    wrong M_b batch offset another head's block, a residual from the wrong fragment moves the one non-zero x."""
+    B = 4
+    bias, target, gain, g2 = _linout_tail(C, key)
+    j = ints((B, n), key + 10, 0, C - 1).long()
+    a = 2.0 ** ints((B, n), key + 11, 3, 5)
+    x = torch.zeros(B, C, n)
+    x.scatter_(1, j[:, None, :], a[:, None, :])
+    wq = torch.zeros(HID, C)
+    for h in range(HEADS):
+        for c in range(C):
+            wq[DH * h + linout_sel(h, c), c] = QWIN
+    ctxn = torch.zeros(B, HEADS, DH, DH)
+    for b in range(B):
+        ctxn[b, b % HEADS] = torch.eye(DH)
+    wout = target - bias[:, None]
+    hb = torch.arange(B) % HEADS
+    col = DH * hb[:, None] + linout_sel(hb[:, None], j)                     # [B, n]: the one k-slot that is switched on
+    ref = target[:, col].permute(1, 0, 2) * gain[None, :, None] + x       # [B, C, n]
+    assert all(len({linout_sel(h, c) for c in range(DH)}) == DH for h in range(HEADS))
+    assert len(set(j.flatten().tolist())) == C or n < 4 * C               # every channel is some pixel's (at the larger sizes)
+    p = NS(x=x, wq=wq, scale=torch.ones(C), ctxn=ctxn, wout=wout, bias=bias, g2=g2, ref=ref, qshift=torch.full((HEADS,), QWIN))
+    _linout_check(p)
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+def linout_uniform(C, n, key=6100):
+    """ld_linattn_out with W_q = 0 (B = 2): q is 0, softmax_d(q) is 1 / 32 for every d -- with the per-pixel maximum and
+    with qshift = 0 -- and the second product is the row sum of M_b over all 128 k-slots / 32.  ctxn[b, h] is a
+    permutation matrix (a draw per batch and head), so M_b is W_out with the columns of each head permuted: entries +-1,
+    row c holding (128 + S_c) / 2 ones with S_c = 32 (y_c - bias_c) in {+-32, +-96}; every partial sum is a multiple of
+    1 / 32 below 4, exact in any order.  x: multiples of 8 in [-16, 16].  Expected: y_c k_c + x (``_linout_tail``)."""
+    B = 2
+    bias, target, gain, g2 = _linout_tail(C, key)
+    t = target[:, 0]                                                       # y_c
+    S = (32 * (t - bias)).long()
+    assert set(S.tolist()) <= {-96, -32, 32, 96}
+    wout = torch.empty(C, HID)
+    order = torch.from_numpy(np.argsort(rng.uniform((C, HID), SEED, key + 10), axis=-1))
+    for c in range(C):
+        plus = (HID + int(S[c])) // 2
+        row = torch.cat([torch.ones(plus), -torch.ones(HID - plus)])
+        wout[c] = row[order[c]]
+    assert torch.equal(wout.sum(1).long(), S)
+    perm = torch.from_numpy(np.argsort(rng.uniform((B, HEADS, DH), SEED, key + 11), axis=-1))
+    ctxn = torch.zeros(B, HEADS, DH, DH)
+    ctxn.scatter_(3, perm[..., None], 1.0)
+    assert bool((ctxn.sum(2) == 1).all()) and bool((ctxn.sum(3) == 1).all())
+    x = 8.0 * ints((B, C, n), key + 12, -2, 2)
+    ref = (t * gain)[None, :, None] + x
+    p = NS(x=x, wq=torch.zeros(HID, C), scale=torch.ones(C), ctxn=ctxn, wout=wout, bias=bias, g2=g2, ref=ref, qshift=torch.zeros(HEADS))
+    _linout_check(p)
+    return p
+
+
+def linout_swapped_slots(p, dtype="bf16"):
+    """The mutation the one-hot probe is for, in torch: k-slots 4 and 20 of every head's M_b exchanged (two channel slots
+    of the chained-operand order of ld_linattn_fold(perm = 1) swapped).  Returns the block's stored value."""
+    idx = torch.arange(HID)
+    d = idx % DH
+    idx = torch.where(d == 4, idx + 16, torch.where(d == 20, idx - 16, idx))
+    return linout_contract(p.x, p.wq[idx], p.ctxn, p.wout, p.bias, p.g2, dtype=dtype).float()
+
+
+@functools.lru_cache(maxsize=None)
+def linout_random(C, n, dtype, sharp=False, key=6200):
+    """Random operands for ld_linattn_out (B = 2): x in [-1, 1] (as storage holds it: it is the kernel's input, not one of
+    its roundings), to_qkv's q rows in [-0.3, 0.3] with norm.g in [0.5, 1.5], to_out.0 in [-0.3, 0.3], its bias in
+    [-1, 1], to_out.1.g in [2, 4] -- the attention branch is at least as large as the residual --, and a context of
+    the magnitude a softmax context has: ctxn = softmax_n(k) v^T of random k, v in [-1.5, 1.5] over 64 pixels.  ``ref``:
+    the fp64 value of the UNROUNDED operands; ``rest[terms]``: linout_contract with W_q as one or two stored terms and
+    the kernel's rounding points; ``d[terms]``: its distance from ref (max |.| / max |ref|).  ``sharp``: the q rows times
+    16 -- logits of +-20, where the rounding of W_q moves softmax_d(q) by more than its own rounding to storage does, so
+    that the second weight term shows in the output (with the plain draw it disappears behind the roundings of q and of
+    the output: d[2] / d[1] is 1 to three digits)."""
+    B = 2
+    u = lambda shape, k, lo=-1.0, hi=1.0: torch.from_numpy(rng.uniform(shape, SEED, key + k, lo, hi))
+    x = u((B, C, n), 0).to(TDT[dtype]).float()
+    g = u((C,), 1, 0.5, 1.5)
+    scale = (g * float(C) ** 0.5).contiguous()
+    wq = u((HID, C), 2, -0.3, 0.3) * (16.0 if sharp else 1.0)
+    wout, bias = u((C, HID), 3, -0.3, 0.3), u((C,), 4)
+    g2 = (u((C,), 5, 2.0, 4.0) * float(C) ** 0.5).contiguous()
+    k, v = u((B, HEADS, DH, 64), 6, -1.5, 1.5), u((B, HEADS, DH, 64), 7, -1.5, 1.5)
+    ctxn = torch.einsum("bhdn,bhen->bhde", k.double().softmax(dim=-1), v.double()).float()
+    q_scale = DH ** -0.5
+    ws = wq * scale[None, :]                                               # fp32, as ld_pack_conv_weight_terms forms it
+    hi = ws.to(TDT[dtype]).float()
+    lo = (ws - hi).to(TDT[dtype]).float()
+    ref = linout_contract(x, wq.double() * scale.double()[None, :], ctxn, wout, bias, g2, q_scale)
+    rest = {1: linout_contract(x, hi, ctxn, wout, bias, g2, q_scale, dtype=dtype),
+            2: linout_contract(x, hi.double() + lo.double(), ctxn, wout, bias, g2, q_scale, dtype=dtype)}
+    top = float(ref.abs().max())
+    d = {t: float((r - ref).abs().max()) / top for t, r in rest.items()}
+    d_rms = {t: float((r - ref).pow(2).mean().sqrt()) / top for t, r in rest.items()}
+    branch = float((ref - x.double()).abs().max())
+    assert branch >= float(x.abs().max())                                  # the attention branch is not hidden behind the residual
+    qb = (hi.norm(dim=1) * 1.01).reshape(HEADS, DH).amax(dim=1)            # the Cauchy-Schwarz bound of q per head (unet.py)
+    return NS(x=x, wq=wq, scale=scale, ctxn=ctxn, wout=wout, bias=bias, g2=g2, q_scale=q_scale, qshift=qb.contiguous(), ref=ref,
+              rest=rest, d=d, d_rms=d_rms, top=top)
 
 
 # --------------------------------------------------------------------------------------------- the motivating mutation

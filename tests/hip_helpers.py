@@ -119,6 +119,43 @@ def conv1x1(srcs, wpacked, B, H, W, cout, dtype, bias=None, epi=0, unshuffle=0, 
     return out
 
 
+SENTINEL = -1024.0
+
+
+def linattn_out(p, dtype, terms=1, qshift=None, q_scale=1.0, expect_refusal=False):
+    """ld_linattn_out_terms driven by itself on a probe of tests/exact_probes.py (x [B, C, n], wq [128, C] + scale, ctxn,
+    wout [C, 128], bias, g2): W_q from ld_pack_conv_weight_terms, M_b from ld_linattn_fold(perm = 1).  The output buffer
+    holds NaN and one extra pixel row of SENTINEL behind the last pixel: every pixel must come back finite and the extra
+    row untouched (the store predicate p < n).  Returns the output as [B, C, n] fp32 on the CPU; with ``expect_refusal``
+    the call must return -1 and leave the whole buffer as it was."""
+    lib, dt, tdt = cabi.lib(), cabi.dtype_code(dtype), TDT[dtype]
+    B, Cc, n = p.x.shape
+    hid = p.wq.shape[0]
+    xd = p.x.permute(0, 2, 1).contiguous().to(DEV, tdt)
+    wq, scale = p.wq.to(DEV, torch.float32).contiguous(), p.scale.to(DEV, torch.float32).contiguous()
+    wqp = nans(terms * wq.numel(), dtype=tdt)
+    cabi.check(lib.ld_pack_conv_weight_terms(wq.data_ptr(), scale.data_ptr(), wqp.data_ptr(), hid, Cc, 1, 0, dt, terms, st()), "pack")
+    ctxn, wout = p.ctxn.to(DEV, torch.float32).contiguous(), p.wout.to(DEV, torch.float32).contiguous()
+    wfold = nans(B, Cc * hid, dtype=tdt)
+    cabi.check(lib.ld_linattn_fold(ctxn.data_ptr(), wout.data_ptr(), wfold.data_ptr(), B, Cc, hid // 32, 32, 1, dt, st()), "fold")
+    assert bool(torch.isfinite(wfold.float()).all()) and bool(torch.isfinite(wqp.float()).all())
+    buf = nans(B * n + 1, Cc, dtype=tdt)
+    buf[-1] = SENTINEL
+    bias, g2 = p.bias.to(DEV, torch.float32).contiguous(), p.g2.to(DEV, torch.float32).contiguous()
+    qs = None if qshift is None else qshift.to(DEV, torch.float32).contiguous()
+    rc = lib.ld_linattn_out_terms(xd.data_ptr(), wqp.data_ptr(), cabi.ptr(qs), wfold.data_ptr(), bias.data_ptr(), g2.data_ptr(),
+                                  buf.data_ptr(), B, n, Cc, q_scale, dt, terms, st())
+    torch.cuda.synchronize()
+    got = buf.float().cpu()
+    assert bool((got[-1] == SENTINEL).all()), "the row behind the last pixel was written"
+    if expect_refusal:
+        assert rc == -1 and bool(torch.isnan(got[:-1]).all())
+        return None
+    cabi.check(rc, "linattn_out")
+    assert bool(torch.isfinite(got[:-1]).all()), f"{int((~torch.isfinite(got[:-1])).any(-1).sum())} pixels not written"
+    return got[:-1].reshape(B, n, Cc).permute(0, 2, 1).contiguous()
+
+
 def gn_stats_ref(y, groups):
     """[B, groups, 2] fp64 (sum, sumsq) of an NCHW fp32 tensor."""
     B, Cc = y.shape[:2]

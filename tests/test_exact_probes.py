@@ -103,6 +103,87 @@ def test_linattn_probes(C, H, W):
     assert float((kv[:, 256:].abs().round() - kv[:, 256:].abs()).abs().max()) < 1e-6
 
 
+@pytest.mark.parametrize("heads", P.OTHER_HEADS)
+@pytest.mark.parametrize("n", P.ATTN_HEADS_SIZES)
+def test_attention_probes_at_other_head_counts(n, heads):
+    """The builders with a ``heads`` parameter (tests/test_hip_attention_heads.py): the same preconditions, a tensor of
+    3 * heads * 32 channels, and the default head count still gives the tensors it gave."""
+    p, u = P.attention_onehot(n, heads=heads), P.attention_uniform(n, heads=heads)
+    assert p.qkv.shape == u.qkv.shape == (2, n, 96 * heads) and p.ref.shape == u.ref.shape == (2, n, 32 * heads)
+    assert 4.0 / (n + 1) / 8.0 > 10 * max(1e-5, 4 * u.d_even)
+    assert P.attention_onehot(n, heads=4) is P.attention_onehot(n, heads=P.HEADS) and P.attention_onehot(n, heads=4).qkv.shape[-1] == 384
+
+
+@pytest.mark.parametrize("heads", P.OTHER_HEADS)
+@pytest.mark.parametrize("C,H,W", P.KVCTX_HEADS_SHAPES)
+def test_linattn_probes_at_other_head_counts(C, H, W, heads):
+    """C = 128 (64 of its channels non-zero) and an odd pixel count (7 x 7: the balanced channels sum to +1, the
+    expected context there is 1 / 49) are new with these shapes."""
+    p = P.linattn_uniform(C, H, W, heads=heads)
+    n = H * W
+    print(f"linattn C={C} n={n} heads={heads}: fp32 torch distance {p.d:.2e}")
+    assert p.ref.shape == (2, heads, 32, 32) and p.w.shape == (96 * heads, C, 1, 1)
+    assert 1.0 / (n + 1) > 10 * max(1e-5, 4 * p.d)
+    assert float(p.ref[..., 0::2].abs().max()) == (n % 2) / n and bool((p.ref[..., 1::2].abs() == 1).all())
+    g = (p.scale / C ** 0.5).reshape(1, C, 1, 1)
+    kv = F.conv2d(unet_ref.rms_norm(p.x, g), p.w)
+    hid = 32 * heads
+    assert float(kv[:, hid:2 * hid].abs().max()) == 0.0
+    assert float((kv[:, 2 * hid:].abs() - 1).abs().max()) < 1e-6
+
+
+@pytest.mark.parametrize("n", P.LINOUT_SIZES)
+@pytest.mark.parametrize("C", P.LINOUT_CHANNELS)
+def test_linout_probes(C, n):
+    """Calling the builders proves them (_linout_check).  And what the one-hot probe is for: two k-slots of the chained
+    operand exchanged change stored outputs on it, at every shape, while the uniform probe cannot see that."""
+    p, u = P.linout_onehot(C, n), P.linout_uniform(C, n)
+    assert p.x.shape == (4, C, n) and u.x.shape == (2, C, n)
+    assert int((p.x != 0).sum()) == 4 * n                                   # one non-zero channel per pixel
+    for dt in ("bf16", "fp16"):
+        bad = P.linout_swapped_slots(p, dt)
+        assert not torch.equal(bad, p.ref)
+        assert torch.equal(P.linout_swapped_slots(u, dt), u.ref)
+    print(f"linout one-hot C={C} n={n}: {int((bad != p.ref).sum())} of {bad.numel()} outputs differ with k-slots 4 and 20 exchanged")
+
+
+def test_linout_contract_is_the_oracle_block():
+    """linout_contract without rounding, fed the oracle's own context, IS LinearAttention.forward + x (fp64 vs the fp32
+    oracle): the reference of the random-operand test restates the right operation."""
+    B, C, H, W = 2, 64, 9, 11
+    n = H * W
+    r = lambda shape, key, lo=-1.0, hi=1.0: torch.from_numpy(rng.uniform(shape, 1234, key, lo, hi))
+    x = r((B, C, H, W), 1, -2, 2)
+    sd = {"a.norm.g": r((1, C, 1, 1), 2, 0.5, 1.5), "a.to_qkv.weight": r((384, C, 1, 1), 3, -0.3, 0.3),
+          "a.to_out.0.weight": r((C, 128, 1, 1), 4, -0.3, 0.3), "a.to_out.0.bias": r((C,), 5), "a.to_out.1.g": r((1, C, 1, 1), 6, 2.0, 4.0)}
+    ref = unet_ref.linear_attention(sd, "a", x) + x
+    _, k, v = [t.reshape(B, 4, 32, n) for t in F.conv2d(unet_ref.rms_norm(x, sd["a.norm.g"]), sd["a.to_qkv.weight"]).chunk(3, dim=1)]
+    ctxn = torch.einsum("bhdn,bhen->bhde", k.softmax(dim=-1), v)
+    scale = sd["a.norm.g"].flatten() * C ** 0.5
+    got = P.linout_contract(x.reshape(B, C, n), sd["a.to_qkv.weight"][:128, :, 0, 0] * scale[None, :], ctxn, sd["a.to_out.0.weight"][:, :, 0, 0],
+                            sd["a.to_out.0.bias"], sd["a.to_out.1.g"].flatten() * C ** 0.5, 32 ** -0.5)
+    err = float((got.reshape(B, C, H, W) - ref.double()).abs().max()) / float(ref.abs().max())
+    print(f"linout_contract vs the oracle block: {err:.2e}")
+    assert err < 1e-5
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("C", P.LINOUT_CHANNELS)
+def test_linout_random_operands(C, dtype):
+    """The restatement's own distance d from the unrounded fp64 value, per weight-term count (what the GPU test's
+    max(floor, 2 d) is made of): a few storage half-ulps of the largest output, and two terms are not worse than one."""
+    for n in (49, 1024):
+        p = P.linout_random(C, n, dtype)
+        print(f"linout random C={C} n={n} {dtype}: d one term {p.d[1]:.2e}, two terms {p.d[2]:.2e}, max |ref| {p.top:.2f}")
+        ulp = 2.0 ** -8 if dtype == "bf16" else 2.0 ** -11
+        assert 0.25 * ulp < p.d[1] < 8 * ulp and p.d[2] <= p.d[1] * 1.05
+        assert float((p.qshift[:, None] - (p.wq * p.scale[None, :]).norm(dim=1).reshape(4, 32)).min()) > 0
+        assert float(p.qshift.max()) <= 40.0                                 # a bound the product code would pass on (unet.py)
+        s = P.linout_random(C, n, dtype, sharp=True)
+        print(f"   sharp: d one term {s.d[1]:.2e}, two terms {s.d[2]:.2e}; rms {s.d_rms[1]:.3e}, {s.d_rms[2]:.3e} ({s.d_rms[2] / s.d_rms[1]:.3f})")
+        assert s.d_rms[2] < 0.995 * s.d_rms[1]                               # here the second term shows
+
+
 def _emulated_bf16(conv, x, w, b):
     """A clean bf16 kernel: fp32 arithmetic on bf16-rounded operands, the output rounded once."""
     q = lambda t: t.to(torch.bfloat16).float()

@@ -432,3 +432,56 @@ def test_linattn_kvctx_uniform(dtype, C_, H, W):
                                                   hh.st()), "ctxfold")
                 assert bool(torch.isfinite(wfold.float()).all())
                 assert torch.equal(wfold2, wfold), (terms, single, perm)
+
+
+LINOUT_CASES = [(C_, terms) for C_ in P.LINOUT_CHANNELS for terms in (1, 2) if (C_, terms) != (128, 2)]
+
+
+@pytest.mark.parametrize("dtype", LOWP)
+@pytest.mark.parametrize("n", P.LINOUT_SIZES)
+@pytest.mark.parametrize("C_,terms", LINOUT_CASES)
+def test_linattn_out_one_hot(dtype, C_, terms, n):
+    """ld_linattn_out / _terms by itself (hip_helpers.linattn_out: chosen ctxn, M_b from ld_linattn_fold(perm = 1), W_q from
+    ld_pack_conv_weight_terms) on the one-hot probe: softmax_d(q) switches on ONE k-slot per head, M_b is one head's block
+    of W_out, the block's value y_c k_c + x is an integer -- torch.equal, with the per-pixel maximum and with qshift, one
+    and two weight terms, a partial tile (n = 49), a tail whose last 16-pixel group holds 4 pixels (196), a 16-pixel tail
+    (784) and full tiles (1024); the row behind the last pixel stays untouched and every pixel is written.
+    Measured on the MI355X (printed per case): 0 outputs differ in all 40 cases, both shift modes -- the hardware rsq / rcp
+    errors, if any, disappear in the roundings of q and of the output, as the builder's docstring argues.  With k-slots 4
+    and 20 of every head exchanged in the perm = 1 mapping of ld_linattn_fold / _ctxfold (an in-bounds change, built on a
+    scratch copy) this test fails in all 40 cases: 2.6 - 4.1 % of the outputs differ, by up to 8 -- exactly the outputs
+    exact_probes.linout_swapped_slots predicts on the CPU (200 of 6272 at C = 32, n = 49; 641 of 25088 at n = 196) --,
+    test_linattn_out_uniform passes all 40 (every k-slot carries 1 / 32), the random-operand test of test_hip_ops.py
+    fails all 24 (e / d 4.7 - 75), and test_hip_ops.test_linear_attention_fused_16bit PASSES its four bf16 cases at
+    C = 32 (it reads 1.6e-2 at 28 x 28 and 2.3e-2 at 64 x 96 against its 6e-2) and fails the other twelve (fp16 at C = 32
+    by 1.6e-2 against 1.5e-2; C = 64 reads 8.1e-2, C = 128 2.0e-1)."""
+    p = P.linout_onehot(C_, n)
+    for qshift in (None, p.qshift):
+        got = hh.linattn_out(p, dtype, terms, qshift)
+        bad = got != p.ref
+        print(f"linout one-hot C={C_} n={n} {dtype} terms={terms} {'qshift' if qshift is not None else 'max'}: {int(bad.sum())} of {bad.numel()} differ, "
+              f"max |diff| {float((got - p.ref).abs().max()):.2e}")
+        assert torch.equal(got, p.ref), (qshift is not None, int(bad.sum()), int(bad.any(1).sum()), "outputs / pixels differ")
+
+
+@pytest.mark.parametrize("dtype", LOWP)
+@pytest.mark.parametrize("n", P.LINOUT_SIZES)
+@pytest.mark.parametrize("C_,terms", LINOUT_CASES)
+def test_linattn_out_uniform(dtype, C_, terms, n):
+    """W_q = 0: softmax_d(q) = 1 / 32 on all 128 k-slots (with the max reduction and with qshift = 0), M_b = W_out with
+    permuted columns (+-1): the second product is a row sum of 128 terms / 32, exact in any order; torch.equal.
+    Measured on the MI355X: 0 outputs differ in all 40 cases, with the max reduction and with qshift = 0."""
+    p = P.linout_uniform(C_, n)
+    for qshift in (None, p.qshift):
+        got = hh.linattn_out(p, dtype, terms, qshift)
+        bad = got != p.ref
+        print(f"linout uniform C={C_} n={n} {dtype} terms={terms} {'qshift' if qshift is not None else 'max'}: {int(bad.sum())} of {bad.numel()} differ, "
+              f"max |diff| {float((got - p.ref).abs().max()):.2e}")
+        assert torch.equal(got, p.ref), (qshift is not None, int(bad.sum()))
+
+
+@pytest.mark.parametrize("dtype", LOWP)
+def test_linattn_out_refuses_two_terms_at_128_channels(dtype):
+    """Two-term W_q is built for C = 32 / 64: C = 128 returns -1 and writes nothing (the NaN-filled output and the row
+    behind it are as they were)."""
+    hh.linattn_out(P.linout_uniform(128, 49), dtype, terms=2, expect_refusal=True)
