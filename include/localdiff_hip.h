@@ -777,6 +777,11 @@ int ld_mc_adam(const ld_mc_adam_tensor* tensors, int count, double beta1, double
 int ld_p_losses_grad(const float* model_out, const float* x_start, const float* noise, const int* t, const float* sqrt_ab,
                      const float* sqrt_1mab, const float* loss_weight, float g, float* d_model_out, int B,
                      int64_t elems_per_sample, int objective, void* stream);
+/* The same with the upstream scalar g * *dev_scale: dev_scale points at one float in device memory, the loss scale of
+ * ld_dn_scaler_state (amp = "fp16"); nothing waits for it. */
+int ld_p_losses_grad_scaled(const float* model_out, const float* x_start, const float* noise, const int* t, const float* sqrt_ab,
+                            const float* sqrt_1mab, const float* loss_weight, float g, const float* dev_scale, float* d_model_out,
+                            int B, int64_t elems_per_sample, int objective, void* stream);
 /* Bytes of the `work` scratch of the two entry points below (0 for a shape they refuse). */
 int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C);
 /* GroupNorm (training mode: statistics of this batch) -> FiLM -> SiLU over y [B, H, W, ldc] (a convolution output, bias
@@ -1072,6 +1077,37 @@ int ld_dn_opt_step(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, float
                    float* ema, int64_t flat_floats, const double* sumsq, double max_norm, double beta1, double beta2, double eps,
                    double step_size, double bc2_sqrt, int ema_mode, float ema_w, void* stream);
 
+/* Loss scaling (amp = "fp16"): torch.amp.GradScaler's state and decisions in device memory.  The gradients are produced
+ * multiplied by `scale` (ld_p_losses_grad_scaled reads it on the device); ld_dn_opt_sqnorm / ld_dn_opt_reduce give the squared
+ * norm of those scaled gradients, which is non-finite exactly when one of them is; ld_dn_opt_scaler_update decides and
+ * ld_dn_opt_step_scaled acts, so the host never waits for the decision. */
+typedef struct ld_dn_scaler_state {
+  float scale;             /* the loss scale the NEXT gradients are produced with */
+  int32_t growth_tracker;  /* finite steps in a row since the scale last changed (GradScaler._growth_tracker) */
+  int32_t adam_steps;      /* optimiser steps that were not skipped: Adam's own step count */
+  int32_t skipped_steps;
+  int32_t found_inf;       /* the last step's flag: 1 = it was skipped */
+  float inv_scale;         /* (float)(1 / (double)scale) of the scale the last gradients were produced with */
+  float step_size;         /* lr / (1 - beta1^adam_steps), rounded to fp32 as ld_dn_opt_step rounds its argument */
+  float bc2_sqrt;          /* sqrt(1 - beta2^adam_steps), the same way */
+} ld_dn_scaler_state;
+/* One thread fills *state (device): scale = init_scale (positive, finite), the two counts as given, skipped_steps = found_inf =
+ * 0, inv_scale = 1 / scale. */
+int ld_dn_scaler_init(ld_dn_scaler_state* state, float init_scale, int adam_steps, int growth_tracker, void* stream);
+/* One thread, between the norm and the step: found_inf = !isfinite(*sumsq); inv_scale from the current scale; a finite norm
+ * counts an Adam step and computes step_size and bc2_sqrt for it in fp64 (pow), a non-finite one counts a skipped step; then
+ * torch's _amp_update_scale_: found_inf -> scale *= backoff_factor, tracker = 0; else tracker += 1 and at growth_interval
+ * scale *= growth_factor (only if the product is finite) and tracker = 0.  growth_factor > 1, 0 < backoff_factor < 1,
+ * growth_interval >= 1. */
+int ld_dn_opt_scaler_update(ld_dn_scaler_state* state, const double* sumsq, double lr, double beta1, double beta2,
+                            double growth_factor, double backoff_factor, int growth_interval, void* stream);
+/* ld_dn_opt_step with found_inf, inv_scale, step_size and bc2_sqrt read from *state: coef from sqrt(*sumsq) * inv_scale, the
+ * gradient (g * inv_scale) * coef (torch unscales in place, then clips; with a power-of-two scale both products are exact).
+ * On found_inf the parameters and both moments keep their bits; either way the gradient is zeroed and the EMA acts. */
+int ld_dn_opt_step_scaled(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, float* grad, float* exp_avg, float* exp_avg_sq,
+                          float* ema, int64_t flat_floats, const double* sumsq, const ld_dn_scaler_state* state, double max_norm,
+                          double beta1, double beta2, double eps, int ema_mode, float ema_w, void* stream);
+
 /* ---- training the denoiser, the convolutions in bf16 (conv_precision = "bf16"): csrc/conv16.hip ---------------------------------
  * ld_pc_conv and ld_seg_wgrad with both operands of every product rounded to bf16 (round-to-nearest-even, NaN kept) and
  * multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Memory keeps its formats: activations, gradients and the
@@ -1104,6 +1140,13 @@ int ld_dn_conv16_from16_to16(const ld_pc_conv_args* args, const void* weight_bf1
  * [cip][k * k, flipped][cop] (dgr[c][k * k - 1 - t][o] = w[o][c][t]), zero in the padded channels.  k 1 or 3; cop >= co and
  * cip >= ci, both even. */
 int ld_dn_pack_conv16(const float* w_oihw, void* fwd_bf16, void* dgr_bf16, int co, int cop, int ci, int cip, int k, void* stream);
+/* The fp16 forms (amp = "fp16"): ld_dn_conv16, ld_dn_wgrad16 and ld_dn_pack_conv16 with both operands rounded to fp16
+ * (round-to-nearest-even; a value beyond 65504 becomes inf, it is not saturated: the loss scaler finds overflows by it), fp16
+ * packed weights and v_mfma_f32_32x32x16_f16; the same tiles, order of additions, shapes and refusals.  fp32 in, fp32 out. */
+int ld_dn_conv_f16(const ld_pc_conv_args* args, const void* weight_f16, void* stream);
+int ld_dn_wgrad_f16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout, int ksize,
+                    int splits, void* stream);
+int ld_dn_pack_conv_f16(const float* w_oihw, void* fwd_f16, void* dgr_f16, int co, int cop, int ci, int cip, int k, void* stream);
 
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH

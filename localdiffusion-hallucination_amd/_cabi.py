@@ -85,6 +85,12 @@ class DnOptTensor(C.Structure):
     _fields_ = [("param", vp), ("count", i64), ("offset", i64), ("first_wg", i32), ("flags", i32)]
 
 
+class DnScalerState(C.Structure):
+    """``ld_dn_scaler_state``: the loss scaler's state in device memory (amp = "fp16")."""
+    _fields_ = [("scale", f32), ("growth_tracker", i32), ("adam_steps", i32), ("skipped_steps", i32), ("found_inf", i32),
+                ("inv_scale", f32), ("step_size", f32), ("bc2_sqrt", f32)]
+
+
 DN_OPT_CHUNK, DN_OPT_ADAM, DN_OPT_MAX_WORLD = 4096, 1, 64     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM, LD_DN_OPT_MAX_WORLD
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
@@ -216,6 +222,7 @@ _SIGS = {
     "ld_mc_conv1_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ld_mc_adam": (C.c_int, [C.POINTER(McAdamTensor), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ld_p_losses_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, vp, C.c_int, i64, C.c_int, vp]),
+    "ld_p_losses_grad_scaled": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, C.c_int, i64, C.c_int, vp]),
     "ld_dn_gn_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ld_dn_gn_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_gn_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -263,6 +270,10 @@ _SIGS = {
     "ld_dn_opt_reduce_tail": (C.c_int, [vp, C.c_int, i64, i64, vp, vp]),
     "ld_dn_opt_step": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_int, f32, vp]),
+    "ld_dn_scaler_init": (C.c_int, [vp, f32, C.c_int, C.c_int, vp]),
+    "ld_dn_opt_scaler_update": (C.c_int, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp]),
+    "ld_dn_opt_step_scaled": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, C.c_int, f32, vp]),
     "ld_dn_conv16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
     "ld_dn_wgrad16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_conv16_from16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
@@ -277,6 +288,9 @@ _SIGS = {
     "ld_dn_gn_backward_from16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, vp]),
     "ld_dn_pack_conv16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_conv_f16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
+    "ld_dn_wgrad_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_dn_pack_conv_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

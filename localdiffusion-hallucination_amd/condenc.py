@@ -169,12 +169,12 @@ class BasicBlock(TrainableModule):
         cb, idn = self.convblock, self.identity
         mid, co = self.mid_dim, self.dim_out
         if self.image:                                          # OIHW is [out][9 input_dim] in memory: a 1x1 over the columns
-            p.w1f, p.w1d = pack_conv(lib, st, cb[0].weight, mid, self.cmp, 9 * self.dim, self.cik, 1, self.conv_precision)
-            p.w3f, p.w3d = pack_conv(lib, st, idn[0].weight, co, self.cop, 9 * self.dim, self.cik, 1, self.conv_precision)
+            p.w1f, p.w1d = pack_conv(lib, st, cb[0].weight, mid, self.cmp, 9 * self.dim, self.cik, 1, self.operand_precision)
+            p.w3f, p.w3d = pack_conv(lib, st, idn[0].weight, co, self.cop, 9 * self.dim, self.cik, 1, self.operand_precision)
         else:
-            p.w1f, p.w1d = pack_conv(lib, st, cb[0].weight, mid, self.cmp, self.dim, self.cik, 3, self.conv_precision)
-            p.w3f, p.w3d = pack_conv(lib, st, idn[0].weight, co, self.cop, self.dim, self.cik, 3, self.conv_precision)
-        p.w2f, p.w2d = pack_conv(lib, st, cb[3].weight, co, self.cop, mid, self.cmp, 3, self.conv_precision)
+            p.w1f, p.w1d = pack_conv(lib, st, cb[0].weight, mid, self.cmp, self.dim, self.cik, 3, self.operand_precision)
+            p.w3f, p.w3d = pack_conv(lib, st, idn[0].weight, co, self.cop, self.dim, self.cik, 3, self.operand_precision)
+        p.w2f, p.w2d = pack_conv(lib, st, cb[3].weight, co, self.cop, mid, self.cmp, 3, self.operand_precision)
         p.b1, p.b2, p.b3 = pack_vec(cb[0].bias, self.cmp), pack_vec(cb[3].bias, self.cop), pack_vec(idn[0].bias, self.cop)
         p.g1, p.be1 = pack_vec(cb[1].weight, mid), pack_vec(cb[1].bias, mid)
         p.g2, p.be2 = pack_vec(cb[4].weight, co), pack_vec(cb[4].bias, co)

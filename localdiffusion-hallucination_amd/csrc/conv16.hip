@@ -32,6 +32,12 @@
 // eight values (one DPP quad_perm move each), so that the even lane holds both channels of its even rows and the odd lane
 // both channels of its odd rows, and each stores eight dwords: half the store instructions of sixteen 2-byte stores, 64
 // contiguous bytes per pixel row and half-wave parity either way.
+//
+// The _f16 entry points (amp = "fp16" of trainable.py) are the same three kernels with the operand format as a template
+// parameter: the loader rounds to fp16 (pack_f16x2: v_cvt_pk_f16_f32, round-to-nearest-even; a value beyond 65504 becomes
+// inf, it is NOT saturated -- the loss scaler of denoiser_opt.hip finds its overflows that way), the packed weights are fp16
+// and the product is v_mfma_f32_32x32x16_f16.  Tiles, LDS image, chunk pipeline, epilogue and slab order are the code above;
+// only the fp32-in / fp32-out forms exist.
 #include <type_traits>
 
 #include "common.hip.h"
@@ -41,7 +47,19 @@ constexpr int CV_T = 64;        // tile: 64 rows x 64 columns per workgroup (4 w
 constexpr int CV_KC = 32;       // K per chunk
 constexpr int CV_LD = CV_KC + 8;   // bf16 per LDS row (80 bytes)
 typedef __attribute__((ext_vector_type(16))) float cv_f32x16;
-typedef unsigned short cv_bf16;    // bf16 bits
+typedef unsigned short cv_bf16;    // the bits of a 16-bit operand (bf16, or fp16 in the F = f16 kernels)
+
+// the operand format F of a kernel: how two fp32 values are rounded to a packed pair, and the MFMA that multiplies them
+template <typename F> __device__ __forceinline__ unsigned cv_pack(float lo, float hi);
+template <> __device__ __forceinline__ unsigned cv_pack<bf16>(float lo, float hi) { return pack_bf16x2(lo, hi); }
+template <> __device__ __forceinline__ unsigned cv_pack<f16>(float lo, float hi) { return pack_f16x2(lo, hi); }
+template <typename F> __device__ __forceinline__ cv_f32x16 cv_mfma(bf16x8 a, bf16x8 b, cv_f32x16 acc);
+template <> __device__ __forceinline__ cv_f32x16 cv_mfma<bf16>(bf16x8 a, bf16x8 b, cv_f32x16 acc) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+}
+template <> __device__ __forceinline__ cv_f32x16 cv_mfma<f16>(bf16x8 a, bf16x8 b, cv_f32x16 acc) {   // (the same 16 bytes, read as fp16)
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+}
 
 // the lane's fragment of K-step s (16 k) of a [row][CV_LD] image: 8 consecutive k of row `row`
 __device__ __forceinline__ bf16x8 cv_frag(const cv_bf16 (*img)[CV_LD], int row, int s, int kh) {
@@ -51,8 +69,10 @@ __device__ __forceinline__ bf16x8 cv_frag(const cv_bf16 (*img)[CV_LD], int row, 
 // ------------------------------------------------------------------------------------------------ convolution
 // A16: a.src points at bf16 (8 per thread and chunk, one row) instead of fp32 (4 per thread and chunk, two rows)
 // O16: a.out points at bf16; the epilogue's fp32 value is rounded to nearest even
-template <bool A16, bool O16>
+// F: the operand format (bf16 or f16); A16 and O16 are bf16 storage and exist for F = bf16 only
+template <typename F, bool A16, bool O16>
 __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const cv_bf16* __restrict__ w) {
+  static_assert(std::is_same_v<F, bf16> || (!A16 && !O16), "16-bit storage is bf16");
   __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [pixel][k]
   __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [output channel][k]
   constexpr int UA = A16 ? 1 : CV_T / 32;
@@ -110,7 +130,7 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
 #pragma unroll
     for (int u = 0; u < UA; ++u) {
       if constexpr (A16) *reinterpret_cast<uint4*>(&sa[lr][lk]) = ra[u];
-      else *reinterpret_cast<uint2*>(&sa[lr + 32 * u][lk]) = make_uint2(pack_bf16x2(ra[u].x, ra[u].y), pack_bf16x2(ra[u].z, ra[u].w));
+      else *reinterpret_cast<uint2*>(&sa[lr + 32 * u][lk]) = make_uint2(cv_pack<F>(ra[u].x, ra[u].y), cv_pack<F>(ra[u].z, ra[u].w));
     }
     *reinterpret_cast<uint4*>(&sb[wr][wk]) = rb;
     __syncthreads();
@@ -121,7 +141,7 @@ __global__ __launch_bounds__(256) void dn_conv16_kernel(ld_pc_conv_args a, const
     }
 #pragma unroll
     for (int s = 0; s < CV_KC / 16; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc, 0, 0, 0);
+      acc = cv_mfma<F>(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc);
   }
   // C/D layout of 32x32x16: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int co = n0 + wn * 32 + c;
@@ -164,9 +184,10 @@ struct CvWgradDev {
   int H, W, Cin, Cout, ks, chunks_per_split;
 };
 
-// A16: d.a points at bf16; rb then holds the four channels of a pixel as two dwords of bf16 pairs
-template <bool A16>
+// A16: d.a points at bf16; rb then holds the four channels of a pixel as two dwords of bf16 pairs (F = bf16 only)
+template <typename F, bool A16>
 __global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
+  static_assert(std::is_same_v<F, bf16> || !A16, "16-bit storage is bf16");
   __shared__ __attribute__((aligned(16))) cv_bf16 sa[CV_T][CV_LD];   // [output channel][pixel of the chunk]
   __shared__ __attribute__((aligned(16))) cv_bf16 sb[CV_T][CV_LD];   // [input channel][pixel of the chunk]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -205,26 +226,26 @@ __global__ __launch_bounds__(256) void dn_wgrad16_kernel(CvWgradDev d) {
   const int kh = lane >> 5, c = lane & 31;
   for (long q = c0; q < c1; ++q) {
     __syncthreads();                                          // the previous chunk's reads of the tiles are done
-    *reinterpret_cast<unsigned*>(&sa[lc][lp]) = pack_bf16x2(ra[0].x, ra[1].x);
-    *reinterpret_cast<unsigned*>(&sa[lc + 1][lp]) = pack_bf16x2(ra[0].y, ra[1].y);
-    *reinterpret_cast<unsigned*>(&sa[lc + 2][lp]) = pack_bf16x2(ra[0].z, ra[1].z);
-    *reinterpret_cast<unsigned*>(&sa[lc + 3][lp]) = pack_bf16x2(ra[0].w, ra[1].w);
+    *reinterpret_cast<unsigned*>(&sa[lc][lp]) = cv_pack<F>(ra[0].x, ra[1].x);
+    *reinterpret_cast<unsigned*>(&sa[lc + 1][lp]) = cv_pack<F>(ra[0].y, ra[1].y);
+    *reinterpret_cast<unsigned*>(&sa[lc + 2][lp]) = cv_pack<F>(ra[0].z, ra[1].z);
+    *reinterpret_cast<unsigned*>(&sa[lc + 3][lp]) = cv_pack<F>(ra[0].w, ra[1].w);
     if constexpr (A16) {                                      // (low half: the even channel, and the first pixel of a pair)
       *reinterpret_cast<unsigned*>(&sb[lc][lp]) = (rb[0].x & 0xffffu) | (rb[1].x << 16);
       *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = (rb[0].x >> 16) | (rb[1].x & 0xffff0000u);
       *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = (rb[0].y & 0xffffu) | (rb[1].y << 16);
       *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = (rb[0].y >> 16) | (rb[1].y & 0xffff0000u);
     } else {
-      *reinterpret_cast<unsigned*>(&sb[lc][lp]) = pack_bf16x2(rb[0].x, rb[1].x);
-      *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = pack_bf16x2(rb[0].y, rb[1].y);
-      *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = pack_bf16x2(rb[0].z, rb[1].z);
-      *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = pack_bf16x2(rb[0].w, rb[1].w);
+      *reinterpret_cast<unsigned*>(&sb[lc][lp]) = cv_pack<F>(rb[0].x, rb[1].x);
+      *reinterpret_cast<unsigned*>(&sb[lc + 1][lp]) = cv_pack<F>(rb[0].y, rb[1].y);
+      *reinterpret_cast<unsigned*>(&sb[lc + 2][lp]) = cv_pack<F>(rb[0].z, rb[1].z);
+      *reinterpret_cast<unsigned*>(&sb[lc + 3][lp]) = cv_pack<F>(rb[0].w, rb[1].w);
     }
     __syncthreads();
     if (q + 1 < c1) fetch(q + 1);
 #pragma unroll
     for (int s = 0; s < CV_KC / 16; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc, 0, 0, 0);
+      acc = cv_mfma<F>(cv_frag(sa, wm * 32 + c, s, kh), cv_frag(sb, wn * 32 + c, s, kh), acc);
   }
   // C/D layout of 32x32x16: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   float* slab = d.work + (long)blockIdx.z * d.Cout * taps * d.Cin;
@@ -247,6 +268,7 @@ __global__ void dn_wgrad16_reduce_kernel(const float* __restrict__ work, float* 
 // ------------------------------------------------------------------------------------------------ weight packing
 // One thread per pair of neighbouring elements of fwd [cop][kk][cip] (the first `half` threads) or of dgr [cip][kk][cop]
 // with the taps flipped; w is OIHW [co][ci][kk].
+template <typename F>
 __global__ void dn_pack_conv16_kernel(const float* __restrict__ w, unsigned* fwd, unsigned* dgr, long half, int co, int cop, int ci,
                                       int cip, int kk) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -257,21 +279,21 @@ __global__ void dn_pack_conv16_kernel(const float* __restrict__ w, unsigned* fwd
     const int c = (int)(e % cip), t = (int)((e / cip) % kk), o = (int)(e / ((long)cip * kk));
 #pragma unroll
     for (int j = 0; j < 2; ++j) v[j] = (o < co && c + j < ci) ? w[((long)o * ci + c + j) * kk + t] : 0.0f;
-    fwd[i] = pack_bf16x2(v[0], v[1]);
+    fwd[i] = cv_pack<F>(v[0], v[1]);
   } else {
     const long e = 2 * (i - half);
     const int o = (int)(e % cop), t = kk - 1 - (int)((e / cop) % kk), c = (int)(e / ((long)cop * kk));
 #pragma unroll
     for (int j = 0; j < 2; ++j) v[j] = (o + j < co && c < ci) ? w[((long)(o + j) * ci + c) * kk + t] : 0.0f;
-    dgr[i - half] = pack_bf16x2(v[0], v[1]);
+    dgr[i - half] = cv_pack<F>(v[0], v[1]);
   }
 }
 }  // namespace
 
 namespace {
 // ld_dn_conv16 and its _from16 / _to16 forms: `name` is the entry point's, `a16` says what args->src points at, `o16` what
-// args->out does
-int cv_conv(const char* name, bool a16, bool o16, const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
+// args->out does, `fp16` the operand format (ld_dn_conv_f16: fp32 in, fp32 out only)
+int cv_conv(const char* name, bool fp16, bool a16, bool o16, const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
   LD_REQUIRE(a, "%s: null args", name);
   LD_REQUIRE(a->ksize == 1 || a->ksize == 3, "%s: ksize %d (1 or 3)", name, a->ksize);
   LD_REQUIRE(a->stride == 1, "%s: stride %d (1 only)", name, a->stride);
@@ -294,20 +316,22 @@ int cv_conv(const char* name, bool a16, bool o16, const ld_pc_conv_args* a, cons
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((M + CV_T - 1) / CV_T), (unsigned)(a->Cout / CV_T));
   const cv_bf16* w = reinterpret_cast<const cv_bf16*>(weight_bf16);
-  if (a16 && o16) {
-    LD_LAUNCH((dn_conv16_kernel<true, true>), grid, dim3(256), 0, st, *a, w);
+  if (fp16) {
+    LD_LAUNCH((dn_conv16_kernel<f16, false, false>), grid, dim3(256), 0, st, *a, w);
+  } else if (a16 && o16) {
+    LD_LAUNCH((dn_conv16_kernel<bf16, true, true>), grid, dim3(256), 0, st, *a, w);
   } else if (a16) {
-    LD_LAUNCH((dn_conv16_kernel<true, false>), grid, dim3(256), 0, st, *a, w);
+    LD_LAUNCH((dn_conv16_kernel<bf16, true, false>), grid, dim3(256), 0, st, *a, w);
   } else if (o16) {
-    LD_LAUNCH((dn_conv16_kernel<false, true>), grid, dim3(256), 0, st, *a, w);
+    LD_LAUNCH((dn_conv16_kernel<bf16, false, true>), grid, dim3(256), 0, st, *a, w);
   } else {
-    LD_LAUNCH((dn_conv16_kernel<false, false>), grid, dim3(256), 0, st, *a, w);
+    LD_LAUNCH((dn_conv16_kernel<bf16, false, false>), grid, dim3(256), 0, st, *a, w);
   }
   LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
 }
 
-int cv_wgrad(const char* name, bool a16, const float* dy, const void* a, float* work, float* dw, int B, int H, int W, int Cin,
+int cv_wgrad(const char* name, bool fp16, bool a16, const float* dy, const void* a, float* work, float* dw, int B, int H, int W, int Cin,
              int Cout, int ksize, int splits, void* stream) {
   LD_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize %d (1 or 3)", name, ksize);
   LD_REQUIRE(B > 0 && H > 0 && W > 0, "%s: empty shape B=%d H=%d W=%d", name, B, H, W);
@@ -323,56 +347,86 @@ int cv_wgrad(const char* name, bool a16, const float* dy, const void* a, float* 
   CvWgradDev d{dy, a, work, M, nchunks, H, W, Cin, Cout, ksize, (int)per};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)tiles, (unsigned)(ksize * ksize), (unsigned)splits);
-  if (a16) {
-    LD_LAUNCH(dn_wgrad16_kernel<true>, grid, dim3(256), 0, st, d);
+  if (fp16) {
+    LD_LAUNCH((dn_wgrad16_kernel<f16, false>), grid, dim3(256), 0, st, d);
+  } else if (a16) {
+    LD_LAUNCH((dn_wgrad16_kernel<bf16, true>), grid, dim3(256), 0, st, d);
   } else {
-    LD_LAUNCH(dn_wgrad16_kernel<false>, grid, dim3(256), 0, st, d);
+    LD_LAUNCH((dn_wgrad16_kernel<bf16, false>), grid, dim3(256), 0, st, d);
   }
   const long n = (long)Cout * ksize * ksize * Cin;
   LD_LAUNCH(dn_wgrad16_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, dw, n, splits);
-  LD_LAUNCH_CHECK(a16 ? "dn_wgrad16_from16" : "dn_wgrad16");
+  LD_LAUNCH_CHECK(name + 3);
   return LD_OK;
 }
 }  // namespace
 
 extern "C" int ld_dn_conv16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16", false, false, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16", false, false, false, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_conv16_from16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16_from16", true, false, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16_from16", false, true, false, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_conv16_to16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16_to16", false, true, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16_to16", false, false, true, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_conv16_from16_to16(const ld_pc_conv_args* a, const void* weight_bf16, void* stream) {
-  return cv_conv("ld_dn_conv16_from16_to16", true, true, a, weight_bf16, stream);
+  return cv_conv("ld_dn_conv16_from16_to16", false, true, true, a, weight_bf16, stream);
 }
 
 extern "C" int ld_dn_wgrad16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
                              int ksize, int splits, void* stream) {
-  return cv_wgrad("ld_dn_wgrad16", false, dy, a, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
+  return cv_wgrad("ld_dn_wgrad16", false, false, dy, a, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
 }
 
 extern "C" int ld_dn_wgrad16_from16(const float* dy, const void* a_bf16, float* work, float* dw, int B, int H, int W, int Cin,
                                     int Cout, int ksize, int splits, void* stream) {
-  return cv_wgrad("ld_dn_wgrad16_from16", true, dy, a_bf16, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
+  return cv_wgrad("ld_dn_wgrad16_from16", false, true, dy, a_bf16, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
 }
+
+namespace {
+int cv_pack_conv(const char* name, bool fp16, const float* w_oihw, void* fwd16, void* dgr16, int co, int cop, int ci, int cip, int k,
+                 void* stream) {
+  LD_REQUIRE(k == 1 || k == 3, "%s: ksize %d (1 or 3)", name, k);
+  LD_REQUIRE(co > 0 && ci > 0 && cop >= co && cip >= ci, "%s: co %d of %d, ci %d of %d", name, co, cop, ci, cip);
+  LD_REQUIRE(cop % 2 == 0 && cip % 2 == 0, "%s: padded channels %d, %d (even)", name, cop, cip);
+  LD_REQUIRE(w_oihw && fwd16 && dgr16, "%s: null pointer", name);
+  LD_REQUIRE(((uintptr_t)fwd16 | (uintptr_t)dgr16) % 4 == 0, "%s: outputs must be 4-byte aligned", name);
+  const long half = (long)cop * k * k * cip / 2;
+  LD_REQUIRE((2 * half + 255) / 256 < (1L << 31), "%s: %ld elements", name, 2 * half);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((2 * half + 255) / 256));
+  unsigned* fwd = reinterpret_cast<unsigned*>(fwd16);
+  unsigned* dgr = reinterpret_cast<unsigned*>(dgr16);
+  if (fp16) {
+    LD_LAUNCH(dn_pack_conv16_kernel<f16>, grid, dim3(256), 0, st, w_oihw, fwd, dgr, half, co, cop, ci, cip, k * k);
+  } else {
+    LD_LAUNCH(dn_pack_conv16_kernel<bf16>, grid, dim3(256), 0, st, w_oihw, fwd, dgr, half, co, cop, ci, cip, k * k);
+  }
+  LD_LAUNCH_CHECK(name + 3);
+  return LD_OK;
+}
+}  // namespace
 
 extern "C" int ld_dn_pack_conv16(const float* w_oihw, void* fwd_bf16, void* dgr_bf16, int co, int cop, int ci, int cip, int k,
                                  void* stream) {
-  LD_REQUIRE(k == 1 || k == 3, "ld_dn_pack_conv16: ksize %d (1 or 3)", k);
-  LD_REQUIRE(co > 0 && ci > 0 && cop >= co && cip >= ci, "ld_dn_pack_conv16: co %d of %d, ci %d of %d", co, cop, ci, cip);
-  LD_REQUIRE(cop % 2 == 0 && cip % 2 == 0, "ld_dn_pack_conv16: padded channels %d, %d (even)", cop, cip);
-  LD_REQUIRE(w_oihw && fwd_bf16 && dgr_bf16, "ld_dn_pack_conv16: null pointer");
-  LD_REQUIRE(((uintptr_t)fwd_bf16 | (uintptr_t)dgr_bf16) % 4 == 0, "ld_dn_pack_conv16: outputs must be 4-byte aligned");
-  const long half = (long)cop * k * k * cip / 2;
-  LD_REQUIRE((2 * half + 255) / 256 < (1L << 31), "ld_dn_pack_conv16: %ld elements", 2 * half);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LD_LAUNCH(dn_pack_conv16_kernel, dim3((unsigned)((2 * half + 255) / 256)), dim3(256), 0, st, w_oihw, reinterpret_cast<unsigned*>(fwd_bf16),
-            reinterpret_cast<unsigned*>(dgr_bf16), half, co, cop, ci, cip, k * k);
-  LD_LAUNCH_CHECK("dn_pack_conv16");
-  return LD_OK;
+  return cv_pack_conv("ld_dn_pack_conv16", false, w_oihw, fwd_bf16, dgr_bf16, co, cop, ci, cip, k, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ fp16 operands (amp = "fp16")
+extern "C" int ld_dn_conv_f16(const ld_pc_conv_args* a, const void* weight_f16, void* stream) {
+  return cv_conv("ld_dn_conv_f16", true, false, false, a, weight_f16, stream);
+}
+
+extern "C" int ld_dn_wgrad_f16(const float* dy, const float* a, float* work, float* dw, int B, int H, int W, int Cin, int Cout,
+                               int ksize, int splits, void* stream) {
+  return cv_wgrad("ld_dn_wgrad_f16", true, false, dy, a, work, dw, B, H, W, Cin, Cout, ksize, splits, stream);
+}
+
+extern "C" int ld_dn_pack_conv_f16(const float* w_oihw, void* fwd_f16, void* dgr_f16, int co, int cop, int ci, int cip, int k,
+                                   void* stream) {
+  return cv_pack_conv("ld_dn_pack_conv_f16", true, w_oihw, fwd_f16, dgr_f16, co, cop, ci, cip, k, stream);
 }

@@ -419,11 +419,15 @@ __global__ __launch_bounds__(256) void dn_gather3_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------- the loss gradient
+// With a trailing `const float* dev_scale` (ld_p_losses_grad_scaled) the upstream scalar is g * *dev_scale, the loss scale
+// read on the device (a power of two by default, so the product is exact); without, the kernel is what it always was
+template <typename... Scale>
 __global__ __launch_bounds__(256) void dn_p_losses_grad_kernel(const float* __restrict__ mo, const float* __restrict__ x0,
                                                                const float* __restrict__ z, const int* __restrict__ t,
                                                                const float* __restrict__ sab, const float* __restrict__ s1mab,
                                                                const float* __restrict__ lw, float g, float* __restrict__ out,
-                                                               long per, int B, int objective) {
+                                                               long per, int B, int objective, Scale... dev_scale) {
+  if constexpr (sizeof...(Scale) != 0) g = g * *(dev_scale, ...);
   const int b = blockIdx.y;
   const int tb = t[b];
   const float a = sab[tb], c = s1mab[tb];
@@ -442,21 +446,43 @@ inline bool dn_gn_shape_ok(int B, int H, int W, int C, int ldc, int G) {
 }
 }  // namespace
 
+namespace {
+int dn_p_losses_grad(const char* name, bool scaled, const float* model_out, const float* x_start, const float* noise, const int* t,
+                     const float* sqrt_ab, const float* sqrt_1mab, const float* loss_weight, float g, const float* dev_scale,
+                     float* d_model_out, int B, int64_t elems_per_sample, int objective, void* stream) {
+  LD_REQUIRE(model_out && x_start && noise && t && sqrt_ab && sqrt_1mab && loss_weight && d_model_out && (dev_scale || !scaled),
+             "%s: null pointer", name);
+  LD_REQUIRE(B > 0 && B <= 65535 && elems_per_sample > 0, "%s: batch %d (1..65535) of %ld elements", name, B,
+             (long)elems_per_sample);
+  LD_REQUIRE(objective == LD_OBJ_X0 || objective == LD_OBJ_NOISE || objective == LD_OBJ_V, "%s: objective %d", name, objective);
+  long wgs = ((long)elems_per_sample + 255) / 256;
+  if (wgs > 1024) wgs = 1024;
+  const dim3 grid((unsigned)wgs, (unsigned)B);
+  if (scaled) {
+    LD_LAUNCH(dn_p_losses_grad_kernel<const float*>, grid, dim3(256), 0, dn_st(stream), model_out, x_start, noise, t, sqrt_ab, sqrt_1mab,
+              loss_weight, g, d_model_out, (long)elems_per_sample, B, objective, dev_scale);
+  } else {
+    LD_LAUNCH(dn_p_losses_grad_kernel<>, grid, dim3(256), 0, dn_st(stream), model_out, x_start, noise, t, sqrt_ab, sqrt_1mab,
+              loss_weight, g, d_model_out, (long)elems_per_sample, B, objective);
+  }
+  LD_LAUNCH_CHECK(name + 3);
+  return LD_OK;
+}
+}  // namespace
+
 extern "C" int ld_p_losses_grad(const float* model_out, const float* x_start, const float* noise, const int* t,
                                 const float* sqrt_ab, const float* sqrt_1mab, const float* loss_weight, float g,
                                 float* d_model_out, int B, int64_t elems_per_sample, int objective, void* stream) {
-  LD_REQUIRE(model_out && x_start && noise && t && sqrt_ab && sqrt_1mab && loss_weight && d_model_out,
-             "ld_p_losses_grad: null pointer");
-  LD_REQUIRE(B > 0 && B <= 65535 && elems_per_sample > 0, "ld_p_losses_grad: batch %d (1..65535) of %ld elements", B,
-             (long)elems_per_sample);
-  LD_REQUIRE(objective == LD_OBJ_X0 || objective == LD_OBJ_NOISE || objective == LD_OBJ_V, "ld_p_losses_grad: objective %d",
-             objective);
-  long wgs = ((long)elems_per_sample + 255) / 256;
-  if (wgs > 1024) wgs = 1024;
-  LD_LAUNCH(dn_p_losses_grad_kernel, dim3((unsigned)wgs, (unsigned)B), dim3(256), 0, dn_st(stream), model_out, x_start, noise, t,
-            sqrt_ab, sqrt_1mab, loss_weight, g, d_model_out, (long)elems_per_sample, B, objective);
-  LD_LAUNCH_CHECK("p_losses_grad");
-  return LD_OK;
+  return dn_p_losses_grad("ld_p_losses_grad", false, model_out, x_start, noise, t, sqrt_ab, sqrt_1mab, loss_weight, g, nullptr,
+                          d_model_out, B, elems_per_sample, objective, stream);
+}
+
+extern "C" int ld_p_losses_grad_scaled(const float* model_out, const float* x_start, const float* noise, const int* t,
+                                       const float* sqrt_ab, const float* sqrt_1mab, const float* loss_weight, float g,
+                                       const float* dev_scale, float* d_model_out, int B, int64_t elems_per_sample, int objective,
+                                       void* stream) {
+  return dn_p_losses_grad("ld_p_losses_grad_scaled", true, model_out, x_start, noise, t, sqrt_ab, sqrt_1mab, loss_weight, g,
+                          dev_scale, d_model_out, B, elems_per_sample, objective, stream);
 }
 
 extern "C" int64_t ld_dn_gn_work_bytes(int B, int H, int W, int C) {

@@ -17,6 +17,13 @@
 // Data-parallel training puts ld_dn_opt_reduce in the place of ld_dn_opt_sqnorm: the ranks all-gather their flat gradients,
 // and one launch adds the copies in rank order (plain fp32, left to right) while it gathers the norm's partials, so every
 // rank steps on the same bits and a W-rank step equals a one-rank step that accumulated the W shards in order.
+//
+// Loss scaling (amp = "fp16"): the gradients arrive multiplied by a scale that lives in device memory (ld_dn_scaler_state).
+// Between the norm and the step a one-thread kernel, ld_dn_opt_scaler_update, takes torch.amp.GradScaler's decisions from
+// the squared norm alone -- a non-finite norm skips the step and backs the scale off, growth_interval finite ones in a row
+// grow it -- and leaves what the step needs (found_inf, 1 / scale, Adam's two bias corrections for its OWN step count,
+// which does not advance on a skip) in the state; ld_dn_opt_step_scaled is the step above reading them there.  The host
+// never sees any of it, so a step still does not wait for the GPU.
 #include "common.hip.h"
 #include "dn_common.hip.h"
 
@@ -117,16 +124,39 @@ __device__ __forceinline__ float opt_lerp(float e, float p, float w) {
 
 __device__ __forceinline__ void opt_store4(float* p, const float4& q) { *reinterpret_cast<float4*>(p) = q; }
 
+// The step of one workgroup.  SCALED (ld_dn_opt_step_scaled): the gradients carry the loss scale -- the norm and every
+// gradient are multiplied by inv_scale first (torch unscales in place, then clips: (g * inv_scale) * coef, two multiplies in
+// this order; with a power-of-two scale both are exact and the order could not matter) -- and on `skip` (the scaler found a
+// non-finite gradient) parameters and moments keep their bits while the gradient is still zeroed and the EMA still acts.
+// One body, two kernels: opt_step_kernel<> is the fp32 step with the argument list it always had; opt_step_kernel<const
+// ld_dn_scaler_state*> takes the state behind it and reads found_inf, inv_scale and Adam's two bias corrections there.
+template <typename... State>
 __global__ __launch_bounds__(OPT_BS) void opt_step_kernel(const ld_dn_opt_tensor* __restrict__ tab, int n, float* grad, float* m,
                                                           float* v, float* ema, long flat, const double* __restrict__ sumsq,
-                                                          double max_norm, OptScalars s) {
+                                                          double max_norm, OptScalars s, State... state) {
+  constexpr bool SCALED = sizeof...(State) != 0;
+  float inv_scale = 1.0f;
+  bool skip = false;
+  if constexpr (SCALED) {
+    const ld_dn_scaler_state* st = (state, ...);
+    s.step_size = st->step_size;
+    s.bc2_sqrt = st->bc2_sqrt;
+    inv_scale = st->inv_scale;
+    skip = st->found_inf != 0;
+  }
   OptChunk c;
   if (!opt_chunk(tab, n, flat, c)) return;
   const bool adam = (c.e.flags & LD_DN_OPT_ADAM) != 0;
   if (!adam && s.ema_mode == 0) return;
   // clip_grad_norm_'s coefficient; a NaN norm stays NaN (c > 1 is false for it), an infinite one gives 0
-  const double cd = max_norm / (sqrt(*sumsq) + 1e-6);
+  double norm = sqrt(*sumsq);
+  if constexpr (SCALED) norm *= (double)inv_scale;
+  const double cd = max_norm / (norm + 1e-6);
   const float coef = (float)(cd > 1.0 ? 1.0 : cd);
+  auto unscaled = [&](float g) {                                    // grad.mul_(inv_scale): GradScaler.unscale_
+    if constexpr (SCALED) return g * inv_scale;
+    else return g;
+  };
   float* P = c.e.param;
   float* G = grad + c.e.offset;
   float* M = m + c.e.offset;
@@ -140,15 +170,17 @@ __global__ __launch_bounds__(OPT_BS) void opt_step_kernel(const ld_dn_opt_tensor
     if (vec && i + 4 <= c.hi) {
       float4 p = ld4(P + i);
       if (adam) {
-        const float4 g = ld4(G + i);
-        float4 mm = ld4(M + i), vv = ld4(V + i);
-        opt_adam(p.x, g.x, mm.x, vv.x, coef, s);
-        opt_adam(p.y, g.y, mm.y, vv.y, coef, s);
-        opt_adam(p.z, g.z, mm.z, vv.z, coef, s);
-        opt_adam(p.w, g.w, mm.w, vv.w, coef, s);
-        opt_store4(P + i, p);
-        opt_store4(M + i, mm);
-        opt_store4(V + i, vv);
+        if (!SCALED || !skip) {
+          const float4 g = ld4(G + i);
+          float4 mm = ld4(M + i), vv = ld4(V + i);
+          opt_adam(p.x, unscaled(g.x), mm.x, vv.x, coef, s);
+          opt_adam(p.y, unscaled(g.y), mm.y, vv.y, coef, s);
+          opt_adam(p.z, unscaled(g.z), mm.z, vv.z, coef, s);
+          opt_adam(p.w, unscaled(g.w), mm.w, vv.w, coef, s);
+          opt_store4(P + i, p);
+          opt_store4(M + i, mm);
+          opt_store4(V + i, vv);
+        }
         opt_store4(G + i, make_float4(0.f, 0.f, 0.f, 0.f));
       }
       if (s.ema_mode == 1) {
@@ -163,11 +195,13 @@ __global__ __launch_bounds__(OPT_BS) void opt_step_kernel(const ld_dn_opt_tensor
       for (long q = i; q < end; ++q) {
         float p = P[q];
         if (adam) {
-          float mm = M[q], vv = V[q];
-          opt_adam(p, G[q], mm, vv, coef, s);
-          P[q] = p;
-          M[q] = mm;
-          V[q] = vv;
+          if (!SCALED || !skip) {
+            float mm = M[q], vv = V[q];
+            opt_adam(p, unscaled(G[q]), mm, vv, coef, s);
+            P[q] = p;
+            M[q] = mm;
+            V[q] = vv;
+          }
           G[q] = 0.f;
         }
         if (s.ema_mode == 1) E[q] = p;
@@ -175,6 +209,47 @@ __global__ __launch_bounds__(OPT_BS) void opt_step_kernel(const ld_dn_opt_tensor
       }
     }
   }
+}
+
+// ---------------------------------------------------------------- the loss scaler: one thread
+__global__ void opt_scaler_init_kernel(ld_dn_scaler_state* st, float scale, int adam_steps, int growth_tracker) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  st->scale = scale;
+  st->growth_tracker = growth_tracker;
+  st->adam_steps = adam_steps;
+  st->skipped_steps = 0;
+  st->found_inf = 0;
+  st->inv_scale = (float)(1.0 / (double)scale);
+  st->step_size = 0.0f;
+  st->bc2_sqrt = 1.0f;
+}
+
+// GradScaler.step's decision and GradScaler.update (_amp_update_scale_) from the squared norm of the SCALED gradients: it is
+// non-finite exactly when a gradient element is (fp64 does not overflow on squares of finite fp32 values)
+__global__ void opt_scaler_update_kernel(ld_dn_scaler_state* st, const double* __restrict__ sumsq, double lr, double beta1,
+                                         double beta2, double growth, double backoff, int growth_interval) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  ld_dn_scaler_state s = *st;
+  const bool found_inf = !isfinite(*sumsq);
+  s.found_inf = found_inf ? 1 : 0;
+  s.inv_scale = (float)(1.0 / (double)s.scale);                     // of the scale these gradients were produced with
+  if (!found_inf) {
+    s.adam_steps += 1;
+    const double t = (double)s.adam_steps;
+    s.step_size = (float)(lr / (1.0 - pow(beta1, t)));              // what ld_dn_opt_step is handed in double and rounds
+    s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+    s.growth_tracker += 1;
+    if (s.growth_tracker == growth_interval) {
+      const float grown = (float)((double)s.scale * growth);
+      if (isfinite(grown)) s.scale = grown;
+      s.growth_tracker = 0;
+    }
+  } else {
+    s.skipped_steps += 1;
+    s.scale = (float)((double)s.scale * backoff);
+    s.growth_tracker = 0;
+  }
+  *st = s;
 }
 
 // ---------------------------------------------------------------- data-parallel: the rank-ordered sum of the gathered gradients
@@ -383,8 +458,65 @@ extern "C" int ld_dn_opt_step(const ld_dn_opt_tensor* table, int n_tensors, int 
   s.bc2_sqrt = (float)bc2_sqrt;
   s.ema_w = ema_w;
   s.ema_mode = ema_mode;
-  LD_LAUNCH(opt_step_kernel, dim3((unsigned)n_wg), dim3(OPT_BS), 0, dn_st(stream), table, n_tensors, grad, exp_avg, exp_avg_sq, ema,
+  LD_LAUNCH(opt_step_kernel<>, dim3((unsigned)n_wg), dim3(OPT_BS), 0, dn_st(stream), table, n_tensors, grad, exp_avg, exp_avg_sq, ema,
             (long)flat_floats, sumsq, max_norm, s);
   LD_LAUNCH_CHECK("dn_opt_step");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_scaler_init(ld_dn_scaler_state* state, float init_scale, int adam_steps, int growth_tracker, void* stream) {
+  LD_REQUIRE(state && (uintptr_t)state % 4 == 0, "ld_dn_scaler_init: null or misaligned state");
+  LD_REQUIRE(init_scale > 0.0f && init_scale <= 3.4028234663852886e38f, "ld_dn_scaler_init: init_scale %g (positive and finite)",
+             (double)init_scale);
+  LD_REQUIRE(adam_steps >= 0 && growth_tracker >= 0, "ld_dn_scaler_init: adam_steps %d, growth_tracker %d (non-negative)",
+             adam_steps, growth_tracker);
+  LD_LAUNCH(opt_scaler_init_kernel, dim3(1), dim3(64), 0, dn_st(stream), state, init_scale, adam_steps, growth_tracker);
+  LD_LAUNCH_CHECK("dn_scaler_init");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_opt_scaler_update(ld_dn_scaler_state* state, const double* sumsq, double lr, double beta1, double beta2,
+                                       double growth_factor, double backoff_factor, int growth_interval, void* stream) {
+  LD_REQUIRE(state && sumsq, "ld_dn_opt_scaler_update: null pointer");
+  LD_REQUIRE((uintptr_t)state % 4 == 0 && (uintptr_t)sumsq % 8 == 0,
+             "ld_dn_opt_scaler_update: a pointer is not aligned (the state 4 bytes, sumsq 8)");
+  LD_REQUIRE(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "ld_dn_opt_scaler_update: lr %g beta1 %g beta2 %g",
+             lr, beta1, beta2);
+  LD_REQUIRE(growth_factor > 1.0 && backoff_factor > 0.0 && backoff_factor < 1.0 && growth_interval >= 1,
+             "ld_dn_opt_scaler_update: growth %g (> 1) backoff %g (0..1) growth_interval %d (>= 1)", growth_factor, backoff_factor,
+             growth_interval);
+  LD_LAUNCH(opt_scaler_update_kernel, dim3(1), dim3(64), 0, dn_st(stream), state, sumsq, lr, beta1, beta2, growth_factor,
+            backoff_factor, growth_interval);
+  LD_LAUNCH_CHECK("dn_opt_scaler_update");
+  return LD_OK;
+}
+
+extern "C" int ld_dn_opt_step_scaled(const ld_dn_opt_tensor* table, int n_tensors, int n_wg, float* grad, float* exp_avg,
+                                     float* exp_avg_sq, float* ema, int64_t flat_floats, const double* sumsq,
+                                     const ld_dn_scaler_state* state, double max_norm, double beta1, double beta2, double eps,
+                                     int ema_mode, float ema_w, void* stream) {
+  LD_REQUIRE(opt_sizes_ok(n_tensors, n_wg, flat_floats), "ld_dn_opt_step_scaled: %d tensors, %d workgroups, %lld floats (at least "
+             "one tensor, a workgroup per tensor, a multiple of 4 floats)", n_tensors, n_wg, (long long)flat_floats);
+  LD_REQUIRE(max_norm >= 0.0, "ld_dn_opt_step_scaled: max_norm %g is negative or NaN", max_norm);
+  LD_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+             "ld_dn_opt_step_scaled: beta1 %g beta2 %g eps %g", beta1, beta2, eps);
+  LD_REQUIRE(ema_mode >= 0 && ema_mode <= 2 && ema_w >= 0.f && ema_w <= 1.f, "ld_dn_opt_step_scaled: ema_mode %d (0 keep, 1 copy, "
+             "2 lerp) weight %g (0..1)", ema_mode, (double)ema_w);
+  LD_REQUIRE(table && grad && exp_avg && exp_avg_sq && ema && sumsq && state, "ld_dn_opt_step_scaled: null pointer");
+  LD_REQUIRE(dn_aligned16(grad) && dn_aligned16(exp_avg) && dn_aligned16(exp_avg_sq) && dn_aligned16(ema) &&
+                 ((uintptr_t)table | (uintptr_t)sumsq) % 8 == 0 && (uintptr_t)state % 4 == 0,
+             "ld_dn_opt_step_scaled: a pointer is not aligned (the flat buffers 16 bytes; the table and sumsq 8; the state 4)");
+  OptScalars s;
+  s.omb1 = (float)(1.0 - beta1);
+  s.beta2 = (float)beta2;
+  s.omb2 = (float)(1.0 - beta2);
+  s.eps = (float)eps;
+  s.step_size = 0.0f;                                               // (both from the state, on the device)
+  s.bc2_sqrt = 1.0f;
+  s.ema_w = ema_w;
+  s.ema_mode = ema_mode;
+  LD_LAUNCH(opt_step_kernel<const ld_dn_scaler_state*>, dim3((unsigned)n_wg), dim3(OPT_BS), 0, dn_st(stream), table, n_tensors,
+            grad, exp_avg, exp_avg_sq, ema, (long)flat_floats, sumsq, max_norm, s, state);
+  LD_LAUNCH_CHECK("dn_opt_step_scaled");
   return LD_OK;
 }

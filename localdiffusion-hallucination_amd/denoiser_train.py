@@ -30,8 +30,22 @@ after every step (``replica_digest`` checks it), and a W-rank step equals a one-
 micro-batches in order.  Drawn ``t`` and noise are the rank's rows of what one rank would draw for the global batch (seed all
 ranks alike).  The gather is not overlapped with the backward pass.
 
+Mixed precision as the reference has it (``amp=True, mixed_precision_type="fp16"``, ddpm.py:1269-1284): the online model's
+convolutions run on the fp16 matrix cores (``TrainableUnet.amp``: operands rounded to fp16, everything in memory fp32 -- not
+autocast's fp16 activations) under ``torch.amp.GradScaler``'s loss scaling, whose state (``ld_dn_scaler_state``) and whose
+decisions live on the device.  ``accumulate`` multiplies the loss gradient by the scale it reads there
+(``ld_p_losses_grad_scaled``); ``apply`` puts one one-thread launch, ``ld_dn_opt_scaler_update``, between the norm and the step:
+the squared norm of the scaled gradients is non-finite exactly when one of them is, and from it alone the kernel decides skip or
+step, backs the scale off or grows it, and computes Adam's bias corrections for Adam's OWN step count, which a skipped step
+does not advance; ``ld_dn_opt_step_scaled`` reads all of that from the state, unscales, clips and steps -- or, on a skip,
+leaves parameters and moments alone -- and zeroes the gradients and updates the EMA either way, as the reference does
+(ddpm.py:1560-1571).  Nothing waits for the GPU.  The scale is a power of two and the factors are 2 and 0.5 by default, so
+every scaling and unscaling is exact and ``(g * inv_scale) * coef`` could as well be multiplied in the other order; with
+other ``scaler_kwargs`` factors the order is torch's.  Data parallel: every rank reduces the same gathered bits in rank order,
+so ``found_inf`` and the scale are the same on all ranks with nothing new on the wire.
+
 NOT covered: 16-bit storage, more than one node, ragged shards (a batch size that is no multiple of the world size), a sharded
-evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, fp16 with loss scaling, FID, writing the kernel-layout weight copies from the optimiser launch
+evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, FID, writing the kernel-layout weight copies from the optimiser launch
 (the modules repack after a step, as they do under ``torch.optim.Adam``), handing padded tensors between modules.
 """
 import ctypes as C
@@ -42,7 +56,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import SWITCHES, check_storage_precision, check_switch, stream
+from .trainable import SWITCHES, check_amp_precision, check_storage_precision, check_switch, stream
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -77,13 +91,79 @@ def online_kwargs(model):
                 full_attn=tuple(cfg.full_attn), mode=cfg.mode)
 
 
-def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr, betas, eps, ema_step, initted):
+SCALER_DEFAULTS = dict(init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000)   # GradScaler's
+SCALER_KEYS = ("scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker")           # its state_dict()
+MIXED_PRECISION_TYPES = ("fp16", "bf16")
+
+
+def check_scaler_kwargs(kw):
+    """``SCALER_DEFAULTS`` overridden by ``kw`` (None: nothing), validated: ``init_scale`` a positive power of two (every
+    scaling is then exact), ``growth_factor`` > 1, 0 < ``backoff_factor`` < 1, ``growth_interval`` an int >= 1.  Needs no GPU."""
+    kw = dict(kw or {})
+    unknown = sorted(set(kw) - set(SCALER_DEFAULTS))
+    if unknown:
+        raise ValueError(f"DenoiserTrainer: scaler_kwargs {unknown} are not among {sorted(SCALER_DEFAULTS)}")
+    out = {**SCALER_DEFAULTS, **kw}
+    for k in ("init_scale", "growth_factor", "backoff_factor"):
+        v = out[k]
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
+            raise ValueError(f"DenoiserTrainer: scaler_kwargs {k} = {v!r} must be a finite number")
+        out[k] = float(v)
+    s = out["init_scale"]
+    if s <= 0 or math.frexp(s)[0] != 0.5 or s > 2.0 ** 127 or s < 2.0 ** -126:
+        raise ValueError(f"DenoiserTrainer: scaler_kwargs init_scale = {s!r} must be a positive power of two (an fp32 normal)")
+    if not out["growth_factor"] > 1.0:
+        raise ValueError(f"DenoiserTrainer: scaler_kwargs growth_factor = {out['growth_factor']!r} must be greater than 1")
+    if not 0.0 < out["backoff_factor"] < 1.0:
+        raise ValueError(f"DenoiserTrainer: scaler_kwargs backoff_factor = {out['backoff_factor']!r} must lie in (0, 1)")
+    g = out["growth_interval"]
+    if not isinstance(g, int) or isinstance(g, bool) or g < 1:
+        raise ValueError(f"DenoiserTrainer: scaler_kwargs growth_interval = {g!r} must be an int of at least 1")
+    return out
+
+
+def check_amp(amp, mixed_precision_type, conv_precision, scaler_kwargs):
+    """What ``DenoiserTrainer(amp=, mixed_precision_type=, conv_precision=, scaler_kwargs=)`` means: ``(amp mode of the
+    modules, conv_precision, scaler settings or None)``.  ``conv_precision`` None is "not given".  Needs no GPU."""
+    if not isinstance(amp, bool):
+        raise ValueError(f"DenoiserTrainer: amp = {amp!r} must be True or False")
+    if not isinstance(mixed_precision_type, str) or mixed_precision_type not in MIXED_PRECISION_TYPES:
+        raise ValueError(f"DenoiserTrainer: mixed_precision_type {mixed_precision_type!r} is not one of "
+                         f"{', '.join(repr(v) for v in MIXED_PRECISION_TYPES)}")
+    if not amp:
+        if scaler_kwargs is not None:
+            raise ValueError("DenoiserTrainer: scaler_kwargs without amp=True (there is no loss scaler)")
+        return "no", "fp32" if conv_precision is None else conv_precision, None
+    if mixed_precision_type == "bf16":
+        if conv_precision not in (None, "bf16"):
+            raise ValueError(f"DenoiserTrainer: amp=True with mixed_precision_type 'bf16' is conv_precision 'bf16'; "
+                             f"conv_precision {conv_precision!r} contradicts it")
+        if scaler_kwargs is not None:
+            raise ValueError("DenoiserTrainer: scaler_kwargs with mixed_precision_type 'bf16' (bf16 has fp32's range: no loss scaler)")
+        return "no", "bf16", None
+    conv_precision = "fp32" if conv_precision is None else conv_precision
+    check_amp_precision("DenoiserTrainer", "fp16", conv_precision)
+    return "fp16", conv_precision, check_scaler_kwargs(scaler_kwargs)
+
+
+def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr, betas, eps, ema_step, initted, scaler=None):
     """The dictionary ``Trainer.save`` writes (ddpm.py:1495-1507), from CPU tensors.  ``diffusion_sd``: the
     ``GaussianDiffusion.state_dict()`` (its ``model.*`` entries give the key order and are replaced); ``online_sd`` / ``ema_sd``:
     the online and the EMA weights by the Unet's names, in the order of ``parameters()``; ``moments``: {name: (exp_avg,
     exp_avg_sq)} of the parameters that have them.  ``model`` = the buffers + ``model.<online>``; ``ema`` = the same under
     ``online_model.``, the buffers + ``model.<ema>`` under ``ema_model.``, ``initted`` and ``step``; ``opt`` = a
-    ``torch.optim.Adam.state_dict()`` whose ``state[i]`` exists for the parameters with moments."""
+    ``torch.optim.Adam.state_dict()`` whose ``state[i]`` exists for the parameters with moments and whose ``step`` is
+    ``opt_step`` -- Adam's own count, which under a loss scaler is the number of steps that were not skipped and can be below
+    ``step``.  ``scaler``: None (no amp; the reference writes None too) or ``GradScaler.state_dict()``'s five keys
+    (``SCALER_KEYS``), written under ``'scaler'`` as plain numbers (ddpm.py:1504)."""
+    if scaler is not None:
+        if set(scaler) != set(SCALER_KEYS):
+            raise ValueError(f"checkpoint_dict: scaler must have the keys {SCALER_KEYS}, not {sorted(scaler)}")
+        scaler = {"scale": float(scaler["scale"]), "growth_factor": float(scaler["growth_factor"]),
+                  "backoff_factor": float(scaler["backoff_factor"]), "growth_interval": int(scaler["growth_interval"]),
+                  "_growth_tracker": int(scaler["_growth_tracker"])}
+        if not 0 <= int(opt_step) <= int(step):
+            raise ValueError(f"checkpoint_dict: Adam's step count {opt_step} is not within the trainer's {step} steps")
     def with_weights(w):
         return {k: (w[k[6:]] if k.startswith("model.") else v).detach().cpu().clone() for k, v in diffusion_sd.items()}
     missing = [k for k in diffusion_sd if k.startswith("model.") and k[6:] not in online_sd]
@@ -101,7 +181,7 @@ def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr
             state[i] = {"step": torch.tensor(float(opt_step)), "exp_avg": m.detach().cpu().clone(),
                         "exp_avg_sq": v.detach().cpu().clone()}
     opt = {"state": state, "param_groups": checkpoint.adam_param_groups(len(online_sd), lr, betas, eps)}
-    return {"step": int(step), "model": model, "opt": opt, "ema": ema, "scaler": None}
+    return {"step": int(step), "model": model, "opt": opt, "ema": ema, "scaler": scaler}
 
 
 def shard_rows(n_rows, world, rank):
@@ -168,13 +248,28 @@ class DenoiserTrainer:
     to bf16 for the products, the softmax and its statistics fp32.  The same guarantees: no loss scaling, a step reproducible
     bit for bit, identical replicas, nothing in a checkpoint, the EMA / inference ``Unet`` not involved.
 
-    ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and Adam's step count); ``ema_step`` and
-    ``ema_initted`` are ``ema_pytorch``'s two buffers."""
+    ``amp=True`` (default False) with ``mixed_precision_type="fp16"`` (the default; the reference's two arguments and
+    defaults, ddpm.py:1269-1284) trains with the convolutions on the fp16 matrix cores (``TrainableUnet.amp``) under a loss
+    scaler on the device (the module docstring); ``scaler_kwargs`` overrides ``GradScaler``'s defaults (``SCALER_DEFAULTS``:
+    ``init_scale`` a power of two, ``growth_factor``, ``backoff_factor``, ``growth_interval``).  It covers what
+    ``conv_precision="bf16"`` covers and leaves fp32 what that leaves fp32 (GroupNorm, RMSNorm, the attention cores, the head,
+    the time MLP, everything in memory, the master weights and their gradients); ``conv_precision="bf16"`` with it is
+    refused, and with that the storage switches.  ``amp=True`` with ``mixed_precision_type="bf16"`` is
+    ``conv_precision="bf16"`` and no scaler (an explicit ``conv_precision="fp32"`` contradicts it: ``ValueError``); any other
+    type is a ``ValueError``; ``amp=False`` changes nothing at all.  ``scaler_state()`` reads the scaler back;
+    ``check_finite()`` does not raise under a scaler (a non-finite norm is a skipped step there).
+
+    ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and without a scaler Adam's step count; with one,
+    Adam's count lives on the device and does not advance on a skipped step); ``ema_step`` and ``ema_initted`` are
+    ``ema_pytorch``'s two buffers and advance at every call."""
 
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
-                 conv_precision="fp32", act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32",
-                 full_attn_precision="fp32"):
+                 conv_precision=None, act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32",
+                 full_attn_precision="fp32", amp=False, mixed_precision_type="fp16", scaler_kwargs=None):
+        if conv_precision is not None:
+            check_switch("DenoiserTrainer", "conv_precision", conv_precision)
+        module_amp, conv_precision, scaler = check_amp(amp, mixed_precision_type, conv_precision, scaler_kwargs)
         switches = dict(conv_precision=conv_precision, act_storage=act_storage, conv_out_storage=conv_out_storage,
                         attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         for switch in SWITCHES:
@@ -202,8 +297,9 @@ class DenoiserTrainer:
             if not isinstance(v, int) or isinstance(v, bool) or v < lo:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
         # (raises ValueError for what it cannot train)
-        online = TrainableUnet(**online_kwargs(model), **switches)
+        online = TrainableUnet(**online_kwargs(model), **switches, amp=module_amp)
         vars(self).update(switches)                   # (what the trainer was built with: self.conv_precision and so on)
+        self.amp, self.mixed_precision_type, self.scaler = bool(amp), mixed_precision_type, scaler     # scaler: settings or None
         dev = diffusion.device
         if dev.type != "cuda":
             raise ValueError(f"DenoiserTrainer: diffusion is on {dev}; the trainer runs on HIP kernels only (there is no CPU path)")
@@ -263,10 +359,34 @@ class DenoiserTrainer:
                     self._host_send = torch.empty(self._flat + 4, dtype=torch.float32).pin_memory()
                     self._host_recv = torch.empty(self.world, self._flat + 4, dtype=torch.float32).pin_memory()
             self._work = torch.zeros(1 + int(lib.ld_dn_opt_sqnorm_work_bytes(self._n_wg)) // 8, dtype=torch.float64, device=dev)
+            self._scaler_state = self._scale = None
+            if self.scaler is not None:                     # ld_dn_scaler_state: 8 dwords; its first is the scale
+                self._scaler_state = torch.zeros(C.sizeof(cabi.DnScalerState) // 4, dtype=torch.int32, device=dev)
+                self._scale = self._scaler_state[:1].view(torch.float32)
+                self._init_scaler(self.scaler["init_scale"], 0, 0)
         with torch.no_grad():                               # ema_pytorch: the EMA model starts as a copy of the online one
             for k, p in named:
                 self._segment(self._ema, k).copy_(p.reshape(-1))
         self._attach_grads()
+
+    def _init_scaler(self, scale, adam_steps, growth_tracker, skipped_steps=0):
+        with torch.cuda.device(self.device):
+            cabi.check(cabi.lib().ld_dn_scaler_init(self._scaler_state.data_ptr(), float(scale), int(adam_steps),
+                                                    int(growth_tracker), stream(self.device)), "dn_scaler_init")
+            if skipped_steps:
+                self._scaler_state[3].fill_(int(skipped_steps))
+
+    def scaler_state(self):
+        """The loss scaler as it stands -- the one call that reads ``ld_dn_scaler_state`` back, so it waits for the GPU:
+        ``GradScaler.state_dict()``'s five keys (``SCALER_KEYS``) plus ``adam_steps`` (the optimiser steps that were not
+        skipped), ``skipped_steps`` and ``found_inf`` (whether the last step was skipped).  ``RuntimeError`` without amp."""
+        if self._scaler_state is None:
+            raise RuntimeError("DenoiserTrainer: no loss scaler (amp=True with mixed_precision_type 'fp16' makes one)")
+        st = cabi.DnScalerState.from_buffer_copy(self._scaler_state.cpu().numpy().tobytes())
+        return {"scale": float(st.scale), "growth_factor": self.scaler["growth_factor"],
+                "backoff_factor": self.scaler["backoff_factor"], "growth_interval": self.scaler["growth_interval"],
+                "_growth_tracker": int(st.growth_tracker), "adam_steps": int(st.adam_steps),
+                "skipped_steps": int(st.skipped_steps), "found_inf": bool(st.found_inf)}
 
     def _segment(self, flat, name):
         off, count, _ = self._segments[name]
@@ -328,7 +448,8 @@ class DenoiserTrainer:
                                            gd.loss_weight.data_ptr(), per_sample.data_ptr(), B, x0[0].numel(),
                                            cabi.OBJ[gd.objective], stream(dev)), "p_losses")
                 value = per_sample.mean() * float(scale)
-            out.backward(gd.p_losses_grad(out, x0, noise, t, grad_output=float(scale)))
+            # under amp the upstream scalar is scale * the loss scale, read on the device; ``value`` stays unscaled
+            out.backward(gd.p_losses_grad(out, x0, noise, t, grad_output=float(scale), grad_scale=self._scale))
             if self.data_parallel:
                 self._loss_slot[0].add_(value)
         return value
@@ -373,9 +494,21 @@ class DenoiserTrainer:
                                                      self._loss.data_ptr(), st), "dn_opt_reduce_tail")
                 self._loss_slot.zero_()
                 loss = self._loss[0].clone()
-            cabi.check(lib.ld_dn_opt_step(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(), self._m.data_ptr(),
-                                          self._v.data_ptr(), self._ema.data_ptr(), self._flat, sumsq, self.max_grad_norm, b1, b2,
-                                          self.eps, step_size, bc2_sqrt, mode, 1.0 - decay, st), "dn_opt_step")
+            if self._scaler_state is not None:
+                # sumsq is the squared norm of the SCALED gradients: the update kernel takes the scaler's decisions from it and
+                # leaves found_inf, 1 / scale and Adam's bias corrections (for Adam's own count) where the step reads them
+                sc, state = self.scaler, self._scaler_state.data_ptr()
+                cabi.check(lib.ld_dn_opt_scaler_update(state, sumsq, self.lr, b1, b2, sc["growth_factor"], sc["backoff_factor"],
+                                                       sc["growth_interval"], st), "dn_opt_scaler_update")
+                cabi.check(lib.ld_dn_opt_step_scaled(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(),
+                                                     self._m.data_ptr(), self._v.data_ptr(), self._ema.data_ptr(), self._flat,
+                                                     sumsq, state, self.max_grad_norm, b1, b2, self.eps, mode, 1.0 - decay, st),
+                           "dn_opt_step_scaled")
+            else:
+                cabi.check(lib.ld_dn_opt_step(self._table.data_ptr(), self._n, self._n_wg, self._grad.data_ptr(),
+                                              self._m.data_ptr(), self._v.data_ptr(), self._ema.data_ptr(), self._flat, sumsq,
+                                              self.max_grad_norm, b1, b2, self.eps, step_size, bc2_sqrt, mode, 1.0 - decay, st),
+                           "dn_opt_step")
         # the packed-weight caches are keyed on _version, which a raw kernel write does not move
         torch.autograd.graph.increment_version(self._params)
         self.last_ema = (mode, decay)                       # what the launch was told: (EMA_KEEP / EMA_COPY / EMA_LERP, decay)
@@ -451,9 +584,12 @@ class DenoiserTrainer:
         return dict(step=self.step, sumsq=float(mine[0]), weight_sum=float(mine[1]), weight_xor=int(mine[2]))
 
     def check_finite(self):
-        """Read the last step's gradient norm back (the one place that does) and raise on a non-finite value; returns it."""
-        norm = math.sqrt(float(self._work[0].item())) if self.step else 0.0
-        if not math.isfinite(norm):
+        """Read the last step's gradient norm back (the one place that does) and raise on a non-finite value; returns it.
+        Under a loss scaler it is the norm of the SCALED gradients, and a non-finite one is a skipped step, not an error: it is
+        returned (``inf`` / ``nan``) without raising."""
+        sumsq = float(self._work[0].item()) if self.step else 0.0
+        norm = math.sqrt(sumsq) if sumsq >= 0.0 else sumsq          # (a NaN or a negative garbage value stays what it is)
+        if not math.isfinite(norm) and self._scaler_state is None:
             raise FloatingPointError(f"DenoiserTrainer: the gradient norm of step {self.step} is {norm}; the weights and moments "
                                      "took the step as torch would have (they hold NaN now)")
         return norm
@@ -494,8 +630,12 @@ class DenoiserTrainer:
         cpu = lambda d: {k: v.detach().cpu() for k, v in d.items()}                        # noqa: E731
         moments = {k: (m.cpu(), v.cpu()) for k, (m, v) in self.moments().items()}
         online = {k: p for k, p in self.online_model.named_parameters()}
+        opt_step, scaler = self.step, None
+        if self._scaler_state is not None:
+            full = self.scaler_state()
+            opt_step, scaler = full["adam_steps"], {k: full[k] for k in SCALER_KEYS}
         return checkpoint_dict(self.step, cpu(self.diffusion.state_dict()), cpu(online), cpu(self.ema_state_dict()), moments,
-                               self.step, self.lr, self.betas, self.eps, self.ema_step, self.ema_initted)
+                               opt_step, self.lr, self.betas, self.eps, self.ema_step, self.ema_initted, scaler=scaler)
 
     def save(self, path):
         """Write the reference's ``Trainer.save`` file (``checkpoint.load_reference_checkpoint`` and the reference's own
@@ -504,7 +644,10 @@ class DenoiserTrainer:
 
     def load(self, path, trust_pickle=False):
         """Restore what ``save`` wrote (or the reference's ``Trainer.save``): the EMA weights into ``diffusion`` and the EMA
-        buffer, the online weights, both moments, Adam's step count and the counters."""
+        buffer, the online weights, both moments, Adam's step count and the counters.  A trainer with a loss scaler takes
+        ``scale`` and ``_growth_tracker`` from the file's ``'scaler'`` when it has them (else it keeps its own scale) and
+        accepts an Adam step count below ``step`` (steps were skipped); one without ignores ``'scaler'``, as the reference
+        does (ddpm.py:1526-1527), and keeps the check that the two counts are equal."""
         data = checkpoint._read(path, trust_pickle)
         info = checkpoint.load_reference_checkpoint(data, self.diffusion, use_ema=True)
         if info["source"] != "ema":
@@ -528,7 +671,17 @@ class DenoiserTrainer:
         if len(steps) > 1:
             raise RuntimeError(f"DenoiserTrainer.load: the parameters' Adam step counts differ ({sorted(steps)[:4]})")
         self.step = int(data["step"])
-        if steps and steps != {self.step}:
+        if self._scaler_state is not None:
+            adam_steps = min(steps) if steps else self.step
+            if not 0 <= adam_steps <= self.step:
+                raise RuntimeError(f"DenoiserTrainer.load: Adam's step count {adam_steps} is not within the trainer's step {self.step}")
+            saved = data.get("scaler") or {}
+            if "scale" in saved and "_growth_tracker" in saved:
+                scale, tracker = float(saved["scale"]), int(saved["_growth_tracker"])
+            else:
+                scale, tracker = self.scaler_state()["scale"], 0
+            self._init_scaler(scale, adam_steps, tracker, skipped_steps=self.step - adam_steps)
+        elif steps and steps != {self.step}:
             raise RuntimeError(f"DenoiserTrainer.load: Adam's step count {steps} is not the trainer's step {self.step}")
         self.ema_step, self.ema_initted = int(data["ema"]["step"]), bool(data["ema"]["initted"])
         self._attach_grads()

@@ -751,10 +751,12 @@ class GaussianDiffusion(nn.Module):
         return (total, loss) if per_sample else total
 
     @torch.no_grad()
-    def p_losses_grad(self, model_out, x_start, noise, t, grad_output=1.0):
+    def p_losses_grad(self, model_out, x_start, noise, t, grad_output=1.0, grad_scale=None):
         """d loss / d ``model_out`` for the loss ``p_losses`` returns (the batch mean of ``loss_weight[t]`` times the
         per-sample mean squared error against the objective's target, ddpm.py:1186-1201), all three objectives;
-        ``grad_output`` is the upstream scalar.  ``model_out``, ``x_start``, ``noise``: [B, ...] of one shape, ``t`` [B]."""
+        ``grad_output`` is the upstream scalar.  ``model_out``, ``x_start``, ``noise``: [B, ...] of one shape, ``t`` [B].
+        ``grad_scale``: a one-element fp32 tensor on the device (a loss scale); the upstream scalar is then ``grad_output``
+        times its value, read by the kernel (``ld_p_losses_grad_scaled``): the host does not wait for it."""
         dev = self.device
         mo = model_out.detach().to(dev, torch.float32).contiguous()
         x0 = x_start.to(dev, torch.float32).contiguous()
@@ -764,6 +766,17 @@ class GaussianDiffusion(nn.Module):
                              f"must agree and t must be [{mo.shape[0]}]")
         t32 = t.to(dev, torch.int32).contiguous()
         out = torch.empty_like(mo)
+        if grad_scale is not None:
+            if not (isinstance(grad_scale, torch.Tensor) and grad_scale.dtype == torch.float32 and grad_scale.numel() == 1
+                    and grad_scale.device == mo.device):
+                raise ValueError(f"p_losses_grad: grad_scale must be a one-element float32 tensor on {mo.device}")
+            cabi.check(cabi.lib().ld_p_losses_grad_scaled(mo.data_ptr(), x0.data_ptr(), nz.data_ptr(), t32.data_ptr(),
+                                                          self.sqrt_alphas_cumprod.data_ptr(),
+                                                          self.sqrt_one_minus_alphas_cumprod.data_ptr(), self.loss_weight.data_ptr(),
+                                                          float(grad_output), grad_scale.data_ptr(), out.data_ptr(), mo.shape[0],
+                                                          mo[0].numel(), cabi.OBJ[self.objective], self._st()),
+                       "p_losses_grad_scaled")
+            return out
         cabi.check(cabi.lib().ld_p_losses_grad(mo.data_ptr(), x0.data_ptr(), nz.data_ptr(), t32.data_ptr(),
                                                self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
                                                self.loss_weight.data_ptr(), float(grad_output), out.data_ptr(), mo.shape[0],

@@ -61,7 +61,7 @@ class AttentionPacked:
 
     def __init__(self, mod, to_out, dev):
         lib, st = cabi.lib(), stream(dev)
-        prec = mod.conv_precision
+        prec = mod.operand_precision
         self.wqf, self.wqd = pack_conv(lib, st, mod.to_qkv.weight, 3 * mod.hidden, mod.ld3, mod.dim, mod.cp, 1, prec)
         self.wof, self.wod = pack_conv(lib, st, to_out.weight, mod.dim, mod.cp, mod.hidden, mod.hp, 1, prec)
         self.bo = pack_vec(to_out.bias, mod.cp)

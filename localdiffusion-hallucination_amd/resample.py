@@ -99,7 +99,7 @@ class Downsample(TrainableModule):
         p.wf, p.wd = w.new_zeros(cop * C4), w.new_zeros(C4 * cop)    # [cop][p dim + c] and its transpose [p dim + c][cop]
         cabi.check(lib.ld_seg_permute3(w.data_ptr(), p.wf.data_ptr(), co, self.dim, 4, 0, C4, 1, self.dim, st), "permute3")
         cabi.check(lib.ld_seg_permute3(w.data_ptr(), p.wd.data_ptr(), co, self.dim, 4, 0, 1, cop, self.dim * cop, st), "permute3")
-        p.wf, p.wd = (as_conv_precision(t, self.conv_precision) for t in (p.wf, p.wd))     # (its own layout: not pack_conv's)
+        p.wf, p.wd = (as_conv_precision(t, self.operand_precision) for t in (p.wf, p.wd))     # (its own layout: not pack_conv's)
         p.b = pack_vec(conv.bias, cop)
         p.ones, p.zeros = ones_zeros(max(C4, cop), dev)
         return p
@@ -159,7 +159,7 @@ class Upsample(TrainableModule):
     def _pack(self, dev):
         lib, st, p = cabi.lib(), stream(dev), _Packed()
         conv = self._modules["1"]
-        p.wf, p.wd = pack_conv(lib, st, conv.weight, self.dim_out, self.cop, self.dim, self.cip, 3, self.conv_precision)
+        p.wf, p.wd = pack_conv(lib, st, conv.weight, self.dim_out, self.cop, self.dim, self.cip, 3, self.operand_precision)
         p.b = pack_vec(conv.bias, self.cop)
         p.ones, p.zeros = ones_zeros(max(self.cip, self.cop), dev)
         return p
@@ -268,9 +268,9 @@ class Conv2d(TrainableModule):
             p.w, p.b = self.weight.detach().contiguous(), self.bias.detach().contiguous()
             return p
         if self.use == "stem":                                       # OIHW is [co][49 ci] in memory: a 1x1 over the columns
-            p.wf, p.wd = pack_conv(lib, st, self.weight, co, self.cop, 49 * ci, self.cip, 1, self.conv_precision)
+            p.wf, p.wd = pack_conv(lib, st, self.weight, co, self.cop, 49 * ci, self.cip, 1, self.operand_precision)
         else:
-            p.wf, p.wd = pack_conv(lib, st, self.weight, co, self.cop, ci, self.cip, 3, self.conv_precision)
+            p.wf, p.wd = pack_conv(lib, st, self.weight, co, self.cop, ci, self.cip, 3, self.operand_precision)
         p.b = pack_vec(self.bias, self.cop)
         p.ones, p.zeros = ones_zeros(max(self.cip, self.cop), dev)
         return p

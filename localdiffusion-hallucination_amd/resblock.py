@@ -46,14 +46,14 @@ class _Packed:
     def __init__(self, blk, dev):
         lib, st = cabi.lib(), stream(dev)
         ci, co, cip, cop = blk.dim, blk.dim_out, blk.cip, blk.cop
-        self.w1f, self.w1d = pack_conv(lib, st, blk.block1.proj.weight, co, cop, ci, cip, 3, blk.conv_precision)
-        self.w2f, self.w2d = pack_conv(lib, st, blk.block2.proj.weight, co, cop, co, cop, 3, blk.conv_precision)
+        self.w1f, self.w1d = pack_conv(lib, st, blk.block1.proj.weight, co, cop, ci, cip, 3, blk.operand_precision)
+        self.w2f, self.w2d = pack_conv(lib, st, blk.block2.proj.weight, co, cop, co, cop, 3, blk.operand_precision)
         self.b1, self.b2 = pack_vec(blk.block1.proj.bias, cop), pack_vec(blk.block2.proj.bias, cop)
         self.g1, self.be1 = pack_vec(blk.block1.norm.weight, co), pack_vec(blk.block1.norm.bias, co)
         self.g2, self.be2 = pack_vec(blk.block2.norm.weight, co), pack_vec(blk.block2.norm.bias, co)
         self.wrf = self.wrd = self.br = None
         if blk.has_res_conv:
-            self.wrf, self.wrd = pack_conv(lib, st, blk.res_conv.weight, co, cop, ci, cip, 1, blk.conv_precision)
+            self.wrf, self.wrd = pack_conv(lib, st, blk.res_conv.weight, co, cop, ci, cip, 1, blk.operand_precision)
             self.br = pack_vec(blk.res_conv.bias, cop)
         self.ones, self.zeros = ones_zeros(max(cip, cop), dev)
 

@@ -27,6 +27,17 @@ more than one, and ``DenoiserTrainer`` passes it through.
                            Unlike ``act_storage`` it moves results, by about what the bf16 convolutions themselves do.
   ``attn_precision``       ``LinearAttention``: the four passes of its core on ``csrc/linattn16.hip`` (a placeholder on ``Attention``).
   ``full_attn_precision``  ``Attention``: the three passes of its core on ``csrc/attention16.hip``.
+
+``amp`` (``AMP_TYPES``: ``"no"``, the default, or ``"fp16"``) is the reference's mixed-precision mode under the reference's name
+and is NOT one of ``SWITCHES`` (those are fp32 / bf16 pairs): at ``"fp16"`` every launch that ``conv_precision = "bf16"`` would
+put on the bf16 matrix cores -- the 3x3 and 1x1 convolutions, the im2col convolutions, ``to_qkv`` / ``to_out``, and both of
+their gradients -- runs on the fp16 forms of ``csrc/conv16.hip`` instead (``ld_dn_conv_f16``, ``ld_dn_wgrad_f16``,
+``ld_dn_pack_conv_f16``): operands rounded to fp16, fp32 accumulation, fp16 kernel-layout weights (``amp`` is in their cache
+key), and everything in memory and everything else fp32.  fp16 has three more significand bits than bf16 and a narrow range: a
+large operand becomes inf and a small one underflows, so this mode is meant to run under the loss scaler of
+``DenoiserTrainer(amp=True)``.  It is validated on assignment like a switch, handed down by ``TrainableUnet`` like
+``conv_precision``, no part of a ``state_dict``, and refused together with ``conv_precision = "bf16"`` (two masters for the
+same launches); the storage switches need ``conv_precision = "bf16"`` and so stay out of reach.
 """
 import ctypes as C
 
@@ -63,7 +74,7 @@ class PackedWeights:
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def _packed_for(self, dev):
-        key = (dev, getattr(self, "conv_precision", "fp32")) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = (dev, getattr(self, "conv_precision", "fp32"), getattr(self, "amp", "no")) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._packed is None or self._packed[0] != key:
             with torch.no_grad():
                 self._packed = (key, self._pack(dev))
@@ -80,6 +91,19 @@ def check_switch(owner, switch, value, allowed=("fp32", "bf16")):
     if not isinstance(value, str) or value not in allowed:
         raise ValueError(f"{owner}: {switch} {value!r} is not one of {', '.join(repr(v) for v in allowed)}")
     return value
+
+
+AMP_TYPES = ("no", "fp16")      # TrainableModule.amp (the module docstring); outside SWITCHES
+
+
+def check_amp_precision(name, amp, conv_precision):
+    """``amp = "fp16"`` and ``conv_precision = "bf16"`` both route the convolution launches: together they are refused."""
+    if amp == "fp16" and conv_precision == "bf16":
+        raise ValueError(f"{name}: amp 'fp16' and conv_precision 'bf16' both choose the operand format of the convolutions; "
+                         "set one of them")
+
+
+_OPERAND_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
 def check_act_storage(name, value, allowed=("fp32", "bf16")):
@@ -107,12 +131,14 @@ def check_act_storage_precision(name, act_storage, conv_precision):
 
 def pack_conv(lib, st, w, co, cop, ci, cip, k, precision="fp32"):
     """OIHW [co, ci, k, k] -> forward layout [cop][k*k][cip] and data-gradient layout [cip][flipped k*k][cop], zero in the
-    padded channels; fp32, or with ``precision="bf16"`` rounded to bf16 (what ``Run.conv`` then takes), in one launch."""
+    padded channels; fp32, or with ``precision="bf16"`` / ``"fp16"`` (a module's ``operand_precision``) rounded to that
+    format (what ``Run.conv`` then takes), in one launch."""
     w = w.detach().contiguous()
     kk = k * k
-    if precision == "bf16":
-        fwd, dgr = (torch.empty(cop * kk * cip, dtype=torch.bfloat16, device=w.device) for _ in range(2))
-        cabi.check(lib.ld_dn_pack_conv16(w.data_ptr(), fwd.data_ptr(), dgr.data_ptr(), co, cop, ci, cip, k, st), "dn_pack_conv16")
+    if precision in _OPERAND_DTYPES:
+        fwd, dgr = (torch.empty(cop * kk * cip, dtype=_OPERAND_DTYPES[precision], device=w.device) for _ in range(2))
+        pack, what = (lib.ld_dn_pack_conv16, "dn_pack_conv16") if precision == "bf16" else (lib.ld_dn_pack_conv_f16, "dn_pack_conv_f16")
+        cabi.check(pack(w.data_ptr(), fwd.data_ptr(), dgr.data_ptr(), co, cop, ci, cip, k, st), what)
         return fwd, dgr
     fwd, dgr = w.new_zeros(cop * kk * cip), w.new_zeros(cip * kk * cop)
     cabi.check(lib.ld_seg_permute3(w.data_ptr(), fwd.data_ptr(), co, ci, kk, 0, kk * cip, 1, cip, st), "permute3")
@@ -122,8 +148,8 @@ def pack_conv(lib, st, w, co, cop, ci, cip, k, precision="fp32"):
 
 def as_conv_precision(t, precision):
     """A kernel-layout weight a module packed by itself (fp32), as ``Run.conv`` takes it at ``precision``: rounded to bf16
-    (torch's cast: round-to-nearest-even, as ``ld_dn_pack_conv16`` rounds) or as it is."""
-    return t.to(torch.bfloat16) if precision == "bf16" else t
+    or fp16 (torch's cast: round-to-nearest-even, overflow to inf, as ``ld_dn_pack_conv16`` / ``_f16`` round) or as it is."""
+    return t.to(_OPERAND_DTYPES[precision]) if precision in _OPERAND_DTYPES else t
 
 
 def pack_vec(v, n):
@@ -151,6 +177,8 @@ class Run:
         self.lib, self.st = cabi.lib(), stream(dev)
         self.fill = mod.debug_fill
         self.bf16 = getattr(mod, "conv_precision", "fp32") == "bf16"      # (the precision ``packed`` was made at)
+        self.fp16 = getattr(mod, "amp", "no") == "fp16"                   # amp: the same launches on the fp16 matrix cores
+        self.wdtype = torch.bfloat16 if self.bf16 else torch.float16 if self.fp16 else torch.float32
         self.act16 = getattr(mod, "act_storage", "fp32") == "bf16"        # conv-only activations are kept as bf16
         self.y16 = getattr(mod, "conv_out_storage", "fp32") == "bf16"     # the convolution outputs GroupNorm reads, too
 
@@ -205,10 +233,14 @@ class Run:
         a.src, a.weight, a.scale, a.shift = src.data_ptr(), weight.data_ptr(), self.p.ones.data_ptr(), shift.data_ptr()
         a.residual, a.out = cabi.ptr(residual), out.data_ptr()
         a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.Cout, a.ksize, a.stride, a.relu = self.B, H, W, cin, H, W, cout, k, 1, 0
-        if (weight.dtype == torch.bfloat16) != self.bf16:
+        if weight.dtype != self.wdtype:
             raise RuntimeError(f"{type(self.mod).__name__}: a {weight.dtype} kernel-layout weight at conv_precision "
-                               f"{'bf16' if self.bf16 else 'fp32'} (the module's _pack does not pass the precision on)")
-        if self.from16(src) or self.bf16:
+                               f"{'bf16' if self.bf16 else 'fp32'}{', amp fp16' if self.fp16 else ''} (the module's _pack does "
+                               "not pass the precision on)")
+        if self.fp16:
+            a.weight = None
+            cabi.check(self.lib.ld_dn_conv_f16(C.byref(a), weight.data_ptr(), self.st), "dn_conv_f16")
+        elif self.from16(src) or self.bf16:
             what = "dn_conv16" + ("_from16" if src.dtype == torch.bfloat16 else "") + ("_to16" if to16 else "")
             a.weight = None
             cabi.check(getattr(self.lib, "ld_" + what)(C.byref(a), weight.data_ptr(), self.st), what)
@@ -223,7 +255,9 @@ class Run:
         kk = k * k
         splits = int(self.lib.ld_seg_wgrad_splits(B, H, W, cip, cop, k))
         work, dwp = self.empty(splits * cop * kk * cip), self.empty(cop * kk * cip)
-        if self.from16(a):
+        if self.fp16:
+            wgrad, what = self.lib.ld_dn_wgrad_f16, "dn_wgrad_f16"
+        elif self.from16(a):
             wgrad, what = self.lib.ld_dn_wgrad16_from16, "dn_wgrad16_from16"
         else:
             wgrad, what = (self.lib.ld_dn_wgrad16, "dn_wgrad16") if self.bf16 else (self.lib.ld_seg_wgrad, "seg_wgrad")
@@ -287,6 +321,8 @@ class TrainableModule(PackedWeights, nn.Module):
     #                          are written, read and saved as bf16; at conv_precision "bf16" only, where no result changes
     conv_out_storage = "fp32"  # or "bf16" where the module has it (CONV_OUT_STORAGES): the convolution outputs that GroupNorm
     #                            reads are written rounded to bf16, read and saved as that; at conv_precision "bf16" only
+    amp = "no"               # or "fp16" (AMP_TYPES; not one of SWITCHES): what conv_precision "bf16" routes to the bf16 matrix
+    #                          cores runs on the fp16 ones instead; refused together with conv_precision "bf16"
     CONV_PRECISIONS = ("fp32", "bf16")
     ACT_STORAGES = ("fp32",)
     CONV_OUT_STORAGES = ("fp32",)
@@ -295,7 +331,17 @@ class TrainableModule(PackedWeights, nn.Module):
     def __setattr__(self, name, value):
         if name in SWITCHES and hasattr(type(self), name):
             check_switch(type(self).__name__, name, value, getattr(self, SWITCHES[name]))
+        if name == "amp":
+            check_amp_precision(type(self).__name__, check_switch(type(self).__name__, name, value, AMP_TYPES), self.conv_precision)
+        elif name == "conv_precision":
+            check_amp_precision(type(self).__name__, self.amp, value)
         super().__setattr__(name, value)
+
+    @property
+    def operand_precision(self):
+        """What ``pack_conv`` / ``as_conv_precision`` make the kernel-layout weights at: ``"fp16"`` under ``amp``, else
+        ``conv_precision``."""
+        return "fp16" if self.amp == "fp16" else self.conv_precision
 
     def _run(self, x):
         return self.Run(self, self._packed_for(x.device), x.device, x.shape[0], x.shape[2], x.shape[3])

@@ -33,7 +33,7 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import SWITCHES, check_switch, pad64, stream
+from .trainable import AMP_TYPES, SWITCHES, TrainableModule, check_amp_precision, check_switch, pad64, stream
 from .weights import UnetConfig
 
 
@@ -183,7 +183,10 @@ def _switch(name, doc):
         return getattr(self, "_" + name)
 
     def hand_down(self, value):
-        setattr(self, "_" + name, check_switch("TrainableUnet", name, value))
+        check_switch("TrainableUnet", name, value)
+        if name == "conv_precision":
+            check_amp_precision("TrainableUnet", getattr(self, "_amp", "no"), value)
+        setattr(self, "_" + name, value)
         for m in self.modules():
             if len(getattr(type(m), SWITCHES[name], ())) > 1:
                 setattr(m, name, value)
@@ -206,8 +209,9 @@ class TrainableUnet(nn.Module):
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
-                 act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32", full_attn_precision="fp32"):
+                 act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32", full_attn_precision="fp32", amp="no"):
         super().__init__()
+        check_amp_precision("TrainableUnet", check_switch("TrainableUnet", "amp", amp, AMP_TYPES), conv_precision)
         switches = dict(conv_precision=conv_precision, act_storage=act_storage, conv_out_storage=conv_out_storage,
                         attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         for switch in SWITCHES:
@@ -271,6 +275,9 @@ class TrainableUnet(nn.Module):
             setattr(self, "_" + switch, "fp32")
             if value != "fp32":                      # (the default is the modules' class attribute: nothing to hand down)
                 setattr(self, switch, value)
+        self._amp = "no"
+        if amp != "no":
+            self.amp = amp
 
     @property
     def downsample_factor(self):
@@ -304,6 +311,22 @@ class TrainableUnet(nn.Module):
         modules have a switch of their own (``full_attn_precision``) and are not touched.""")
     full_attn_precision = _switch("full_attn_precision", """``"fp32"`` or ``"bf16"``: at ``"bf16"`` every full-softmax
         ``Attention`` runs the three passes of its core on the bf16 matrix cores (``Attention.full_attn_precision``).""")
+
+    @property
+    def amp(self):
+        """``"no"`` or ``"fp16"`` (``trainable.AMP_TYPES``; the reference's mixed-precision mode, not one of the switches): at
+        ``"fp16"`` every launch that ``conv_precision = "bf16"`` would route runs on the fp16 matrix cores instead
+        (``TrainableModule.amp``), everything else stays fp32.  Handed to every ``TrainableModule``; refused together with
+        ``conv_precision = "bf16"``, and a refused value changes nothing."""
+        return self._amp
+
+    @amp.setter
+    def amp(self, value):
+        check_amp_precision("TrainableUnet", check_switch("TrainableUnet", "amp", value, AMP_TYPES), self._conv_precision)
+        self._amp = value
+        for m in self.modules():
+            if isinstance(m, TrainableModule):
+                m.amp = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

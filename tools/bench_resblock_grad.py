@@ -59,6 +59,7 @@ def run_case(dim, H, a):
     switches = grad_bench.switch_values(a, SWITCHES)
     for s, v in switches.items():
         setattr(blk, s, v)
+    blk.amp = a.amp
     x = torch.randn(B, dim, H, H, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
     temb = torch.randn(B, TIME_DIM, device="cuda").requires_grad_(True)
     dout = (torch.randn(B, dim, H, H, device="cuda") / (B * H * H)).contiguous(memory_format=torch.channels_last)
@@ -80,7 +81,7 @@ def run_case(dim, H, a):
     gn_launches = [(label, ms) for label, ms in calls if label.startswith("dn_gn_")]
     eager = {} if a.no_eager else grad_bench.eager_ms(blk, eager_block, x, [temb], dout, a.iters, a.warmup)
     best = min(eager.values()) if eager else None
-    return dict(dim=dim, H=H, B=B, **switches, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(dim=dim, H=H, B=B, **switches, amp=a.amp, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), kernels_ms=sum(v[0] for v in split.values()),
                 gn_backward_passes_ms=gn_pass_ms, gn_backward_mb=gn_bytes(dim, B, H, y_bytes) / 1e6, gn_launches_ms=gn_launches,
                 gn_backward_gbs=(gn_bytes(dim, B, H, y_bytes) / (gn_pass_ms * 1e6) if gn_pass_ms else None),
@@ -92,7 +93,7 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:8.3f} ms, channels_last {r['eager_nhwc_ms']:8.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f})")
-    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']}: HIP {r['hip_ms']:8.3f} ms   "
+    print(f"{r['dim']:4d}->{r['dim']:<4d} @{r['H']:3d}^2 B={r['B']} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']}{grad_bench.amp_tag(r)}: HIP {r['hip_ms']:8.3f} ms   "
           f"{eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
     if r["gn_backward_gbs"]:
@@ -104,4 +105,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report, switches=SWITCHES))
+    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64,256:32", run_case, report, switches=SWITCHES, amp=True))

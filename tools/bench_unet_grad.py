@@ -4,6 +4,7 @@ restated in eager PyTorch (autograd, MIOpen convolutions, ``F.group_norm``, eins
 fp32, ms per forward + backward.
 
   python tools/bench_unet_grad.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300] [--conv-precision fp32|bf16]
+                                  [--amp no|fp16]
                                   [--act-storage fp32|bf16] [--conv-out-storage fp32|bf16]
 A case is data:H = W:batch; the default cases are cfg3 (mvtec, 3 x 256^2, B = 8), mri at 256^2 with B = 8 and mnist at 28^2
 with B = 64.  Every case runs in a child process of its own under a time limit (``--timeout`` seconds; the HIP and the eager
@@ -14,7 +15,8 @@ the library's per-launch timing session gives the launch count and the split of 
 with the boundary repacks (``dn_pack_nhwc``), the glue (``dn_join``) and the time MLP each named.  Prints one line per case,
 the split, and a JSON list at the end.  ``--conv-precision bf16`` times the HIP net with its convolutions on the bf16 matrix
 cores (``TrainableUnet(conv_precision="bf16")``); eager PyTorch stays fp32, and the printed output difference then holds the
-operands' rounding.  ``--act-storage bf16`` (with ``--conv-precision bf16``) keeps the activations that only convolutions read
+operands' rounding.  ``--amp fp16`` times it with the same launches on the fp16 matrix cores (``TrainableUnet(amp="fp16")``; no
+loss scaling here: the gradients of sum(out * dout) stay in fp16's range).  ``--act-storage bf16`` (with ``--conv-precision bf16``) keeps the activations that only convolutions read
 as bf16 (``TrainableUnet(act_storage="bf16")``): the same results; the row's ``peak_mb`` (``torch.cuda.max_memory_allocated`` over
 the timed HIP calls) shows what it saves.  ``--conv-out-storage bf16`` (with ``--conv-precision bf16`` as well) keeps the
 convolution outputs that the ``ResnetBlock``s' GroupNorms read as bf16 (``TrainableUnet(conv_out_storage="bf16")``); every row
@@ -41,6 +43,8 @@ FAMILIES = (("dn_pack_nhwc", "dn_pack_nhwc (boundary repacks)"), ("dn_join", "dn
             ("dn_conv16_from16 (forward)", "convolutions, forward"), ("dn_conv16_from16 (data gradient)", "convolutions, data gradient"),
             ("dn_conv16_to16 (forward)", "convolutions, forward"), ("dn_conv16_from16_to16 (forward)", "convolutions, forward"),
             ("dn_wgrad16", "convolutions, weight gradient"), ("dn_pack_conv16", "weight packing (bf16)"),
+            ("dn_conv_f16 (forward)", "convolutions, forward"), ("dn_conv_f16 (data gradient)", "convolutions, data gradient"),
+            ("dn_wgrad_f16", "convolutions, weight gradient"), ("dn_pack_conv_f16", "weight packing (fp16)"),
             ("dn_colsum", "bias gradients"), ("dn_gn", "GroupNorm"), ("dn_la_", "linear attention"), ("dn_fa_", "full attention"),
             ("dn_rms_", "RMSNorm"), ("dn_head_", "head"), ("seg_pool", "max pool"))
 SWITCHES = tuple(grad_bench.SWITCH_HELP)            # every training precision switch: all are TrainableUnet arguments
@@ -168,7 +172,7 @@ def families(split):
 def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
-    net = ldh.TrainableUnet(dim=32, **grad_bench.switch_values(a, SWITCHES), **KWARGS[data]).cuda()
+    net = ldh.TrainableUnet(dim=32, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -203,7 +207,7 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, **grad_bench.switch_values(a, SWITCHES), peak_mb=peak / 2 ** 20,
+    return dict(data=data, H=H, B=B, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, peak_mb=peak / 2 ** 20,
                 conv_out_bf16_saves_mb=y_saving / 2 ** 20, resnet_blocks=len(seen), hip_ms=hip, eager_nchw_ms=eager.get("nchw"),
                 eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
@@ -215,11 +219,11 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:9.3f} ms, channels_last {r['eager_nhwc_ms']:9.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f}; outputs differ by {r['out_diff_to_eager']:.1e})")
-    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']} / attn {r['attn_precision']} / full attn {r['full_attn_precision']}: HIP {r['hip_ms']:9.3f} ms, "
+    print(f"{r['data']:5s} @{r['H']:3d}^2 B={r['B']:<2d} {r['conv_precision']} / act {r['act_storage']} / conv out {r['conv_out_storage']} / attn {r['attn_precision']} / full attn {r['full_attn_precision']}{grad_bench.amp_tag(r)}: HIP {r['hip_ms']:9.3f} ms, "
           f"peak {r['peak_mb']:8.1f} MiB (y1 / y2 of the {r['resnet_blocks']} ResnetBlocks as bf16 {'save' if r['conv_out_storage'] == 'bf16' else 'would save'} "
           f"{r['conv_out_bf16_saves_mb']:.1f} MiB of what autograd keeps), {r['launches']} launches, kernels {r['kernels_ms']:9.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, CASES, run_case, report, switches=SWITCHES))
+    sys.exit(grad_bench.main(__file__, CASES, run_case, report, switches=SWITCHES, amp=True))

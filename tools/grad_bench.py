@@ -46,7 +46,7 @@ class TimedLib:
 
         def wrapped(*args):
             label = name[3:]
-            if name == "ld_pc_conv" or name.startswith("ld_dn_conv16"):
+            if name == "ld_pc_conv" or name.startswith(("ld_dn_conv16", "ld_dn_conv_f16")):
                 label += " (forward)" if self.phase == "forward" else " (data gradient)"
             if name in ("ld_dn_pack_nhwc", "ld_dn_pack_nhwc_to16"):
                 label += f" ({self.phase})"
@@ -131,10 +131,20 @@ def switch_values(a, switches):
     return {s: getattr(a, s) for s in switches}
 
 
-def main(tool, cases, run_case, report, heads=False, switches=()):
+AMP_HELP = ("the HIP side's convolutions on the fp16 matrix cores (TrainableModule.amp: fp16 operands, fp32 accumulation; not "
+            "together with --conv-precision bf16); a trainer also runs its loss scaler")
+
+
+def amp_tag(row):
+    """What a report line says about ``--amp``: nothing unless it was given."""
+    return f" / amp {row['amp']}" if row.get("amp", "no") != "no" else ""
+
+
+def main(tool, cases, run_case, report, heads=False, switches=(), amp=False):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
     returns the case's JSON row and ``report(row)`` prints it.  ``switches``: the training precision switches the tool takes
-    a flag for, e.g. ``("conv_precision", "act_storage")`` (``add_switch_flags``).  Every case runs in a child process
+    a flag for, e.g. ``("conv_precision", "act_storage")`` (``add_switch_flags``); ``amp``: the tool also takes ``--amp
+    no|fp16`` (``args.amp``).  Every case runs in a child process
     (``tool --child``) under ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is
     started on the GPU after it."""
     ap = argparse.ArgumentParser()
@@ -142,6 +152,8 @@ def main(tool, cases, run_case, report, heads=False, switches=()):
     if heads:
         ap.add_argument("--heads", type=int, default=4)
     add_switch_flags(ap, {s: SWITCH_HELP[s] for s in switches})
+    if amp:
+        ap.add_argument("--amp", default="no", choices=["no", "fp16"], help=AMP_HELP)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -154,7 +166,7 @@ def main(tool, cases, run_case, report, heads=False, switches=()):
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup") + tuple(switches) if hasattr(a, k)
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "amp") + tuple(switches) if hasattr(a, k)
                  for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:

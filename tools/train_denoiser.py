@@ -58,6 +58,10 @@ def parse(argv=None):
     ap.add_argument("--objective", default="pred_v", choices=["pred_noise", "pred_x0", "pred_v"])
     ap.add_argument("--train-lr", type=float, default=1e-4)
     grad_bench.add_switch_flags(ap, SWITCH_HELP)
+    ap.add_argument("--amp", action="store_true", help="the reference's mixed precision (Trainer(amp=True)): see --mixed-precision-type")
+    ap.add_argument("--mixed-precision-type", default="fp16", choices=["fp16", "bf16"],
+                    help="with --amp: fp16 = the convolutions on the fp16 matrix cores under a loss scaler on the device "
+                         "(GradScaler's defaults); bf16 = --conv-precision bf16, no scaler")
     ap.add_argument("--save-every", type=int, default=100)
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
@@ -99,8 +103,13 @@ def setup(a, **trainer_kw):
     gd = ldh.GaussianDiffusion(config, net, image_size=int(hr.shape[2]), timesteps=a.timesteps, objective=a.objective)
     if a.init:
         print("init:", checkpoint.load_reference_checkpoint(a.init, gd))
-    trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr,
-                                  **grad_bench.switch_values(a, SWITCH_HELP), **trainer_kw)
+    switches = grad_bench.switch_values(a, SWITCH_HELP)
+    if getattr(a, "amp", False):
+        if a.mixed_precision_type == "bf16" and switches["conv_precision"] == "fp32":
+            del switches["conv_precision"]                    # (the flag's default: --amp chooses)
+        trainer_kw = dict(trainer_kw, amp=True, mixed_precision_type=a.mixed_precision_type)
+    trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr, **switches,
+                                  **trainer_kw)
     return trainer, batches(tr_idx), batches(va_idx)
 
 
@@ -147,6 +156,9 @@ def main(argv=None):
         print(f"train images {sum(b[0].shape[0] for b in train)}, validation images {sum(b[0].shape[0] for b in val)}, "
               f"steps {trainer.step}, ranks {trainer.world}")
         print(f"last gradient norm: {trainer.check_finite():.4f}")
+        if trainer.scaler is not None:
+            s = trainer.scaler_state()
+            print(f"loss scaler: scale {s['scale']:.0f}, {s['adam_steps']} optimiser steps, {s['skipped_steps']} skipped")
         print(f"best evaluation loss: {best:.6f}")
     d = trainer.replica_digest()
     print(f"replica digest: step {d['step']} sumsq {d['sumsq']!r} weight_sum {d['weight_sum']!r} "
