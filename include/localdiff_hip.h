@@ -893,6 +893,21 @@ int ld_dn_la_backward_reduce16(const float* qkv, const float* dout, const float*
  * and the three output formulas in fp32 with the unrounded p and ks, as ld_dn_la_backward_apply writes them. */
 int ld_dn_la_backward_apply16(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
                               const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The same four passes on the fp16 matrix cores (LinearAttention.amp_attn = "fp16"; the <f16> instantiations of the same
+ * kernel templates): the arguments, `work`, parts, refusals and the order of every sum are the ...16 entry points', the
+ * operands are rounded to fp16 instead (v_cvt_pk_f16_f32: round-to-nearest-even, no saturation -- beyond 65504 is inf;
+ * subnormal operands are kept, nothing is flushed) and multiplied by v_mfma_f32_32x32x16_f16.  One operand pair differs, in
+ * backward_apply's dv: ks = exp(k - m) / Z is about 1 / (H W) and would be an fp16 subnormal from 128 x 128 pixels on, so
+ *   dv[e] = sum_d fp16(dctx[d][e] (1 / Z[d])) fp16(exp(k[d] - m[d])),
+ * the division moved to the dctx side and the second operand in (0, 1]; dk keeps the unrounded fp32 ks.  What can leave
+ * fp16's range (a large dout or dctx, q / k / v beyond 65504) becomes inf or underflows: these run under a loss scaler. */
+int ld_dn_la_context_f16(const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W, int heads, int ld3,
+                         void* stream);
+int ld_dn_la_out_f16(const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+int ld_dn_la_backward_reduce_f16(const float* qkv, const float* dout, const float* ctx, double* work, float* dctx, float* rk, int B,
+                                 int H, int W, int heads, int ld3, int ldo, void* stream);
+int ld_dn_la_backward_apply_f16(const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
+                                const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
 
 /* ---- training the denoiser, third slice: csrc/attention_grad.hip ------------------------------------------------------------
  * The core of a trainable full Attention (ddpm.py:253-282, attend.py's non-flash path): softmax(q k^T 32^-0.5) v per
@@ -924,6 +939,13 @@ int ld_dn_fa_forward16(const float* qkv, float* out, float* lse, int B, int H, i
  * sum.  The same two passes as ld_dn_fa_backward. */
 int ld_dn_fa_backward16(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
                         int H, int W, int heads, int ld3, int ldo, void* stream);
+/* The same passes on the fp16 matrix cores (Attention.amp_attn = "fp16"; the <f16> instantiations of the same kernel
+ * templates): the contract of forward16 / backward16 with fp16 rounding of the same operands (q, k, v, dO, p, ds;
+ * v_cvt_pk_f16_f32: round-to-nearest-even, beyond 65504 is inf, subnormals kept) and v_mfma_f32_32x32x16_f16.  A small p or
+ * ds underflows and a large dO overflows: these run under a loss scaler. */
+int ld_dn_fa_forward_f16(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo, void* stream);
+int ld_dn_fa_backward_f16(const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv, int B,
+                          int H, int W, int heads, int ld3, int ldo, void* stream);
 
 /* ---- training the denoiser, fourth slice: csrc/resample_grad.hip -------------------------------------------------------------
  * What the layers between the blocks need besides ld_pc_conv / ld_seg_wgrad / ld_dn_colsum: Downsample's rearrangement

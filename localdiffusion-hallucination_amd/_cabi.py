@@ -297,9 +297,10 @@ _SIGS = {
     "ld_allgather": (C.c_int, [vp, vp, C.c_size_t, vp, vp]),
     "ld_comm_destroy": (C.c_int, [vp]),
 }
-# the bf16 matrix-core sibling of an attention-core entry point takes its arguments
-_SIGS.update({name + "16": _SIGS[name] for name in ("ld_dn_la_context", "ld_dn_la_out", "ld_dn_la_backward_reduce",
-                                                    "ld_dn_la_backward_apply", "ld_dn_fa_forward", "ld_dn_fa_backward")})
+# the bf16 ("16") and fp16 ("_f16") matrix-core siblings of an attention-core entry point take its arguments
+_SIGS.update({name + suffix: _SIGS[name] for suffix in ("16", "_f16")
+              for name in ("ld_dn_la_context", "ld_dn_la_out", "ld_dn_la_backward_reduce", "ld_dn_la_backward_apply",
+                           "ld_dn_fa_forward", "ld_dn_fa_backward")})
 
 EXPORTS = tuple(_SIGS)
 _lib = None

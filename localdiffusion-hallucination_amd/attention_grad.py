@@ -9,7 +9,8 @@ gradients on the transposed weights, ``ld_seg_wgrad`` for the two weight gradien
 softmax attention itself in ``csrc/attention_grad.hip``: ``ld_dn_fa_forward`` (an online softmax over tiles of 64 keys that
 keeps one number per row, ``lse``) and ``ld_dn_fa_backward`` (a row pass for dq, a column pass for dk and dv, the
 probabilities recomputed from ``qkv`` and ``lse``), or their bf16 matrix-core siblings ``ld_dn_fa_forward16`` /
-``ld_dn_fa_backward16`` of ``csrc/attention16.hip`` at ``full_attn_precision = "bf16"``.  fp32 storage, no host synchronisation in either direction, no eager-PyTorch
+``ld_dn_fa_backward16`` of ``csrc/attention16.hip`` at ``full_attn_precision = "bf16"``, or the fp16 ones (``ld_dn_fa_forward_f16``
+/ ``ld_dn_fa_backward_f16``) at ``amp_attn = "fp16"``.  fp32 storage, no host synchronisation in either direction, no eager-PyTorch
 arithmetic on an activation, bit-reproducible results (every sum is added in a fixed order; no floating-point atomics),
 and nothing of size [n, n] is kept or written in either direction.
 
@@ -32,8 +33,10 @@ class _Run(RMSNormRun):
     """The launches of one forward / backward of the module on one device."""
 
     def fa(self, name):
-        """The core's entry point ``ld_dn_fa_<name>`` at the module's ``full_attn_precision`` (read at every launch)."""
-        return getattr(self.lib, f"ld_dn_fa_{name}16" if self.mod.full_attn_precision == "bf16" else f"ld_dn_fa_{name}")
+        """The core's entry point ``ld_dn_fa_<name>`` at the module's ``amp_attn`` / ``full_attn_precision`` (read at every
+        launch; the two are never both set)."""
+        suffix = "_f16" if self.mod.amp_attn == "fp16" else "16" if self.mod.full_attn_precision == "bf16" else ""
+        return getattr(self.lib, f"ld_dn_fa_{name}{suffix}")
 
     def forward(self, x, keep=True):
         m, p, lib = self.mod, self.p, self.lib
@@ -83,13 +86,21 @@ class Attention(TrainableModule):
     ds) rounded to bf16, fp32 accumulation; the logits' scale, the online softmax, its normaliser (the unrounded p), lse,
     delta and everything in memory stay fp32, every sum keeps one order.  It is read at every launch and may change between
     calls; it is no part of the ``state_dict``, of the packed weights' cache key or of a checkpoint, and it is independent
-    of ``attn_precision`` (``LinearAttention``'s switch) and of ``conv_precision``."""
+    of ``attn_precision`` (``LinearAttention``'s switch) and of ``conv_precision``.
+
+    ``amp_attn = "fp16"`` (default ``"fp32"``, ``trainable.AMP_ATTN_TYPES``) runs the same three passes on the fp16 matrix
+    cores (``ld_dn_fa_forward_f16`` / ``ld_dn_fa_backward_f16``): that contract with q, k, v, dO, p and ds rounded to fp16
+    instead (three more significand bits; beyond 65504 is inf and a small p or ds underflows, so it is meant for
+    ``DenoiserTrainer``'s loss scaler).  The same rules, independent of ``amp``; together with ``full_attn_precision =
+    "bf16"`` it is refused with ``ValueError`` in either order of assignment."""
 
     Run = _Run
     attn_precision = "fp32"
     ATTN_PRECISIONS = ("fp32",)
     full_attn_precision = "fp32"
     FULL_ATTN_PRECISIONS = ("fp32", "bf16")
+    amp_attn = "fp32"
+    AMP_ATTN_RIVAL = "full_attn_precision"
 
     def __init__(self, dim, heads=4, dim_head=32):
         super().__init__()

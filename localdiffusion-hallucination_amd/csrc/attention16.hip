@@ -6,6 +6,9 @@
 // ds = p (dP - delta) and the trailing 32^-0.5 are fp32, the formulas of attention_grad.hip.  Tensors, layouts, padding
 // rules and `work` (delta [B, heads, n]) are the fp32 path's.  Nothing of size n x n is written, every sum has one fixed
 // order, no floating-point atomics, nothing allocates.
+// Every kernel is a template on the operand format T: <bf16> is the above (the ...16 entry points), <f16> the same code with
+// pack2<f16> (v_cvt_pk_f16_f32: round-to-nearest-even, no saturation, beyond 65504 is inf) and v_mfma_f32_32x32x16_f16 (the
+// ..._f16 entry points; amp_attn = "fp16"): the same operands rounded, everything else unchanged.
 //
 // The MFMA, its lane map (lane l: r = l & 31, hh = l >> 5) and the swizzle of the cols image are mfma16.hip.h's.  Every pass issues its products transposed, the tile's rows on M and the wave's own 32 rows on N, so that a lane owns one
 // row of its side (a query in the forward and the row pass, a key in the column pass) and that row's q / dO (k / v) is a
@@ -59,20 +62,20 @@ __device__ __forceinline__ F16Raw f16_fetch(const float* __restrict__ src, long 
   }
   return v;
 }
-__device__ __forceinline__ void f16_put_rows(unsigned char* img, const F16Raw& v, int tid) {
+template <typename T> __device__ __forceinline__ void f16_put_rows(unsigned char* img, const F16Raw& v, int tid) {
   const int row = f16_ldrow(tid);
 #pragma unroll
   for (int j = 0; j < 2; ++j)
     *reinterpret_cast<uint2*>(img + (row + j) * F16_RS + 8 * (tid & 7)) =
-        make_uint2(pack_bf16x2(v.x[j].x, v.x[j].y), pack_bf16x2(v.x[j].z, v.x[j].w));
+        make_uint2(pack2<T>(v.x[j].x, v.x[j].y), pack2<T>(v.x[j].z, v.x[j].w));
 }
-__device__ __forceinline__ void f16_put_cols(unsigned char* img, const F16Raw& v, int tid) {
+template <typename T> __device__ __forceinline__ void f16_put_cols(unsigned char* img, const F16Raw& v, int tid) {
   const int rr = tid >> 3, c = 4 * (tid & 7);
   const int at = 4 * (rr & 3);
-  *reinterpret_cast<unsigned*>(img + mfma16_off(c, rr >> 2) + at) = pack_bf16x2(v.x[0].x, v.x[1].x);
-  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 1, rr >> 2) + at) = pack_bf16x2(v.x[0].y, v.x[1].y);
-  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 2, rr >> 2) + at) = pack_bf16x2(v.x[0].z, v.x[1].z);
-  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 3, rr >> 2) + at) = pack_bf16x2(v.x[0].w, v.x[1].w);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c, rr >> 2) + at) = pack2<T>(v.x[0].x, v.x[1].x);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 1, rr >> 2) + at) = pack2<T>(v.x[0].y, v.x[1].y);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 2, rr >> 2) + at) = pack2<T>(v.x[0].z, v.x[1].z);
+  *reinterpret_cast<unsigned*>(img + mfma16_off(c + 3, rr >> 2) + at) = pack2<T>(v.x[0].w, v.x[1].w);
 }
 // A operand of K-step s over channels: row `row` of a rows image, channels 16 s + 8 hh .. + 7
 __device__ __forceinline__ uint4 f16_a_rows(const unsigned char* img, int row, int hh, int s) {
@@ -84,19 +87,19 @@ __device__ __forceinline__ uint4 f16_a_cols(const unsigned char* img, int r, int
 }
 // The lane's B operands of a contraction over channels from its own row in memory: channels 16 s + 8 hh .. + 7; x keeps
 // the 16 unrounded values.
-__device__ __forceinline__ void f16_b_row(const float* __restrict__ src, int hh, uint4 (&b)[2], float (&x)[16]) {
+template <typename T> __device__ __forceinline__ void f16_b_row(const float* __restrict__ src, int hh, uint4 (&b)[2], float (&x)[16]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const float4 u = ld4(src + 16 * s + 8 * hh), w = ld4(src + 16 * s + 8 * hh + 4);
     x[8 * s] = u.x; x[8 * s + 1] = u.y; x[8 * s + 2] = u.z; x[8 * s + 3] = u.w;
     x[8 * s + 4] = w.x; x[8 * s + 5] = w.y; x[8 * s + 6] = w.z; x[8 * s + 7] = w.w;
-    b[s] = make_uint4(pack_bf16x2(u.x, u.y), pack_bf16x2(u.z, u.w), pack_bf16x2(w.x, w.y), pack_bf16x2(w.z, w.w));
+    b[s] = make_uint4(pack2<T>(u.x, u.y), pack2<T>(u.z, u.w), pack2<T>(w.x, w.y), pack2<T>(w.z, w.w));
   }
 }
 // B operand of K-step s of the second product from 16 values in accumulator order
-__device__ __forceinline__ uint4 f16_b_acc(const float (&p)[16], int s) {
-  return make_uint4(pack_bf16x2(p[8 * s], p[8 * s + 1]), pack_bf16x2(p[8 * s + 2], p[8 * s + 3]),
-                    pack_bf16x2(p[8 * s + 4], p[8 * s + 5]), pack_bf16x2(p[8 * s + 6], p[8 * s + 7]));
+template <typename T> __device__ __forceinline__ uint4 f16_b_acc(const float (&p)[16], int s) {
+  return make_uint4(pack2<T>(p[8 * s], p[8 * s + 1]), pack2<T>(p[8 * s + 2], p[8 * s + 3]),
+                    pack2<T>(p[8 * s + 4], p[8 * s + 5]), pack2<T>(p[8 * s + 6], p[8 * s + 7]));
 }
 // The exchange tile [64 rows][F16_TS] fp32: a lane's 16 channels 8 g + 4 hh + i of row `row`, accumulator order
 __device__ __forceinline__ void f16_give(float* tile, int row, int hh, const float (&x)[16]) {
@@ -122,6 +125,7 @@ __device__ __forceinline__ void f16_flush(const float* tile, float* __restrict__
 }
 
 // ================================================================================================ forward
+template <typename T>
 __global__ __launch_bounds__(FA_BS) void fa16_forward_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                               float* __restrict__ lse, long n, int heads, int ld3, int ldo) {
   __shared__ __attribute__((aligned(16))) unsigned char s_k[F16_ROWS];      // K  [key][channel]
@@ -141,22 +145,22 @@ __global__ __launch_bounds__(FA_BS) void fa16_forward_kernel(const float* __rest
   uint4 qb[2];
   {
     float x[16];
-    f16_b_row(base + (size_t)qi * ld3, hh, qb, x);
+    f16_b_row<T>(base + (size_t)qi * ld3, hh, qb, x);
   }
   f32x16 o = mfma16_zero();
   float m = FA_NEG, l = 0.f;
   F16Raw rk = f16_fetch(base + hidden, 0, n, ld3, tid), rv = f16_fetch(base + 2 * hidden, 0, n, ld3, tid);
   for (long j0 = 0; j0 < n; j0 += FA_T) {                   // (uniform: the barriers, the shuffles and the MFMAs)
     __syncthreads();
-    f16_put_rows(s_k, rk, tid);
-    f16_put_cols(s_vt, rv, tid);
+    f16_put_rows<T>(s_k, rk, tid);
+    f16_put_cols<T>(s_vt, rv, tid);
     __syncthreads();
     if (j0 + FA_T < n) {                                    // the next tile's requests fly over the products
       rk = f16_fetch(base + hidden, j0 + FA_T, n, ld3, tid);
       rv = f16_fetch(base + 2 * hidden, j0 + FA_T, n, ld3, tid);
     }
-    f32x16 sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
-    sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
+    f32x16 sa = mfma16<T>(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
+    sa = mfma16<T>(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
     const long key0 = j0 + 32 * kh;
     float s[16], tmax = FA_NEG;
 #pragma unroll
@@ -179,8 +183,8 @@ __global__ __launch_bounds__(FA_BS) void fa16_forward_kernel(const float* __rest
     l = l * alpha + ps;
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[i] *= alpha;
-    o = mfma16(f16_a_cols(s_vt, r, hh, kh, 0), f16_b_acc(p, 0), o);
-    o = mfma16(f16_a_cols(s_vt, r, hh, kh, 1), f16_b_acc(p, 1), o);
+    o = mfma16<T>(f16_a_cols(s_vt, r, hh, kh, 0), f16_b_acc<T>(p, 0), o);
+    o = mfma16<T>(f16_a_cols(s_vt, r, hh, kh, 1), f16_b_acc<T>(p, 1), o);
   }
   // the two waves of a query meet, rescaled to the common maximum, in wave order
   float ov[16];
@@ -212,6 +216,7 @@ __global__ __launch_bounds__(FA_BS) void fa16_forward_kernel(const float* __rest
 }
 
 // ================================================================================================ backward: rows (dq)
+template <typename T>
 __global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
                                                          const float* __restrict__ dout, const float* __restrict__ lse,
                                                          float* __restrict__ delta, float* __restrict__ dqkv, long n, int heads,
@@ -236,9 +241,9 @@ __global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict_
   {
     float x[16], g[16], oo[16];
     uint4 unused[2];
-    f16_b_row(base + (size_t)qi * ld3, hh, qb, x);
-    f16_b_row(dout + ((size_t)b * n + qi) * ldo + h * FA_D, hh, gb, g);
-    f16_b_row(out + ((size_t)b * n + qi) * ldo + h * FA_D, hh, unused, oo);
+    f16_b_row<T>(base + (size_t)qi * ld3, hh, qb, x);
+    f16_b_row<T>(dout + ((size_t)b * n + qi) * ldo + h * FA_D, hh, gb, g);
+    f16_b_row<T>(out + ((size_t)b * n + qi) * ldo + h * FA_D, hh, unused, oo);
     dl = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) dl = fmaf(g[i], oo[i], dl);
@@ -250,18 +255,18 @@ __global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict_
   F16Raw rk = f16_fetch(base + hidden, 0, n, ld3, tid), rv = f16_fetch(base + 2 * hidden, 0, n, ld3, tid);
   for (long j0 = 0; j0 < n; j0 += FA_T) {                   // (uniform: the barriers and the MFMAs)
     __syncthreads();
-    f16_put_rows(s_k, rk, tid);
-    f16_put_cols(s_kt, rk, tid);
-    f16_put_rows(s_v, rv, tid);
+    f16_put_rows<T>(s_k, rk, tid);
+    f16_put_cols<T>(s_kt, rk, tid);
+    f16_put_rows<T>(s_v, rv, tid);
     __syncthreads();
     if (j0 + FA_T < n) {
       rk = f16_fetch(base + hidden, j0 + FA_T, n, ld3, tid);
       rv = f16_fetch(base + 2 * hidden, j0 + FA_T, n, ld3, tid);
     }
-    f32x16 sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
-    sa = mfma16(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
-    f32x16 dp = mfma16(f16_a_rows(s_v, 32 * kh + r, hh, 0), gb[0], mfma16_zero());
-    dp = mfma16(f16_a_rows(s_v, 32 * kh + r, hh, 1), gb[1], dp);
+    f32x16 sa = mfma16<T>(f16_a_rows(s_k, 32 * kh + r, hh, 0), qb[0], mfma16_zero());
+    sa = mfma16<T>(f16_a_rows(s_k, 32 * kh + r, hh, 1), qb[1], sa);
+    f32x16 dp = mfma16<T>(f16_a_rows(s_v, 32 * kh + r, hh, 0), gb[0], mfma16_zero());
+    dp = mfma16<T>(f16_a_rows(s_v, 32 * kh + r, hh, 1), gb[1], dp);
     const long key0 = j0 + 32 * kh;
     float ds[16];
 #pragma unroll
@@ -269,8 +274,8 @@ __global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict_
       const float p = key0 + f16_row(i, hh) < n ? fa_exp(sa[i] * FA_SCALE - ls) : 0.f;
       ds[i] = p * (dp[i] - dl);
     }
-    dq = mfma16(f16_a_cols(s_kt, r, hh, kh, 0), f16_b_acc(ds, 0), dq);
-    dq = mfma16(f16_a_cols(s_kt, r, hh, kh, 1), f16_b_acc(ds, 1), dq);
+    dq = mfma16<T>(f16_a_cols(s_kt, r, hh, kh, 0), f16_b_acc<T>(ds, 0), dq);
+    dq = mfma16<T>(f16_a_cols(s_kt, r, hh, kh, 1), f16_b_acc<T>(ds, 1), dq);
   }
   float ov[16];
   if (kh == 1) {
@@ -291,6 +296,7 @@ __global__ __launch_bounds__(FA_BS) void fa16_dq_kernel(const float* __restrict_
 }
 
 // ================================================================================================ backward: columns (dk, dv)
+template <typename T>
 __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           float* __restrict__ dqkv, long n, int heads, int ld3, int ldo) {
@@ -310,8 +316,8 @@ __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict
   uint4 kb[2], vb[2];
   {
     float x[16];
-    f16_b_row(base + hidden + (size_t)ki * ld3, hh, kb, x);
-    f16_b_row(base + 2 * hidden + (size_t)ki * ld3, hh, vb, x);
+    f16_b_row<T>(base + hidden + (size_t)ki * ld3, hh, kb, x);
+    f16_b_row<T>(base + 2 * hidden + (size_t)ki * ld3, hh, vb, x);
   }
   f32x16 dk = mfma16_zero(), dv = mfma16_zero();
   F16Raw rq = f16_fetch(base, 0, n, ld3, tid), rg = f16_fetch(gbase, 0, n, ldo, tid);
@@ -322,10 +328,10 @@ __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict
   }
   for (long i0 = 0; i0 < n; i0 += FA_T) {                   // (uniform: the barriers and the MFMAs)
     __syncthreads();
-    f16_put_rows(s_q, rq, tid);
-    f16_put_cols(s_qt, rq, tid);
-    f16_put_rows(s_g, rg, tid);
-    f16_put_cols(s_gt, rg, tid);
+    f16_put_rows<T>(s_q, rq, tid);
+    f16_put_cols<T>(s_qt, rq, tid);
+    f16_put_rows<T>(s_g, rg, tid);
+    f16_put_cols<T>(s_gt, rg, tid);
     if (tid < FA_T) {
       s_ls[tid] = rls;
       s_dl[tid] = rdl;
@@ -340,10 +346,10 @@ __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict
         rdl = ok ? delta[stat + i0 + FA_T + tid] : 0.f;
       }
     }
-    f32x16 sa = mfma16(f16_a_rows(s_q, 32 * qh + r, hh, 0), kb[0], mfma16_zero());
-    sa = mfma16(f16_a_rows(s_q, 32 * qh + r, hh, 1), kb[1], sa);
-    f32x16 dp = mfma16(f16_a_rows(s_g, 32 * qh + r, hh, 0), vb[0], mfma16_zero());
-    dp = mfma16(f16_a_rows(s_g, 32 * qh + r, hh, 1), vb[1], dp);
+    f32x16 sa = mfma16<T>(f16_a_rows(s_q, 32 * qh + r, hh, 0), kb[0], mfma16_zero());
+    sa = mfma16<T>(f16_a_rows(s_q, 32 * qh + r, hh, 1), kb[1], sa);
+    f32x16 dp = mfma16<T>(f16_a_rows(s_g, 32 * qh + r, hh, 0), vb[0], mfma16_zero());
+    dp = mfma16<T>(f16_a_rows(s_g, 32 * qh + r, hh, 1), vb[1], dp);
     const long qq0 = i0 + 32 * qh;
     float p[16], ds[16];
 #pragma unroll
@@ -358,10 +364,10 @@ __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict
         ds[i] = p[i] * (dp[i] - dlv[j]);
       }
     }
-    dv = mfma16(f16_a_cols(s_gt, r, hh, qh, 0), f16_b_acc(p, 0), dv);
-    dv = mfma16(f16_a_cols(s_gt, r, hh, qh, 1), f16_b_acc(p, 1), dv);
-    dk = mfma16(f16_a_cols(s_qt, r, hh, qh, 0), f16_b_acc(ds, 0), dk);
-    dk = mfma16(f16_a_cols(s_qt, r, hh, qh, 1), f16_b_acc(ds, 1), dk);
+    dv = mfma16<T>(f16_a_cols(s_gt, r, hh, qh, 0), f16_b_acc<T>(p, 0), dv);
+    dv = mfma16<T>(f16_a_cols(s_gt, r, hh, qh, 1), f16_b_acc<T>(p, 1), dv);
+    dk = mfma16<T>(f16_a_cols(s_qt, r, hh, qh, 0), f16_b_acc<T>(ds, 0), dk);
+    dk = mfma16<T>(f16_a_cols(s_qt, r, hh, qh, 1), f16_b_acc<T>(ds, 1), dk);
   }
   float xk[16], xv[16];
   if (qh == 1) {
@@ -392,44 +398,58 @@ __global__ __launch_bounds__(FA_BS) void fa16_dkv_kernel(const float* __restrict
 }
 
 // ================================================================================================ host side
-}  // namespace
-
-extern "C" int ld_dn_fa_forward16(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo,
-                                  void* stream) {
+// One body per entry point for both formats; `fn` is the entry point's name in the messages.
+template <typename T>
+int fa16_forward(const char* fn, const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3, int ldo,
+                 void* stream) {
   LD_REQUIRE(fa_shape_ok(B, H, W, heads) && fa_strides_ok(heads, ld3, ldo),
-             "ld_dn_fa_forward16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of "
-             "4)", B, H, W, heads, ld3, ldo);
-  LD_REQUIRE(qkv && out, "ld_dn_fa_forward16: null pointer");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)", fn, B, H, W,
+             heads, ld3, ldo);
+  LD_REQUIRE(qkv && out, "%s: null pointer", fn);
   LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(out) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
-             "ld_dn_fa_forward16: a pointer is not aligned (qkv, out: 16 bytes)");
+             "%s: a pointer is not aligned (qkv, out: 16 bytes)", fn);
   const int slots = fa_slots(heads, ldo, heads * FA_D);
-  LD_REQUIRE(slots <= 65535, "ld_dn_fa_forward16: ldo %d", ldo);
+  LD_REQUIRE(slots <= 65535, "%s: ldo %d", fn, ldo);
   const long n = (long)H * W;
-  LD_LAUNCH(fa16_forward_kernel, dim3((unsigned)((n + FA_T - 1) / FA_T), (unsigned)slots, (unsigned)B), dim3(FA_BS), 0,
+  LD_LAUNCH(fa16_forward_kernel<T>, dim3((unsigned)((n + FA_T - 1) / FA_T), (unsigned)slots, (unsigned)B), dim3(FA_BS), 0,
             dn_st(stream), qkv, out, lse, n, heads, ld3, ldo);
-  LD_LAUNCH_CHECK("dn_fa_forward16");
+  LD_LAUNCH_CHECK(fn + 3);                                  // (without "ld_")
   return LD_OK;
 }
 
-extern "C" int ld_dn_fa_backward16(const float* qkv, const float* out, const float* dout, const float* lse, void* work,
-                                   float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
+template <typename T>
+int fa16_backward(const char* fn, const float* qkv, const float* out, const float* dout, const float* lse, void* work, float* dqkv,
+                  int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
   LD_REQUIRE(fa_shape_ok(B, H, W, heads) && fa_strides_ok(heads, ld3, ldo),
-             "ld_dn_fa_backward16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples "
-             "of 4)", B, H, W, heads, ld3, ldo);
-  LD_REQUIRE(qkv && out && dout && lse && work && dqkv, "ld_dn_fa_backward16: null pointer");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)", fn, B, H, W,
+             heads, ld3, ldo);
+  LD_REQUIRE(qkv && out && dout && lse && work && dqkv, "%s: null pointer", fn);
   LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(out) && dn_aligned16(dout) && dn_aligned16(dqkv) &&
                  (reinterpret_cast<uintptr_t>(lse) & 3) == 0 && (reinterpret_cast<uintptr_t>(work) & 3) == 0,
-             "ld_dn_fa_backward16: a pointer is not aligned (qkv, out, dout, dqkv: 16 bytes)");
+             "%s: a pointer is not aligned (qkv, out, dout, dqkv: 16 bytes)", fn);
   const int slots = fa_slots(heads, ld3, 3 * heads * FA_D);
-  LD_REQUIRE(slots <= 65535, "ld_dn_fa_backward16: ld3 %d", ld3);
+  LD_REQUIRE(slots <= 65535, "%s: ld3 %d", fn, ld3);
   const long n = (long)H * W;
   const unsigned tiles = (unsigned)((n + FA_T - 1) / FA_T);
   hipStream_t st = dn_st(stream);
   float* delta = static_cast<float*>(work);                // [B, heads, n]: ld_dn_fa_work_bytes
-  LD_LAUNCH(fa16_dq_kernel, dim3(tiles, (unsigned)slots, (unsigned)B), dim3(FA_BS), 0, st, qkv, out, dout, lse, delta, dqkv, n,
+  LD_LAUNCH(fa16_dq_kernel<T>, dim3(tiles, (unsigned)slots, (unsigned)B), dim3(FA_BS), 0, st, qkv, out, dout, lse, delta, dqkv, n,
             heads, ld3, ldo);
-  LD_LAUNCH(fa16_dkv_kernel, dim3(tiles, (unsigned)heads, (unsigned)B), dim3(FA_BS), 0, st, qkv, dout, lse, (const float*)delta,
+  LD_LAUNCH(fa16_dkv_kernel<T>, dim3(tiles, (unsigned)heads, (unsigned)B), dim3(FA_BS), 0, st, qkv, dout, lse, (const float*)delta,
             dqkv, n, heads, ld3, ldo);
-  LD_LAUNCH_CHECK("dn_fa_backward16");
+  LD_LAUNCH_CHECK(fn + 3);
   return LD_OK;
 }
+}  // namespace
+
+#define FA16_ENTRY(suffix, T)                                                                                                  \
+  extern "C" int ld_dn_fa_forward##suffix(const float* qkv, float* out, float* lse, int B, int H, int W, int heads, int ld3,   \
+                                          int ldo, void* stream) {                                                             \
+    return fa16_forward<T>("ld_dn_fa_forward" #suffix, qkv, out, lse, B, H, W, heads, ld3, ldo, stream);                       \
+  }                                                                                                                            \
+  extern "C" int ld_dn_fa_backward##suffix(const float* qkv, const float* out, const float* dout, const float* lse, void* work, \
+                                           float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream) {       \
+    return fa16_backward<T>("ld_dn_fa_backward" #suffix, qkv, out, dout, lse, work, dqkv, B, H, W, heads, ld3, ldo, stream);    \
+  }
+FA16_ENTRY(16, bf16)
+FA16_ENTRY(_f16, f16)

@@ -5,6 +5,11 @@
 // fp64 part format in `work` and the two merge kernels are the fp32 path's (la_common.hip.h).  No floating-point atomics,
 // every sum in one order, nothing allocates.
 //
+// Every kernel is a template on the operand format T: <bf16> is the above (the ...16 entry points), <f16> the same code with
+// pack2<f16> (v_cvt_pk_f16_f32: round-to-nearest-even, no saturation, beyond 65504 is inf) and v_mfma_f32_32x32x16_f16 (the
+// ..._f16 entry points; amp_attn = "fp16").  Images, swizzle, tiles, barriers, the order of every addition and the fp32
+// formulas are the same; the one difference is the dv product of la16_apply_kernel, described there.
+//
 // The MFMA and its lane map (lane l: r = l & 31, hh = l >> 5) are mfma16.hip.h's.
 //
 //   * The two reductions over pixels (context; dctx of the backward): D[d][e] = sum_n P[n][d] V[n][e], K is the pixel axis.
@@ -42,7 +47,7 @@ __device__ __forceinline__ bf16x8 l16_frag(unsigned a, unsigned b, unsigned c, u
 // ================================================================================================ reductions
 // part (b, head, s) of pixels [s ppp, (s + 1) ppp).  CTX: (m, Z, ctx Z) with P = exp(k - m_part), V = v; otherwise
 // sum of softmax_d(q)[d] dO[e].
-template <bool CTX>
+template <typename T, bool CTX>
 __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                             double* __restrict__ work, long HW, int heads, int ld3, int ldo,
                                                             long ppp, int S) {
@@ -109,8 +114,8 @@ __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int at = mfma16_off(4 * l + i, rr >> 2) + 4 * (rr & 3);
-      *reinterpret_cast<unsigned*>(img + at) = pack_bf16x2(pv[0][i], pv[1][i]);
-      *reinterpret_cast<unsigned*>(img + L16_IMG + at) = pack_bf16x2(vv[0][i], vv[1][i]);
+      *reinterpret_cast<unsigned*>(img + at) = pack2<T>(pv[0][i], pv[1][i]);
+      *reinterpret_cast<unsigned*>(img + L16_IMG + at) = pack2<T>(vv[0][i], vv[1][i]);
     }
     if (t0 + LA_TP < p1) {                                // the next tile's requests fly over the barrier and the MFMA
 #pragma unroll
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(LA_BS) void la16_reduce_kernel(const float* __restr
     {                                                     // K-step `wave` of the tile: pixels 16 wave + 8 hh .. + 7
       const int at = mfma16_off(r, 2 * wave + hh);
       const uint4 a = *reinterpret_cast<const uint4*>(img + at), bb = *reinterpret_cast<const uint4*>(img + L16_IMG + at);
-      acc = mfma16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), acc);
+      acc = mfma16<T>(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), acc);
     }
     if ((it & (L16_RUN - 1)) == L16_RUN - 1) {            // the end of a run: fp32 -> fp64
 #pragma unroll
@@ -185,21 +190,31 @@ struct L16Vec {
   float v[4][4];
 };
 // B operand of K-step s: channels g = 2 s, 2 s + 1
-__device__ __forceinline__ bf16x8 l16_b(const L16Vec& x, int s) {
-  return l16_frag(pack_bf16x2(x.v[2 * s][0], x.v[2 * s][1]), pack_bf16x2(x.v[2 * s][2], x.v[2 * s][3]),
-                  pack_bf16x2(x.v[2 * s + 1][0], x.v[2 * s + 1][1]), pack_bf16x2(x.v[2 * s + 1][2], x.v[2 * s + 1][3]));
+template <typename T> __device__ __forceinline__ bf16x8 l16_b(const L16Vec& x, int s) {
+  return l16_frag(pack2<T>(x.v[2 * s][0], x.v[2 * s][1]), pack2<T>(x.v[2 * s][2], x.v[2 * s][3]),
+                  pack2<T>(x.v[2 * s + 1][0], x.v[2 * s + 1][1]), pack2<T>(x.v[2 * s + 1][2], x.v[2 * s + 1][3]));
 }
 // A operand M[r][k] of K-step s from a row-major 32 x 32 fp32 matrix: the row's channels 4 hh + 8 g .. + 3, g = 2 s, 2 s + 1
-__device__ __forceinline__ bf16x8 l16_a_rows(const float* M, int r, int hh, int s) {
+template <typename T> __device__ __forceinline__ bf16x8 l16_a_rows(const float* M, int r, int hh, int s) {
   const float4 x = ld4(M + r * LA_D + 16 * s + 4 * hh), y = ld4(M + r * LA_D + 16 * s + 8 + 4 * hh);
-  return l16_frag(pack_bf16x2(x.x, x.y), pack_bf16x2(x.z, x.w), pack_bf16x2(y.x, y.y), pack_bf16x2(y.z, y.w));
+  return l16_frag(pack2<T>(x.x, x.y), pack2<T>(x.z, x.w), pack2<T>(y.x, y.y), pack2<T>(y.z, y.w));
 }
 // A operand M^T[r][k] of K-step s: column r of the rows 4 hh + 8 g + i
-__device__ __forceinline__ bf16x8 l16_a_cols(const float* M, int r, int hh, int s) {
+template <typename T> __device__ __forceinline__ bf16x8 l16_a_cols(const float* M, int r, int hh, int s) {
   float x[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = M[(8 * (2 * s + (j >> 2)) + 4 * hh + (j & 3)) * LA_D + r];
-  return l16_frag(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]), pack_bf16x2(x[6], x[7]));
+  return l16_frag(pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3]), pack2<T>(x[4], x[5]), pack2<T>(x[6], x[7]));
+}
+// ... with row d = 8 g + 4 hh + i of M scaled by sc[d] before it is rounded (the fp16 dv product of la16_apply_kernel)
+template <typename T> __device__ __forceinline__ bf16x8 l16_a_cols_scaled(const float* M, const float* sc, int r, int hh, int s) {
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int d = 8 * (2 * s + (j >> 2)) + 4 * hh + (j & 3);
+    x[j] = M[d * LA_D + r] * sc[d];
+  }
+  return l16_frag(pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3]), pack2<T>(x[4], x[5]), pack2<T>(x[6], x[7]));
 }
 // softmax over a head's 32 channels: 16 here, 16 in lane l ^ 32; both lanes get the same maximum and sum
 __device__ __forceinline__ L16Vec l16_softmax(const L16Vec& q) {
@@ -284,6 +299,7 @@ __device__ __forceinline__ void l16_flush(const float* tile, float* p, int ld, l
 }
 
 // out[n][head 32 + e] = 32^-0.5 sum_d ctx[d][e] softmax_d(q)[d]; workgroup columns >= heads zero the padding
+template <typename T>
 __global__ __launch_bounds__(LA_BS) void la16_out_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                          float* __restrict__ out, long HW, int heads, int ld3, int ldo, long run) {
   __shared__ __attribute__((aligned(16))) float sT[LA_BS / 64][L16_TILE];
@@ -303,7 +319,7 @@ __global__ __launch_bounds__(LA_BS) void la16_out_kernel(const float* __restrict
   if (base >= p1) return;
   L16Raw raw = l16_fetch(Q, ld3, base, p1, lane);         // (in flight while the A operands load)
   const float* C = ctx + (size_t)(b * heads + h) * LA_D * LA_D;
-  const bf16x8 a0 = l16_a_cols(C, r, hh, 0), a1 = l16_a_cols(C, r, hh, 1);            // ctx^T [e][d]
+  const bf16x8 a0 = l16_a_cols<T>(C, r, hh, 0), a1 = l16_a_cols<T>(C, r, hh, 1);            // ctx^T [e][d]
   const float scale = (float)LA_SCALE;
   for (; base < p1; base += 128) {                        // (uniform in the wave: the shuffles and the MFMA)
     l16_put(tile, raw, lane);
@@ -311,8 +327,8 @@ __global__ __launch_bounds__(LA_BS) void la16_out_kernel(const float* __restrict
     const L16Vec qv = l16_take(tile, r, hh);
     if (base + 128 < p1) raw = l16_fetch(Q, ld3, base + 128, p1, lane);
     const L16Vec p = l16_softmax(qv);
-    f32x16 o = mfma16(a0, l16_b(p, 0), mfma16_zero());
-    o = mfma16(a1, l16_b(p, 1), o);
+    f32x16 o = mfma16<T>(a0, l16_b<T>(p, 0), mfma16_zero());
+    o = mfma16<T>(a1, l16_b<T>(p, 1), o);
     L16Vec ov;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -329,6 +345,11 @@ __global__ __launch_bounds__(LA_BS) void la16_out_kernel(const float* __restrict
 // dqkv of one (pixel, head) from q, k, v, dO and the head's ctx, (m, Z), dctx, rk; columns >= heads zero the padding.
 // s = ctx dO, tk = dctx v and dv = dctx^T ks on the matrix cores; ks, p, dot and the three output formulas in fp32 with
 // the unrounded p and ks, as la_apply_kernel writes them.  Two tiles per wave: (dO, q), then (k, v), then (dq, dk), then dv.
+// The dv product differs by format.  bf16 rounds ks = exp(k - m) (1 / Z) as the operand.  ks is about 1 / n, which from
+// 128 x 128 pixels on lies in fp16's subnormals, so fp16 moves the division to the other side:
+//   dv[e][n] = sum_d fp16(dctx[d][e] iz[d]) fp16(exp(k[d][n] - m[d])),
+// a second pair of dctx^T fragments scaled per contraction row, built once per workgroup, against an operand in (0, 1].
+template <typename T>
 __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                            const float* __restrict__ ctx, const float* __restrict__ kstat,
                                                            const float* __restrict__ dctx, const float* __restrict__ rk,
@@ -360,9 +381,14 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
     rv = l16_fetch(Q + 2 * hidden, ld3, base, p1, lane);
   }
   const float *C = ctx + bh * LA_D * LA_D, *D = dctx + bh * LA_D * LA_D;
-  const bf16x8 c0 = l16_a_rows(C, r, hh, 0), c1 = l16_a_rows(C, r, hh, 1);            // ctx  [d][e]
-  const bf16x8 d0 = l16_a_rows(D, r, hh, 0), d1 = l16_a_rows(D, r, hh, 1);            // dctx [d][e]
-  const bf16x8 e0 = l16_a_cols(D, r, hh, 0), e1 = l16_a_cols(D, r, hh, 1);            // dctx^T [e][d]
+  const bf16x8 c0 = l16_a_rows<T>(C, r, hh, 0), c1 = l16_a_rows<T>(C, r, hh, 1);            // ctx  [d][e]
+  const bf16x8 d0 = l16_a_rows<T>(D, r, hh, 0), d1 = l16_a_rows<T>(D, r, hh, 1);            // dctx [d][e]
+  constexpr bool FOLD = std::is_same<T, f16>::value;      // dv: 1 / Z on the dctx^T side (above)
+  bf16x8 e0, e1;                                          // dctx^T [e][d]
+  if (!FOLD) {
+    e0 = l16_a_cols<T>(D, r, hh, 0);
+    e1 = l16_a_cols<T>(D, r, hh, 1);
+  }
   if (t < LA_D) {
     sK[t] = kstat[(bh * LA_D + t) * 2];
     sK[LA_D + t] = 1.0f / kstat[(bh * LA_D + t) * 2 + 1];
@@ -370,6 +396,10 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
   }
   __syncthreads();
   if (!any) return;
+  if (FOLD) {                                             // dctx^T [e][d] iz[d]
+    e0 = l16_a_cols_scaled<T>(D, sK + LA_D, r, hh, 0);
+    e1 = l16_a_cols_scaled<T>(D, sK + LA_D, r, hh, 1);
+  }
   const float scale = (float)LA_SCALE;
   for (; base < p1; base += 128) {                        // (uniform in the wave: the shuffles and the MFMAs)
     l16_put(t0, rdo, lane);
@@ -387,22 +417,26 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
       rk4 = l16_fetch(Q + hidden, ld3, base + 128, p1, lane);
       rv = l16_fetch(Q + 2 * hidden, ld3, base + 128, p1, lane);
     }
-    f32x16 s = mfma16(c0, l16_b(dov, 0), mfma16_zero());
-    s = mfma16(c1, l16_b(dov, 1), s);
-    f32x16 tk = mfma16(d0, l16_b(vv, 0), mfma16_zero());
-    tk = mfma16(d1, l16_b(vv, 1), tk);
-    L16Vec ks;
+    f32x16 s = mfma16<T>(c0, l16_b<T>(dov, 0), mfma16_zero());
+    s = mfma16<T>(c1, l16_b<T>(dov, 1), s);
+    f32x16 tk = mfma16<T>(d0, l16_b<T>(vv, 0), mfma16_zero());
+    tk = mfma16<T>(d1, l16_b<T>(vv, 1), tk);
+    L16Vec ks, pk;                                        // pk = exp(k - m), ks = pk / Z
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 mk = *reinterpret_cast<const float4*>(sK + 8 * g + 4 * hh);
       const float4 iz = *reinterpret_cast<const float4*>(sK + LA_D + 8 * g + 4 * hh);
-      ks.v[g][0] = la_exp(kv.v[g][0] - mk.x) * iz.x;
-      ks.v[g][1] = la_exp(kv.v[g][1] - mk.y) * iz.y;
-      ks.v[g][2] = la_exp(kv.v[g][2] - mk.z) * iz.z;
-      ks.v[g][3] = la_exp(kv.v[g][3] - mk.w) * iz.w;
+      pk.v[g][0] = la_exp(kv.v[g][0] - mk.x);
+      pk.v[g][1] = la_exp(kv.v[g][1] - mk.y);
+      pk.v[g][2] = la_exp(kv.v[g][2] - mk.z);
+      pk.v[g][3] = la_exp(kv.v[g][3] - mk.w);
+      ks.v[g][0] = pk.v[g][0] * iz.x;
+      ks.v[g][1] = pk.v[g][1] * iz.y;
+      ks.v[g][2] = pk.v[g][2] * iz.z;
+      ks.v[g][3] = pk.v[g][3] * iz.w;
     }
-    f32x16 dv = mfma16(e0, l16_b(ks, 0), mfma16_zero());
-    dv = mfma16(e1, l16_b(ks, 1), dv);
+    f32x16 dv = mfma16<T>(e0, l16_b<T>(FOLD ? pk : ks, 0), mfma16_zero());
+    dv = mfma16<T>(e1, l16_b<T>(FOLD ? pk : ks, 1), dv);
     const L16Vec p = l16_softmax(qv);
     float dot = 0.0f;
 #pragma unroll
@@ -434,82 +468,112 @@ __global__ __launch_bounds__(LA_BS) void la16_apply_kernel(const float* __restri
     l16_wave_sync();
   }
 }
-}  // namespace
 
 // ================================================================================================ host side
-extern "C" int ld_dn_la_context16(const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W, int heads,
-                                  int ld3, void* stream) {
+// One body per pass for both formats; `fn` is the entry point's name in the messages.
+template <typename T>
+int la16_context(const char* fn, const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W, int heads, int ld3,
+                 void* stream) {
   LD_REQUIRE(la_shape_ok(B, H, W, heads) && la_strides_ok(heads, ld3, heads * LA_D),
-             "ld_dn_la_context16: B=%d H=%d W=%d heads=%d ld3=%d (heads >= 1, ld3 >= 96 heads a multiple of 4)", B, H, W, heads, ld3);
-  LD_REQUIRE(qkv && work && ctx && kstat, "ld_dn_la_context16: null pointer");
-  LD_REQUIRE(dn_aligned16(qkv), "ld_dn_la_context16: qkv is not 16-byte aligned");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d (heads >= 1, ld3 >= 96 heads a multiple of 4)", fn, B, H, W, heads, ld3);
+  LD_REQUIRE(qkv && work && ctx && kstat, "%s: null pointer", fn);
+  LD_REQUIRE(dn_aligned16(qkv), "%s: qkv is not 16-byte aligned", fn);
   const long HW = (long)H * W;
   hipStream_t st = dn_st(stream);
   long ppp;
   int S;
   la_parts(B, heads, HW, ppp, S);
-  LD_LAUNCH(la16_reduce_kernel<true>, dim3((unsigned)S, (unsigned)heads, (unsigned)B), dim3(LA_BS), 0, st, qkv,
-            (const float*)nullptr, work, HW, heads, ld3, 0, ppp, S);
+  const auto reduce = la16_reduce_kernel<T, true>;
+  LD_LAUNCH(reduce, dim3((unsigned)S, (unsigned)heads, (unsigned)B), dim3(LA_BS), 0, st, qkv, (const float*)nullptr, work, HW,
+            heads, ld3, 0, ppp, S);
   LD_LAUNCH(la_context_merge_kernel, dim3((unsigned)(B * heads)), dim3(256), 0, st, (const double*)work, ctx, kstat, S);
-  LD_LAUNCH_CHECK("dn_la_context16");
+  LD_LAUNCH_CHECK(fn + 3);                                // (without "ld_")
   return LD_OK;
 }
 
-extern "C" int ld_dn_la_out16(const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3, int ldo,
-                              void* stream) {
+template <typename T>
+int la16_out(const char* fn, const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3, int ldo,
+             void* stream) {
   LD_REQUIRE(la_shape_ok(B, H, W, heads) && la_strides_ok(heads, ld3, ldo),
-             "ld_dn_la_out16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)",
-             B, H, W, heads, ld3, ldo);
-  LD_REQUIRE(qkv && ctx && out, "ld_dn_la_out16: null pointer");
-  LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(ctx) && dn_aligned16(out), "ld_dn_la_out16: a pointer is not 16-byte aligned");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)", fn, B, H, W,
+             heads, ld3, ldo);
+  LD_REQUIRE(qkv && ctx && out, "%s: null pointer", fn);
+  LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(ctx) && dn_aligned16(out), "%s: a pointer is not 16-byte aligned", fn);
   const long HW = (long)H * W;
   const int slots = heads + (ldo - heads * LA_D + LA_D - 1) / LA_D;
-  LD_REQUIRE(slots <= 65535, "ld_dn_la_out16: ldo %d", ldo);
+  LD_REQUIRE(slots <= 65535, "%s: ldo %d", fn, ldo);
   long run;
   unsigned nrun;
   l16_runs(B, slots, HW, run, nrun);
-  LD_LAUNCH(la16_out_kernel, dim3(nrun, (unsigned)slots, (unsigned)B), dim3(LA_BS), 0, dn_st(stream), qkv, ctx, out, HW, heads,
+  LD_LAUNCH(la16_out_kernel<T>, dim3(nrun, (unsigned)slots, (unsigned)B), dim3(LA_BS), 0, dn_st(stream), qkv, ctx, out, HW, heads,
             ld3, ldo, run);
-  LD_LAUNCH_CHECK("dn_la_out16");
+  LD_LAUNCH_CHECK(fn + 3);
   return LD_OK;
 }
 
-extern "C" int ld_dn_la_backward_reduce16(const float* qkv, const float* dout, const float* ctx, double* work, float* dctx,
-                                          float* rk, int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
+template <typename T>
+int la16_backward_reduce(const char* fn, const float* qkv, const float* dout, const float* ctx, double* work, float* dctx, float* rk,
+                         int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
   LD_REQUIRE(la_shape_ok(B, H, W, heads) && la_strides_ok(heads, ld3, ldo),
-             "ld_dn_la_backward_reduce16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, "
-             "multiples of 4)", B, H, W, heads, ld3, ldo);
-  LD_REQUIRE(qkv && dout && ctx && work && dctx && rk, "ld_dn_la_backward_reduce16: null pointer");
-  LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(dout), "ld_dn_la_backward_reduce16: a pointer is not 16-byte aligned");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)", fn, B, H, W,
+             heads, ld3, ldo);
+  LD_REQUIRE(qkv && dout && ctx && work && dctx && rk, "%s: null pointer", fn);
+  LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(dout), "%s: a pointer is not 16-byte aligned", fn);
   const long HW = (long)H * W;
   hipStream_t st = dn_st(stream);
   long ppp;
   int S;
   la_parts(B, heads, HW, ppp, S);
-  LD_LAUNCH(la16_reduce_kernel<false>, dim3((unsigned)S, (unsigned)heads, (unsigned)B), dim3(LA_BS), 0, st, qkv, dout, work, HW,
-            heads, ld3, ldo, ppp, S);
+  const auto reduce = la16_reduce_kernel<T, false>;
+  LD_LAUNCH(reduce, dim3((unsigned)S, (unsigned)heads, (unsigned)B), dim3(LA_BS), 0, st, qkv, dout, work, HW, heads, ld3, ldo, ppp,
+            S);
   LD_LAUNCH(la_reduce_merge_kernel, dim3((unsigned)(B * heads)), dim3(256), 0, st, (const double*)work, ctx, dctx, rk, S);
-  LD_LAUNCH_CHECK("dn_la_backward_reduce16");
+  LD_LAUNCH_CHECK(fn + 3);
   return LD_OK;
 }
 
-extern "C" int ld_dn_la_backward_apply16(const float* qkv, const float* dout, const float* ctx, const float* kstat,
-                                         const float* dctx, const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3,
-                                         int ldo, void* stream) {
+template <typename T>
+int la16_backward_apply(const char* fn, const float* qkv, const float* dout, const float* ctx, const float* kstat, const float* dctx,
+                        const float* rk, float* dqkv, int B, int H, int W, int heads, int ld3, int ldo, void* stream) {
   LD_REQUIRE(la_shape_ok(B, H, W, heads) && la_strides_ok(heads, ld3, ldo),
-             "ld_dn_la_backward_apply16: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, "
-             "multiples of 4)", B, H, W, heads, ld3, ldo);
-  LD_REQUIRE(qkv && dout && ctx && kstat && dctx && rk && dqkv, "ld_dn_la_backward_apply16: null pointer");
+             "%s: B=%d H=%d W=%d heads=%d ld3=%d ldo=%d (heads >= 1, ld3 >= 96 heads, ldo >= 32 heads, multiples of 4)", fn, B, H, W,
+             heads, ld3, ldo);
+  LD_REQUIRE(qkv && dout && ctx && kstat && dctx && rk && dqkv, "%s: null pointer", fn);
   LD_REQUIRE(dn_aligned16(qkv) && dn_aligned16(dout) && dn_aligned16(ctx) && dn_aligned16(dctx) && dn_aligned16(dqkv),
-             "ld_dn_la_backward_apply16: a pointer is not 16-byte aligned");
+             "%s: a pointer is not 16-byte aligned", fn);
   const long HW = (long)H * W;
   const int slots = heads + (ld3 - 3 * heads * LA_D + LA_D - 1) / LA_D;
-  LD_REQUIRE(slots <= 65535, "ld_dn_la_backward_apply16: ld3 %d", ld3);
+  LD_REQUIRE(slots <= 65535, "%s: ld3 %d", fn, ld3);
   long run;
   unsigned nrun;
   l16_runs(B, slots, HW, run, nrun);
-  LD_LAUNCH(la16_apply_kernel, dim3(nrun, (unsigned)slots, (unsigned)B), dim3(LA_BS), 0, dn_st(stream), qkv, dout, ctx, kstat,
+  LD_LAUNCH(la16_apply_kernel<T>, dim3(nrun, (unsigned)slots, (unsigned)B), dim3(LA_BS), 0, dn_st(stream), qkv, dout, ctx, kstat,
             dctx, rk, dqkv, HW, heads, ld3, ldo, run);
-  LD_LAUNCH_CHECK("dn_la_backward_apply16");
+  LD_LAUNCH_CHECK(fn + 3);
   return LD_OK;
 }
+}  // namespace
+
+#define LA16_ENTRY(suffix, T)                                                                                                     \
+  extern "C" int ld_dn_la_context##suffix(const float* qkv, double* work, float* ctx, float* kstat, int B, int H, int W,         \
+                                          int heads, int ld3, void* stream) {                                                    \
+    return la16_context<T>("ld_dn_la_context" #suffix, qkv, work, ctx, kstat, B, H, W, heads, ld3, stream);                      \
+  }                                                                                                                               \
+  extern "C" int ld_dn_la_out##suffix(const float* qkv, const float* ctx, float* out, int B, int H, int W, int heads, int ld3,   \
+                                      int ldo, void* stream) {                                                                   \
+    return la16_out<T>("ld_dn_la_out" #suffix, qkv, ctx, out, B, H, W, heads, ld3, ldo, stream);                                 \
+  }                                                                                                                               \
+  extern "C" int ld_dn_la_backward_reduce##suffix(const float* qkv, const float* dout, const float* ctx, double* work,           \
+                                                  float* dctx, float* rk, int B, int H, int W, int heads, int ld3, int ldo,      \
+                                                  void* stream) {                                                                \
+    return la16_backward_reduce<T>("ld_dn_la_backward_reduce" #suffix, qkv, dout, ctx, work, dctx, rk, B, H, W, heads, ld3, ldo, \
+                                   stream);                                                                                      \
+  }                                                                                                                               \
+  extern "C" int ld_dn_la_backward_apply##suffix(const float* qkv, const float* dout, const float* ctx, const float* kstat,      \
+                                                 const float* dctx, const float* rk, float* dqkv, int B, int H, int W,           \
+                                                 int heads, int ld3, int ldo, void* stream) {                                    \
+    return la16_backward_apply<T>("ld_dn_la_backward_apply" #suffix, qkv, dout, ctx, kstat, dctx, rk, dqkv, B, H, W, heads, ld3, \
+                                  ldo, stream);                                                                                  \
+  }
+LA16_ENTRY(16, bf16)
+LA16_ENTRY(_f16, f16)

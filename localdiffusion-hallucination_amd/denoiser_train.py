@@ -56,7 +56,8 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
-from .trainable import SWITCHES, check_amp_precision, check_storage_precision, check_switch, stream
+from .trainable import (AMP_ATTN_TYPES, SWITCHES, check_amp_attn_precision, check_amp_precision, check_storage_precision, check_switch,
+                        stream)
 from .unet_grad import TrainableUnet
 
 # the parameters the reference's forward never uses (ddpm.py:437: conv_fusion is called without a time embedding)
@@ -144,6 +145,18 @@ def check_amp(amp, mixed_precision_type, conv_precision, scaler_kwargs):
     conv_precision = "fp32" if conv_precision is None else conv_precision
     check_amp_precision("DenoiserTrainer", "fp16", conv_precision)
     return "fp16", conv_precision, check_scaler_kwargs(scaler_kwargs)
+
+
+def check_amp_attn(amp_attn, module_amp, attn_precision, full_attn_precision):
+    """What ``DenoiserTrainer(amp_attn=)`` needs: a value of ``AMP_ATTN_TYPES``; at ``"fp16"`` a loss scaler (``module_amp``
+    ``"fp16"``: ``amp=True`` with ``mixed_precision_type="fp16"``) and neither bf16 attention switch.  Needs no GPU."""
+    check_switch("DenoiserTrainer", "amp_attn", amp_attn, AMP_ATTN_TYPES)
+    if amp_attn == "fp16" and module_amp != "fp16":
+        raise ValueError("DenoiserTrainer: amp_attn 'fp16' needs amp=True with mixed_precision_type 'fp16' (fp16 gradients in "
+                         "the attention cores need the loss scaler, and there is none)")
+    check_amp_attn_precision("DenoiserTrainer", amp_attn, "attn_precision", attn_precision)
+    check_amp_attn_precision("DenoiserTrainer", amp_attn, "full_attn_precision", full_attn_precision)
+    return amp_attn
 
 
 def checkpoint_dict(step, diffusion_sd, online_sd, ema_sd, moments, opt_step, lr, betas, eps, ema_step, initted, scaler=None):
@@ -259,6 +272,14 @@ class DenoiserTrainer:
     type is a ``ValueError``; ``amp=False`` changes nothing at all.  ``scaler_state()`` reads the scaler back;
     ``check_finite()`` does not raise under a scaler (a non-finite norm is a skipped step there).
 
+    ``amp_attn="fp16"`` (default ``"fp32"``; ``trainable.AMP_ATTN_TYPES``) extends ``amp`` to the attention cores: every
+    ``LinearAttention`` and ``Attention`` of the online model runs the passes of its core on the fp16 matrix cores
+    (``TrainableUnet.amp_attn``).  It needs ``amp=True`` with ``mixed_precision_type="fp16"`` -- without the scaler it is a
+    ``ValueError`` -- and is refused together with ``attn_precision="bf16"`` or ``full_attn_precision="bf16"``.  A dO or dctx
+    that overflows fp16 under a large scale is a skipped step and a back-off, like an overflow in a convolution.  The step
+    stays reproducible bit for bit, replicas stay identical, and a checkpoint does not record it; ``amp_attn="fp32"`` spelled
+    out is leaving it out.
+
     ``step`` counts ``apply()`` calls (the reference's ``Trainer.step``, and without a scaler Adam's step count; with one,
     Adam's count lives on the device and does not advance on a skipped step); ``ema_step`` and ``ema_initted`` are
     ``ema_pytorch``'s two buffers and advance at every call."""
@@ -266,7 +287,8 @@ class DenoiserTrainer:
     def __init__(self, diffusion, *, train_lr=1e-4, adam_betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, ema_decay=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0, group=None, comm=None,
                  conv_precision=None, act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32",
-                 full_attn_precision="fp32", amp=False, mixed_precision_type="fp16", scaler_kwargs=None):
+                 full_attn_precision="fp32", amp=False, mixed_precision_type="fp16", scaler_kwargs=None,
+                 amp_attn="fp32"):
         if conv_precision is not None:
             check_switch("DenoiserTrainer", "conv_precision", conv_precision)
         module_amp, conv_precision, scaler = check_amp(amp, mixed_precision_type, conv_precision, scaler_kwargs)
@@ -276,6 +298,7 @@ class DenoiserTrainer:
             check_switch("DenoiserTrainer", switch, switches[switch])
         for switch in ("act_storage", "conv_out_storage"):
             check_storage_precision("DenoiserTrainer", switch, switches[switch], conv_precision)
+        check_amp_attn(amp_attn, module_amp, attn_precision, full_attn_precision)
         if group is not None and comm is not None:
             raise ValueError("DenoiserTrainer: give a torch process group or an LdComm, not both")
         model = getattr(diffusion, "model", None)
@@ -297,8 +320,9 @@ class DenoiserTrainer:
             if not isinstance(v, int) or isinstance(v, bool) or v < lo:
                 raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be an int of at least {lo}")
         # (raises ValueError for what it cannot train)
-        online = TrainableUnet(**online_kwargs(model), **switches, amp=module_amp)
+        online = TrainableUnet(**online_kwargs(model), **switches, amp=module_amp, amp_attn=amp_attn)
         vars(self).update(switches)                   # (what the trainer was built with: self.conv_precision and so on)
+        self.amp_attn = amp_attn
         self.amp, self.mixed_precision_type, self.scaler = bool(amp), mixed_precision_type, scaler     # scaler: settings or None
         dev = diffusion.device
         if dev.type != "cuda":

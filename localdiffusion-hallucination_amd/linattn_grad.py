@@ -10,6 +10,7 @@ and ``ld_dn_colsum`` for ``to_out.0.bias``.  fp32, no host synchronisation in ei
 on an activation, and bit-reproducible results (every sum is added in a fixed order; no floating-point atomics).
 ``LinearAttention.attn_precision = "bf16"`` puts the four passes of the core on the bf16 matrix cores (``csrc/linattn16.hip``:
 operands rounded, fp32 accumulation, the same tensors and the same order of every sum); the default runs the fp32 launches.
+``LinearAttention.amp_attn = "fp16"`` puts them on the fp16 matrix cores (the ``<f16>`` instantiations, ``ld_dn_la_*_f16``).
 
 The layout is ``resblock.py``'s: activations NHWC with a pixel stride of the next multiple of 64 floats, zero in the
 padding; ``to_qkv``'s output is [B, H, W, pad64(3 hidden)] with q at channel 0, k at ``hidden``, v at ``2 hidden`` and a
@@ -95,8 +96,10 @@ class _Run(RMSNormRun):
         return self.work(self.lib.ld_dn_la_work_bytes(self.B, self.mod.heads, self.H, self.W))
 
     def la(self, name):
-        """The core's entry point ``ld_dn_la_<name>`` at the module's ``attn_precision`` (read at every launch)."""
-        return getattr(self.lib, f"ld_dn_la_{name}16" if self.mod.attn_precision == "bf16" else f"ld_dn_la_{name}")
+        """The core's entry point ``ld_dn_la_<name>`` at the module's ``amp_attn`` / ``attn_precision`` (read at every
+        launch; the two are never both set)."""
+        suffix = "_f16" if self.mod.amp_attn == "fp16" else "16" if self.mod.attn_precision == "bf16" else ""
+        return getattr(self.lib, f"ld_dn_la_{name}{suffix}")
 
     # ------------------------------------------------------------------------------------------------ the two halves
     def forward(self, x, keep=True):
@@ -153,11 +156,20 @@ class LinearAttention(TrainableModule):
     backward's reduce and apply -- on the bf16 matrix cores (csrc/linattn16.hip): both operands of every 32 x 32 product of
     a head rounded to bf16, fp32 accumulation, the softmaxes, (m, Z), the merges and everything in memory fp32, every sum in
     a fixed order.  It may change between steps; it is no part of the ``state_dict`` or of the packed weights (the core
-    has none), and it is independent of ``conv_precision``."""
+    has none), and it is independent of ``conv_precision``.
+
+    ``amp_attn = "fp16"`` (default ``"fp32"``, ``trainable.AMP_ATTN_TYPES``) runs the same four passes on the fp16 matrix
+    cores (``ld_dn_la_*_f16``): the bf16 contract with fp16 rounding of the same operands, except that the dv product of the
+    apply pass rounds ``dctx[d][e] / Z[d]`` and ``exp(k - m)`` instead of ``dctx`` and ``exp(k - m) / Z``, which is an fp16
+    subnormal on large maps.  An operand beyond 65504 becomes inf: the mode is meant for ``DenoiserTrainer``'s loss scaler.
+    The same rules as ``attn_precision`` (read at every launch, in no ``state_dict``, independent of ``amp`` and
+    ``conv_precision``), and the two together are refused with ``ValueError`` in either order of assignment."""
 
     Run = _Run
     attn_precision = "fp32"
     ATTN_PRECISIONS = ("fp32", "bf16")
+    amp_attn = "fp32"
+    AMP_ATTN_RIVAL = "attn_precision"
 
     def __init__(self, dim, heads=4, dim_head=32):
         super().__init__()

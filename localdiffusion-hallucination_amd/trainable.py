@@ -38,6 +38,18 @@ large operand becomes inf and a small one underflows, so this mode is meant to r
 ``DenoiserTrainer(amp=True)``.  It is validated on assignment like a switch, handed down by ``TrainableUnet`` like
 ``conv_precision``, no part of a ``state_dict``, and refused together with ``conv_precision = "bf16"`` (two masters for the
 same launches); the storage switches need ``conv_precision = "bf16"`` and so stay out of reach.
+
+``amp_attn`` (``AMP_ATTN_TYPES``: ``"fp32"``, the default, or ``"fp16"``) is ``amp``'s counterpart for the two attention cores and
+is NOT one of ``SWITCHES`` either: at ``"fp16"`` the four passes of a ``LinearAttention``'s core and the three of an
+``Attention``'s run on the fp16 instantiations of ``csrc/linattn16.hip`` / ``csrc/attention16.hip`` (``ld_dn_la_*_f16``,
+``ld_dn_fa_*_f16``): the bf16 kernels' contract with the same operands rounded to fp16 and ``v_mfma_f32_32x32x16_f16``, except
+that the linear core's dv product keeps ``1 / Z`` on the ``dctx`` side (``exp(k - m) / Z`` is an fp16 subnormal from 128 x 128
+pixels on).  It is validated on assignment, read at every launch, no part of a ``state_dict`` or of the packed weights' cache
+key (the cores have none), handed down by ``TrainableUnet`` to both kinds of module, and on a module independent of ``amp`` and
+``conv_precision``.  It is refused together with the bf16 switch of the same launches (``attn_precision = "bf16"`` on
+``LinearAttention``, ``full_attn_precision = "bf16"`` on ``Attention``; either on ``TrainableUnet``).  fp16's range is narrow --
+a large dO or dctx becomes inf, a small p or ds underflows --, so ``DenoiserTrainer`` takes it only with the loss scaler of
+``amp=True``.
 """
 import ctypes as C
 
@@ -100,6 +112,17 @@ def check_amp_precision(name, amp, conv_precision):
     """``amp = "fp16"`` and ``conv_precision = "bf16"`` both route the convolution launches: together they are refused."""
     if amp == "fp16" and conv_precision == "bf16":
         raise ValueError(f"{name}: amp 'fp16' and conv_precision 'bf16' both choose the operand format of the convolutions; "
+                         "set one of them")
+
+
+AMP_ATTN_TYPES = ("fp32", "fp16")      # LinearAttention / Attention / TrainableUnet .amp_attn (the module docstring); outside SWITCHES
+
+
+def check_amp_attn_precision(name, amp_attn, switch, precision):
+    """``amp_attn = "fp16"`` and the bf16 switch of the same attention core both route its launches: together they are
+    refused."""
+    if amp_attn == "fp16" and precision == "bf16":
+        raise ValueError(f"{name}: amp_attn 'fp16' and {switch} 'bf16' both choose the operand format of the attention core; "
                          "set one of them")
 
 
@@ -326,11 +349,18 @@ class TrainableModule(PackedWeights, nn.Module):
     CONV_PRECISIONS = ("fp32", "bf16")
     ACT_STORAGES = ("fp32",)
     CONV_OUT_STORAGES = ("fp32",)
+    AMP_ATTN_RIVAL = None    # an attention module: the bf16 switch of its core, which amp_attn = "fp16" is refused with
     Run = None
 
     def __setattr__(self, name, value):
         if name in SWITCHES and hasattr(type(self), name):
             check_switch(type(self).__name__, name, value, getattr(self, SWITCHES[name]))
+        rival = type(self).AMP_ATTN_RIVAL
+        if rival is not None and name == "amp_attn":
+            check_amp_attn_precision(type(self).__name__, check_switch(type(self).__name__, name, value, AMP_ATTN_TYPES), rival,
+                                     getattr(self, rival))
+        elif rival is not None and name == rival:
+            check_amp_attn_precision(type(self).__name__, self.amp_attn, rival, value)
         if name == "amp":
             check_amp_precision(type(self).__name__, check_switch(type(self).__name__, name, value, AMP_TYPES), self.conv_precision)
         elif name == "conv_precision":

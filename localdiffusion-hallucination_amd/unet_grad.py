@@ -33,7 +33,8 @@ from .condenc import FILTERS, ResUnet
 from .linattn_grad import LinearAttention
 from .resample import Conv2d, Downsample, Upsample
 from .resblock import ResnetBlock
-from .trainable import AMP_TYPES, SWITCHES, TrainableModule, check_amp_precision, check_switch, pad64, stream
+from .trainable import (AMP_ATTN_TYPES, AMP_TYPES, SWITCHES, TrainableModule, check_amp_attn_precision, check_amp_precision,
+                        check_switch, pad64, stream)
 from .weights import UnetConfig
 
 
@@ -186,6 +187,8 @@ def _switch(name, doc):
         check_switch("TrainableUnet", name, value)
         if name == "conv_precision":
             check_amp_precision("TrainableUnet", getattr(self, "_amp", "no"), value)
+        if name in ("attn_precision", "full_attn_precision"):
+            check_amp_attn_precision("TrainableUnet", getattr(self, "_amp_attn", "fp32"), name, value)
         setattr(self, "_" + name, value)
         for m in self.modules():
             if len(getattr(type(m), SWITCHES[name], ())) > 1:
@@ -209,9 +212,11 @@ class TrainableUnet(nn.Module):
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32, attn_heads=4,
                  full_attn=(False, False, False, True), flash_attn=False, mode="mri", conv_precision="fp32",
-                 act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32", full_attn_precision="fp32", amp="no"):
+                 act_storage="fp32", conv_out_storage="fp32", attn_precision="fp32", full_attn_precision="fp32", amp="no",
+                 amp_attn="fp32"):
         super().__init__()
         check_amp_precision("TrainableUnet", check_switch("TrainableUnet", "amp", amp, AMP_TYPES), conv_precision)
+        check_switch("TrainableUnet", "amp_attn", amp_attn, AMP_ATTN_TYPES)
         switches = dict(conv_precision=conv_precision, act_storage=act_storage, conv_out_storage=conv_out_storage,
                         attn_precision=attn_precision, full_attn_precision=full_attn_precision)
         for switch in SWITCHES:
@@ -278,6 +283,9 @@ class TrainableUnet(nn.Module):
         self._amp = "no"
         if amp != "no":
             self.amp = amp
+        self._amp_attn = "fp32"
+        if amp_attn != "fp32":
+            self.amp_attn = amp_attn
 
     @property
     def downsample_factor(self):
@@ -327,6 +335,24 @@ class TrainableUnet(nn.Module):
         for m in self.modules():
             if isinstance(m, TrainableModule):
                 m.amp = value
+
+    @property
+    def amp_attn(self):
+        """``"fp32"`` or ``"fp16"`` (``trainable.AMP_ATTN_TYPES``; not one of the switches): at ``"fp16"`` every ``LinearAttention``
+        and every ``Attention`` runs the passes of its core on the fp16 matrix cores (the modules' ``amp_attn``).  Refused
+        together with ``attn_precision = "bf16"`` or ``full_attn_precision = "bf16"``, in either order; a refused value changes
+        nothing.  Independent of ``amp`` here; ``DenoiserTrainer`` takes it only with ``amp=True``, for the loss scaler."""
+        return self._amp_attn
+
+    @amp_attn.setter
+    def amp_attn(self, value):
+        check_switch("TrainableUnet", "amp_attn", value, AMP_ATTN_TYPES)
+        for switch in ("attn_precision", "full_attn_precision"):
+            check_amp_attn_precision("TrainableUnet", value, switch, getattr(self, "_" + switch))
+        self._amp_attn = value
+        for m in self.modules():
+            if isinstance(m, TrainableModule) and type(m).AMP_ATTN_RIVAL is not None:
+                m.amp_attn = value
 
     def _join(self, a, b):
         _check_join("TrainableUnet", a, b)

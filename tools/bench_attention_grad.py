@@ -3,7 +3,7 @@
 restated in eager PyTorch (autograd) on the same GPU in one process, fp32, ms per forward + backward.
 
   python tools/bench_attention_grad.py [--batch 8] [--heads 4] [--iters 20] [--warmup 3] [--cases 128:32,256:32]
-                                       [--timeout 300] [--full-attn-precision fp32|bf16]
+                                       [--timeout 300] [--full-attn-precision fp32|bf16] [--amp-attn fp32|fp16]
 The default cases are cfg3's two uses of full attention (dim at H = W): the last stage of the down and up paths and
 ``mid_attn``.  Every case runs in a child process of its own under a time limit (``--timeout`` seconds; the HIP and the eager
 module share that process), and the first case that fails or runs out of time ends the run: nothing more is started on the
@@ -55,6 +55,7 @@ def run_case(dim, H, a):
     torch.manual_seed(0)
     mod = ldh.Attention(dim, heads=heads).cuda()
     mod.full_attn_precision = a.full_attn_precision
+    mod.amp_attn = a.amp_attn
     x = torch.randn(B, dim, H, H, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
     dout = (torch.randn(B, dim, H, H, device="cuda") / (B * H * H)).contiguous(memory_format=torch.channels_last)
 
@@ -68,7 +69,7 @@ def run_case(dim, H, a):
 
     hip = grad_bench.time_ms(hip_step, a.iters, a.warmup)
     split, calls = grad_bench.kernel_split(hip_step)
-    passes = {name: ms[idx] for label, ms in calls for name, (lab, idx, _) in PASSES.items() if label in (lab, lab + "16") and len(ms) > idx}
+    passes = {name: ms[idx] for label, ms in calls for name, (lab, idx, _) in PASSES.items() if label in (lab, lab + "16", lab + "_f16") and len(ms) > idx}
     n = H * H
     tflops = {k: PASSES[k][2] * 2 * n * n * 32 * B * heads / (ms * 1e9) for k, ms in passes.items() if ms > 0}
     eager = {}
@@ -76,7 +77,7 @@ def run_case(dim, H, a):
         res = grad_bench.eager_ms(mod, lambda p, xe: eager_attention(p, xe, heads, sdpa), x, [], dout, a.iters, a.warmup)
         eager.update({("sdpa_" if sdpa else "einsum_") + k: v for k, v in res.items()})
     best = min(eager.values()) if eager else None
-    return dict(dim=dim, H=H, B=B, heads=heads, full_attn_precision=a.full_attn_precision, hip_ms=hip, eager_ms=eager, eager_over_hip=(best / hip if best else None),
+    return dict(dim=dim, H=H, B=B, heads=heads, full_attn_precision=a.full_attn_precision, amp_attn=a.amp_attn, hip_ms=hip, eager_ms=eager, eager_over_hip=(best / hip if best else None),
                 kernels_ms=sum(v[0] for v in split.values()), pass_ms=passes, pass_tflops=tflops,
                 split={k: dict(ms=v[0], launches=v[1]) for k, v in split.items()})
 
@@ -86,7 +87,7 @@ def report(r):
     if r["eager_ms"]:
         eg = "eager PyTorch " + ", ".join(f"{k} {v:.3f} ms" for k, v in r["eager_ms"].items()) + \
             f"   (best eager / HIP = {r['eager_over_hip']:.2f})"
-    print(f"dim {r['dim']:4d} heads {r['heads']} @{r['H']:3d}^2 B={r['B']} full attn {r['full_attn_precision']}: HIP {r['hip_ms']:8.3f} ms   {eg}")
+    print(f"dim {r['dim']:4d} heads {r['heads']} @{r['H']:3d}^2 B={r['B']} full attn {r['full_attn_precision']}{grad_bench.amp_tag(r)}: HIP {r['hip_ms']:8.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
     for k, t in r["pass_tflops"].items():
         print(f"      {k:28s} {r['pass_ms'][k]:.3f} ms = {t:.1f} TFLOP/s ({100 * t / FP32_MATRIX_PEAK_TFLOPS:.0f} % of "
@@ -96,4 +97,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "128:32,256:32", run_case, report, heads=True, switches=("full_attn_precision",)))
+    sys.exit(grad_bench.main(__file__, "128:32,256:32", run_case, report, heads=True, switches=("full_attn_precision",), amp_attn=True))

@@ -7,6 +7,7 @@ default mode and a per-tensor ``lerp_`` EMA.  fp32, ms per step.
   python tools/bench_denoiser_train.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300]
                                        [--conv-precision fp32|bf16]   (the HIP trainer's convolutions; eager stays fp32)
                                        [--amp no|fp16]   (fp16: DenoiserTrainer(amp=True): fp16 convolutions and the loss scaler)
+                                       [--amp-attn fp32|fp16]   (fp16, with --amp fp16: the attention cores on the fp16 matrix cores)
                                        [--act-storage fp32|bf16]      (bf16 storage of conv-only activations; peak_mb shows it)
                                        [--conv-out-storage fp32|bf16] (bf16 storage of the convolution outputs GroupNorm reads)
 A case is data:H = W:batch; the default cases are those of tools/bench_unet_grad.py (cfg3 = mvtec 3 x 256^2 B = 8, mri 256^2
@@ -41,7 +42,7 @@ def run_case(data, H, B, a):
     inf = ldh.Unet(dim=32, init_dim=32, **U.KWARGS[data])
     gd = ldh.GaussianDiffusion(dict(OPTS, data=data), inf, image_size=H, timesteps=1000, objective="pred_v").cuda()
     tr = ldh.DenoiserTrainer(gd, train_lr=LR, adam_betas=BETAS, max_grad_norm=MAX_NORM, ema_update_every=1, ema_update_after_step=0,
-                             **grad_bench.switch_values(a, U.SWITCHES), amp=a.amp == "fp16")
+                             **grad_bench.switch_values(a, U.SWITCHES), amp=a.amp == "fp16", amp_attn=a.amp_attn)
     tr.ema_initted = True                                         # (every call lerps)
     cfg = tr.online_model.cfg
     hr = torch.rand(B, cfg.channels, H, H, device="cuda")
@@ -65,7 +66,7 @@ def run_case(data, H, B, a):
     hip_kern = sorted(kern)[2]
     n_all = sum(p.numel() for p in tr.online_model.parameters())
     nbytes = 4 * 10 * n_all
-    row = dict(data=data, H=H, B=B, **grad_bench.switch_values(a, U.SWITCHES), amp=a.amp, peak_mb=peak / 2 ** 20, hip_ms=hip, hip_opt_ms=hip_opt,
+    row = dict(data=data, H=H, B=B, **grad_bench.switch_values(a, U.SWITCHES), amp=a.amp, amp_attn=a.amp_attn, peak_mb=peak / 2 ** 20, hip_ms=hip, hip_opt_ms=hip_opt,
                hip_opt_kernels_ms=hip_kern, params=n_all, tensors=len(tr.names),
                opt_bytes=nbytes, opt_gbs=nbytes / (hip_kern * 1e-3) / 1e9, eager_ms=None, eager_opt_ms=None, eager_over_hip=None,
                eager_opt_over_hip=None)
@@ -114,4 +115,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, U.CASES, run_case, report, switches=U.SWITCHES, amp=True))
+    sys.exit(grad_bench.main(__file__, U.CASES, run_case, report, switches=U.SWITCHES, amp=True, amp_attn=True))

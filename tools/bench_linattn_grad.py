@@ -3,7 +3,7 @@
 module restated in eager PyTorch (autograd) on the same GPU in one process, fp32, ms per forward + backward.
 
   python tools/bench_linattn_grad.py [--batch 8] [--heads 4] [--iters 20] [--warmup 3] [--cases 32:256,64:128,128:64]
-                                     [--timeout 300] [--attn-precision {fp32,bf16}]
+                                     [--timeout 300] [--attn-precision {fp32,bf16}] [--amp-attn {fp32,fp16}]
 The default cases are the three levels of cfg3 that use linear attention (dim at H = W).  Every case runs in a child
 process of its own under a time limit (``--timeout`` seconds; the HIP and the eager module share that process), and the
 first case that fails or runs out of time ends the run: nothing more is started on the GPU after it.  Per case: 3 warm-up
@@ -32,7 +32,7 @@ import localdiffusion_hallucination_amd as ldh                    # noqa: E402
 
 # label -> (index of the pass's main launch inside the entry point, tensors of `hidden` floats per pixel it moves)
 PASSES = {"dn_la_context": (0, 2), "dn_la_out": (0, 2), "dn_la_backward_reduce": (0, 2), "dn_la_backward_apply": (0, 7)}
-PASSES.update({k + "16": v for k, v in list(PASSES.items())})          # the bf16 launches (--attn-precision bf16)
+PASSES.update({k + s: v for k, v in list(PASSES.items()) for s in ("16", "_f16")})    # --attn-precision bf16, --amp-attn fp16
 
 
 def eager_attention(p, x, heads):
@@ -56,6 +56,7 @@ def run_case(dim, H, a):
     torch.manual_seed(0)
     mod = ldh.LinearAttention(dim, heads=heads).cuda()
     mod.attn_precision = a.attn_precision
+    mod.amp_attn = a.amp_attn
     x = torch.randn(B, dim, H, H, device="cuda").contiguous(memory_format=torch.channels_last).requires_grad_(True)
     dout = (torch.randn(B, dim, H, H, device="cuda") / (B * H * H)).contiguous(memory_format=torch.channels_last)
 
@@ -74,7 +75,7 @@ def run_case(dim, H, a):
     eager = {} if a.no_eager else grad_bench.eager_ms(mod, lambda p, xe: eager_attention(p, xe, heads), x, [], dout, a.iters,
                                                       a.warmup)
     best = min(eager.values()) if eager else None
-    return dict(dim=dim, H=H, B=B, heads=heads, attn_precision=a.attn_precision, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
+    return dict(dim=dim, H=H, B=B, heads=heads, attn_precision=a.attn_precision, amp_attn=a.amp_attn, hip_ms=hip, eager_nchw_ms=eager.get("nchw"), eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), kernels_ms=sum(v[0] for v in split.values()), pass_ms=passes,
                 pass_gbs=gbs, split={k: dict(ms=v[0], launches=v[1]) for k, v in split.items()})
 
@@ -84,7 +85,7 @@ def report(r):
     if r["eager_nchw_ms"] is not None:
         eg = (f"eager PyTorch NCHW {r['eager_nchw_ms']:8.3f} ms, channels_last {r['eager_nhwc_ms']:8.3f} ms   "
               f"(best eager / HIP = {r['eager_over_hip']:.2f})")
-    print(f"dim {r['dim']:4d} heads {r['heads']} @{r['H']:3d}^2 B={r['B']} attn {r['attn_precision']}: HIP {r['hip_ms']:8.3f} ms   {eg}")
+    print(f"dim {r['dim']:4d} heads {r['heads']} @{r['H']:3d}^2 B={r['B']} attn {r['attn_precision']}{grad_bench.amp_tag(r)}: HIP {r['hip_ms']:8.3f} ms   {eg}")
     grad_bench.print_split(r["split"], r["kernels_ms"])
     for k, g in r["pass_gbs"].items():
         print(f"      {k:28s} main launch {r['pass_ms'][k]:.3f} ms = {g:.0f} GB/s ({100 * g / HBM_PEAK_GBS:.0f} % of "
@@ -92,4 +93,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64", run_case, report, heads=True, switches=("attn_precision",)))
+    sys.exit(grad_bench.main(__file__, "32:256,64:128,128:64", run_case, report, heads=True, switches=("attn_precision",), amp_attn=True))

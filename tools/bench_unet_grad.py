@@ -4,7 +4,7 @@ restated in eager PyTorch (autograd, MIOpen convolutions, ``F.group_norm``, eins
 fp32, ms per forward + backward.
 
   python tools/bench_unet_grad.py [--iters 20] [--warmup 3] [--cases data:H:B,...] [--timeout 300] [--conv-precision fp32|bf16]
-                                  [--amp no|fp16]
+                                  [--amp no|fp16] [--amp-attn fp32|fp16]
                                   [--act-storage fp32|bf16] [--conv-out-storage fp32|bf16]
 A case is data:H = W:batch; the default cases are cfg3 (mvtec, 3 x 256^2, B = 8), mri at 256^2 with B = 8 and mnist at 28^2
 with B = 64.  Every case runs in a child process of its own under a time limit (``--timeout`` seconds; the HIP and the eager
@@ -172,7 +172,7 @@ def families(split):
 def run_case(data, H, B, a):
     ldh.configure_runtime()
     torch.manual_seed(0)
-    net = ldh.TrainableUnet(dim=32, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, **KWARGS[data]).cuda()
+    net = ldh.TrainableUnet(dim=32, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, amp_attn=a.amp_attn, **KWARGS[data]).cuda()
     cfg = net.cfg
     x = torch.randn(B, cfg.channels, H, H, device="cuda")
     cond = torch.rand(B, cfg.cond_in_channels, H, H, device="cuda") * 2
@@ -207,7 +207,7 @@ def run_case(data, H, B, a):
         eager, ref = eager_ms(net, x, cond, time, dout, a.iters, a.warmup)
         diff = float((hip_step().detach() - ref).abs().max())
     best = min(eager.values()) if eager else None
-    return dict(data=data, H=H, B=B, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, peak_mb=peak / 2 ** 20,
+    return dict(data=data, H=H, B=B, **grad_bench.switch_values(a, SWITCHES), amp=a.amp, amp_attn=a.amp_attn, peak_mb=peak / 2 ** 20,
                 conv_out_bf16_saves_mb=y_saving / 2 ** 20, resnet_blocks=len(seen), hip_ms=hip, eager_nchw_ms=eager.get("nchw"),
                 eager_nhwc_ms=eager.get("nhwc"),
                 eager_over_hip=(best / hip if best else None), out_diff_to_eager=diff,
@@ -226,4 +226,4 @@ def report(r):
 
 
 if __name__ == "__main__":
-    sys.exit(grad_bench.main(__file__, CASES, run_case, report, switches=SWITCHES, amp=True))
+    sys.exit(grad_bench.main(__file__, CASES, run_case, report, switches=SWITCHES, amp=True, amp_attn=True))

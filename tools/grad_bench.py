@@ -135,16 +135,21 @@ AMP_HELP = ("the HIP side's convolutions on the fp16 matrix cores (TrainableModu
             "together with --conv-precision bf16); a trainer also runs its loss scaler")
 
 
+AMP_ATTN_HELP = ("the HIP side's attention cores on the fp16 matrix cores (amp_attn of LinearAttention / Attention / TrainableUnet: "
+                 "fp16 operands, fp32 accumulation; not together with a bf16 attention switch); a trainer needs --amp fp16 with it")
+
+
 def amp_tag(row):
-    """What a report line says about ``--amp``: nothing unless it was given."""
-    return f" / amp {row['amp']}" if row.get("amp", "no") != "no" else ""
+    """What a report line says about ``--amp`` and ``--amp-attn``: nothing unless they were given."""
+    return (f" / amp {row['amp']}" if row.get("amp", "no") != "no" else "") + \
+        (f" / amp attn {row['amp_attn']}" if row.get("amp_attn", "fp32") != "fp32" else "")
 
 
-def main(tool, cases, run_case, report, heads=False, switches=(), amp=False):
+def main(tool, cases, run_case, report, heads=False, switches=(), amp=False, amp_attn=False):
     """The tool's command line.  A case is ``a:b[:c...]`` (numbers, or names such as a layer kind); ``run_case(*case, args)``
     returns the case's JSON row and ``report(row)`` prints it.  ``switches``: the training precision switches the tool takes
     a flag for, e.g. ``("conv_precision", "act_storage")`` (``add_switch_flags``); ``amp``: the tool also takes ``--amp
-    no|fp16`` (``args.amp``).  Every case runs in a child process
+    no|fp16`` (``args.amp``); ``amp_attn``: and ``--amp-attn fp32|fp16`` (``args.amp_attn``).  Every case runs in a child process
     (``tool --child``) under ``--timeout``; the first one that fails or runs out of time ends the run, so that nothing more is
     started on the GPU after it."""
     ap = argparse.ArgumentParser()
@@ -154,6 +159,8 @@ def main(tool, cases, run_case, report, heads=False, switches=(), amp=False):
     add_switch_flags(ap, {s: SWITCH_HELP[s] for s in switches})
     if amp:
         ap.add_argument("--amp", default="no", choices=["no", "fp16"], help=AMP_HELP)
+    if amp_attn:
+        ap.add_argument("--amp-attn", default="fp32", choices=["fp32", "fp16"], help=AMP_ATTN_HELP)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default=cases)
@@ -166,7 +173,7 @@ def main(tool, cases, run_case, report, heads=False, switches=(), amp=False):
         (case,) = todo
         print("ROW " + json.dumps(run_case(*case, a)))
         return 0
-    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "amp") + tuple(switches) if hasattr(a, k)
+    passed_on = [w for k in ("batch", "heads", "iters", "warmup", "amp", "amp_attn") + tuple(switches) if hasattr(a, k)
                  for w in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
     rows = []
     for case in todo:

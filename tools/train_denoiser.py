@@ -62,6 +62,9 @@ def parse(argv=None):
     ap.add_argument("--mixed-precision-type", default="fp16", choices=["fp16", "bf16"],
                     help="with --amp: fp16 = the convolutions on the fp16 matrix cores under a loss scaler on the device "
                          "(GradScaler's defaults); bf16 = --conv-precision bf16, no scaler")
+    ap.add_argument("--amp-attn", default="fp32", choices=["fp32", "fp16"],
+                    help="fp16 (with --amp and --mixed-precision-type fp16 only): the attention cores on the fp16 matrix cores "
+                         "too, under the same loss scaler")
     ap.add_argument("--save-every", type=int, default=100)
     ap.add_argument("--init", default=None, help="reference checkpoint to start from (default: procedural weights, seed 0)")
     ap.add_argument("--seed", type=int, default=42)
@@ -108,6 +111,8 @@ def setup(a, **trainer_kw):
         if a.mixed_precision_type == "bf16" and switches["conv_precision"] == "fp32":
             del switches["conv_precision"]                    # (the flag's default: --amp chooses)
         trainer_kw = dict(trainer_kw, amp=True, mixed_precision_type=a.mixed_precision_type)
+    if getattr(a, "amp_attn", "fp32") != "fp32":
+        trainer_kw = dict(trainer_kw, amp_attn=a.amp_attn)
     trainer = ldh.DenoiserTrainer(gd.to(torch.device("cuda", torch.cuda.current_device())), train_lr=a.train_lr, **switches,
                                   **trainer_kw)
     return trainer, batches(tr_idx), batches(va_idx)
