@@ -15,7 +15,8 @@
  *   - no allocation and no synchronisation inside launch functions, so they may be captured into a HIP graph
  *     (ld_graph_*).  The library's only process-wide mutable state is what this header documents further down: the
  *     launch-routing table (ld_tuning_set / ld_tuning_get: read by the launch functions, written only by an explicit
- *     call or once from the environment), the launch-routing counters (ld_counter: diagnostics, relaxed atomics), the
+ *     call or once from the environment), the launch-routing counters (ld_counter: diagnostics, relaxed atomics) and
+ *     the per-thread word of the last launched route (ld_last_route: a diagnostic too), the
  *     per-(kernel, device) LDS-limit cache and an open timing session (ld_timing_*); none of it changes what a launch
  *     computes, only which kernel variant computes it.
  *   - internal activations are NHWC (channels-last) in the storage dtype (LD_F32, LD_BF16 or LD_F16),
@@ -92,7 +93,7 @@ int ld_stream_wait_event(void* stream, void* ev);
  * is an entry of this table: defaults compiled in, an environment override LD_<NAME IN CAPITALS> read ONCE when the
  * table is first used, and explicit control through ld_tuning_set (what localdiffusion_hallucination_amd.tuning.Tuning
  * applies).  Names (defaults): c1_group (1), c1_group_max_px (32768), c1_group_min_ch (4), c1_pair_max_px (2^40),
- * c1_small_min (256), conv_raw (1), conv_mt4_min_wgs (256), conv_big_min (512), conv_sk (0), conv_sk_max_wgs (256),
+ * c1_small_min (256), c1_big_min (512: workgroups of 256-pixel tiles from which ld_conv1x1 uses them instead of 128-pixel ones), conv_raw (1), conv_mt4_min_wgs (256), conv_big_min (512), conv_sk (0), conv_sk_max_wgs (256),
  * conv_c32 (0: the persistent LDS-DMA kernel is retired from the default routing, finding 99), conv_c32_min_tiles (2048), gn_frags_per_block (512), fold_split_min (32), attn_split_max_wgs (256), attn_split_min_n
  * (2048; and the two-key-group kernel is only taken when the second group owns a key: n > tile size), lead_args (1: gn_apply /
  * conv1x1 launches that qualify use the kernels with preloaded leading arguments), conv_s32 (3: bit mask of the launches the lean
@@ -117,6 +118,21 @@ const char* ld_tuning_name(int index);              /* NULL past the end */
 #define LD_COUNTER_CONV3X3_S32 2      /* ... by the lean Cout = 32 large-map kernel (conv3x3_s32.hip) */
 #define LD_COUNTER_MAX 8
 long long ld_counter(int which);
+/* The tile variant that the CALLING THREAD's most recent successful ld_conv3x3 / ld_conv1x1 call launched, as a packed
+ * word; -1 before the thread's first such launch (a refused call leaves the word as it was).  A diagnostic beside
+ * ld_counter: lets a test assert WHICH instantiation a shape ran on instead of inferring it from the thresholds.
+ *   LD_ROUTE_CONV3X3: bits 0-3 kernel family (0 generic conv3x3.hip, 1 lean conv3x3_s32.hip, 2 persistent
+ *     conv3x3_c32.hip); bits 4-7 MT (16-channel tiles per workgroup); bits 8-11 NW (16-pixel rows per wave: 4 NW rows per
+ *     tile); bit 12 RAW (the instantiation without the GroupNorm prologue); bit 13 SK (split-K halves); bit 14 SIDE (the
+ *     res_conv side output).  The lean and persistent kernels report their 32-channel x 16-row tile as MT 2, NW 4, and RAW
+ *     when the launch carried no GroupNorm prologue.
+ *   LD_ROUTE_CONV1X1: bits 0-3 MT; bits 4-7 NW (64 NW pixels per tile); bits 8-11 the epilogue instantiation (LD_EPI_*;
+ *     6 = LD_EPI_GN_TAIL with `residual` set); bits 12-15 G (K-chunks staged per barrier pair: 1, 2 or 4); bits 16-17 the
+ *     argument passing (0 the argument block, 1 preloaded sources / weights "klead", 2 preloaded tail operand "tlead"). */
+#define LD_ROUTE_CONV3X3 0
+#define LD_ROUTE_CONV1X1 1
+#define LD_ROUTE_MAX 2
+long long ld_last_route(int op);
 int ld_range_push(const char* name /* host string */);
 int ld_range_pop(void);
 
@@ -154,7 +170,7 @@ typedef struct ld_conv3x3_args {
   const float* bias;       /* [Cout] fp32 */
   void* out;               /* NHWC [B,H,W,Cout] */
   double* out_stats;       /* [B, LD_STAT_STRIPES, out_groups, 2] accumulated (caller zeroes) or NULL */
-  int32_t out_groups;
+  int32_t out_groups;      /* Cout / out_groups (channels per group) must divide 32: 1, 2, 4, 8, 16 or 32; else LD_EINVAL */
   int32_t B, H, W, Cout;   /* Cout multiple of 32 */
   const int32_t* t_ptr;
   int32_t dtype;

@@ -20,6 +20,7 @@ OBJ = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}
 SCHED_COLS = 8
 STAT_STRIPES = 16      # LD_STAT_STRIPES
 COUNTER_CONV3X3_C32, COUNTER_CONV3X3_GENERIC, COUNTER_CONV3X3_S32 = 0, 1, 2
+ROUTE_CONV3X3, ROUTE_CONV1X1 = 0, 1     # LD_ROUTE_*: ld_last_route's argument
 SEG_SRC_PLAIN, SEG_SRC_POOL, SEG_SRC_CAT_D2S = 0, 1, 2
 CLF_PLAIN, CLF_HALVE, CLF_AFFINE = 0, 1, 2
 
@@ -110,6 +111,7 @@ _SIGS = {
     "ld_event_destroy": (C.c_int, [vp]),
     "ld_stream_wait_event": (C.c_int, [vp, vp]),
     "ld_counter": (C.c_longlong, [C.c_int]),
+    "ld_last_route": (C.c_longlong, [C.c_int]),
     "ld_tuning_set": (C.c_int, [C.c_char_p, C.c_longlong]),
     "ld_tuning_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
     "ld_tuning_count": (C.c_int, []),

@@ -21,7 +21,15 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // ---------------------------------------------------------------- host-side error plumbing
 int ld_fail(int code, const char* fmt, ...);   // runtime.hip
 void ld_count(int which);                        // runtime.hip: LD_COUNTER_* launch-routing counters
-#define LD_HIP(call)                                                                   \
+// runtime.hip: the calling thread's last launched route (ld_last_route; bit layouts in include/localdiff_hip.h).  Host only.
+void ld_route_set(int op, long long word);
+static inline long long ld_route3(int family, int mt, int nw, bool raw, bool sk, bool side) {
+  return (long long)family | (mt << 4) | (nw << 8) | ((int)raw << 12) | ((int)sk << 13) | ((int)side << 14);
+}
+static inline long long ld_route1(int mt, int nw, int epi, int g, int lead) {
+  return (long long)mt | (nw << 4) | (epi << 8) | (g << 12) | (lead << 16);
+}
+#define LD_HIP(call)                                                                  \
   do {                                                                                 \
     hipError_t e_ = (call);                                                            \
     if (e_ != hipSuccess) return ld_fail(LD_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
@@ -68,6 +76,7 @@ struct LdTuning {
   long long conv_s32, conv_s32_min_tiles;
   long long conv_big4_min;
   long long gn_frags_per_block, fold_split_min, attn_split_max_wgs, attn_split_min_n, lead_args, attn_xcd_map;
+  long long c1_big_min;
 };
 const LdTuning& ld_tuning();
 

@@ -488,6 +488,7 @@ int launch_epi(const Conv1Dev& a, hipStream_t st) {
         LD_LAUNCH((conv1x1_taillead_kernel<T, MT, NW, EPI, 2>), grid, dim3(256), lds, st, LD_C1_TLEAD_ARGS);
       }
       LD_LAUNCH_CHECK("conv1x1(GroupNorm tail, lead)");
+      ld_route_set(LD_ROUTE_CONV1X1, ld_route1(MT, NW, EPI, a.group, 2));
       return LD_OK;
     }
   }
@@ -508,6 +509,7 @@ int launch_epi(const Conv1Dev& a, hipStream_t st) {
       }
 #undef LD_C1_KLEAD_ARGS
       LD_LAUNCH_CHECK("conv1x1(grouped K, lead)");
+      ld_route_set(LD_ROUTE_CONV1X1, ld_route1(MT, NW, EPI, a.group, 1));
       return LD_OK;
     }
   }
@@ -516,6 +518,7 @@ int launch_epi(const Conv1Dev& a, hipStream_t st) {
     if (lds > 65536) LD_HIP(ld_allow_lds((conv1x1_kernel<T, MT, NW, EPI, KG>), lds));   // cached per device
     LD_LAUNCH((conv1x1_kernel<T, MT, NW, EPI, KG>), grid, dim3(256), lds, st, a);
     LD_LAUNCH_CHECK("conv1x1(grouped K)");
+    ld_route_set(LD_ROUTE_CONV1X1, ld_route1(MT, NW, EPI, KG, 0));
     return LD_OK;
   }
   if (a.group == 2) {
@@ -523,10 +526,12 @@ int launch_epi(const Conv1Dev& a, hipStream_t st) {
     if (lds > 65536) LD_HIP(ld_allow_lds((conv1x1_kernel<T, MT, NW, EPI, 2>), lds));
     LD_LAUNCH((conv1x1_kernel<T, MT, NW, EPI, 2>), grid, dim3(256), lds, st, a);
     LD_LAUNCH_CHECK("conv1x1(grouped K, pairs)");
+    ld_route_set(LD_ROUTE_CONV1X1, ld_route1(MT, NW, EPI, 2, 0));
     return LD_OK;
   }
   LD_LAUNCH((conv1x1_kernel<T, MT, NW, EPI>), grid, dim3(256), chunk + tail, st, a);
   LD_LAUNCH_CHECK("conv1x1");
+  ld_route_set(LD_ROUTE_CONV1X1, ld_route1(MT, NW, EPI, 1, 0));
   return LD_OK;
 }
 
@@ -582,7 +587,7 @@ int dispatch(const Conv1Dev& a0, hipStream_t st) {
   const long small_min = ld_tuning().c1_small_min;
   if (mt4 && (long)((HW + 127) / 128) * (a.Cout / 64) * a.B < small_min) mt4 = false;
   const long blocks4 = (long)((HW + 255) / 256) * (a.Cout / (mt4 ? 64 : 32)) * a.B;
-  const bool big = blocks4 >= 512;
+  const bool big = blocks4 >= ld_tuning().c1_big_min;
   if (mt4) return big ? launch<T, 4, 4>(a, st) : launch<T, 4, 2>(a, st);
   return big ? launch<T, 2, 4>(a, st) : launch<T, 2, 2>(a, st);
 }

@@ -51,6 +51,7 @@ int launch_dbg(const Conv3Dev& a, hipStream_t st) {
   LD_LAUNCH((conv3x3_kernel<T, MT, NW, DEEP, DBG, SK, RAW, SIDE>), grid, dim3(SK ? 512 : 256), lds, st, d.s[0].data, d.w, d.H, d.W, d.tiles_x,
             d.s[0].C, d.s[0].ld, d.s[0].ups, d.nsrc, d.wsplit, d.Cout, d);
   LD_LAUNCH_CHECK("conv3x3");
+  ld_route_set(LD_ROUTE_CONV3X3, ld_route3(0, MT, NW, RAW, SK, SIDE));
   return LD_OK;
 }
 
@@ -194,8 +195,10 @@ extern "C" int ld_conv3x3(const ld_conv3x3_args* p, void* stream) {
   }
   if (p->nsrc == 1) a.s[1] = a.s[0];
   if (p->out_stats) {
-    LD_REQUIRE(p->out_groups > 0 && p->Cout % p->out_groups == 0 && (p->Cout / p->out_groups) <= 32,
-               "ld_conv3x3: out_groups %d incompatible with Cout %d", p->out_groups, p->Cout);
+    // a workgroup's 32- or 64-channel tile must hold whole groups: the epilogue adds (16 MT) / gs groups per workgroup, so a
+    // group width that does not divide 32 (Cout = 96 with 8 groups: 12 channels) gave WRONG statistics (finding 142)
+    LD_REQUIRE(p->out_groups > 0 && p->Cout % p->out_groups == 0 && 32 % (p->Cout / p->out_groups) == 0,
+               "ld_conv3x3: out_groups %d incompatible with Cout %d (channels per group must divide 32)", p->out_groups, p->Cout);
   }
   a.w = p->weight; a.bias = p->bias; a.out = p->out; a.ostats = p->out_stats;
   a.ogroups = p->out_groups > 0 ? p->out_groups : 1;

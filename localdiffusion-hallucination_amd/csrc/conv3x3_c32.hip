@@ -419,6 +419,7 @@ int launch_c32_dbg(C32Dev& a, size_t lds, dim3 grid, hipStream_t st) {
   if (lds > 65536) LD_HIP(ld_allow_lds((conv3x3_c32_kernel<T, NCH, R, DBG>), lds));   // cached per device
   LD_LAUNCH((conv3x3_c32_kernel<T, NCH, R, DBG>), grid, dim3(512), lds, st, a);
   LD_LAUNCH_CHECK("conv3x3_c32");
+  ld_route_set(LD_ROUTE_CONV3X3, ld_route3(2, 2, 4, !a.s[0].stats, false, false));
   return LD_OK;
 }
 

@@ -290,6 +290,7 @@ int launch_s32(const ld_conv3x3_args* p, hipStream_t st) {
   const dim3 grid((p->W / 16) * (p->H / 16), 1, p->B);
   LD_LAUNCH((conv3x3_s32_kernel<T, NCH, PRO>), grid, dim3(256), 0, st, s0.data, p->weight, p->H | (p->W << 16), ld0, s0.C, d);
   LD_LAUNCH_CHECK("conv3x3_s32");
+  ld_route_set(LD_ROUTE_CONV3X3, ld_route3(1, 2, 4, !PRO, false, false));
   return LD_OK;
 }
 

@@ -196,7 +196,8 @@ LdTuning g_tuning = {/*c1_group*/ 1, /*c1_group_max_px*/ 32768, /*c1_group_min_c
                      /*conv_raw*/ 1, /*conv_mt4_min_wgs*/ 256, /*conv_big_min*/ 512, /*conv_sk*/ 0, /*conv_sk_max_wgs*/ 256,
                      /*conv_c32*/ 0, /*conv_c32_min_tiles*/ 2048, /*conv_s32*/ 3, /*conv_s32_min_tiles*/ 1024, /*conv_big4_min*/ 256,
                      /*gn_frags_per_block*/ 512, /*fold_split_min*/ 32,
-                     /*attn_split_max_wgs*/ 256, /*attn_split_min_n*/ 2048, /*lead_args*/ 1, /*attn_xcd_map*/ 1};
+                     /*attn_split_max_wgs*/ 256, /*attn_split_min_n*/ 2048, /*lead_args*/ 1, /*attn_xcd_map*/ 1,
+                     /*c1_big_min*/ 512};
 struct TuningEntry { const char* name; long long LdTuning::*field; };
 const TuningEntry g_tuning_entries[] = {
     {"c1_group", &LdTuning::c1_group}, {"c1_group_max_px", &LdTuning::c1_group_max_px}, {"c1_group_min_ch", &LdTuning::c1_group_min_ch},
@@ -205,7 +206,8 @@ const TuningEntry g_tuning_entries[] = {
     {"conv_sk_max_wgs", &LdTuning::conv_sk_max_wgs}, {"conv_c32", &LdTuning::conv_c32}, {"conv_c32_min_tiles", &LdTuning::conv_c32_min_tiles},
     {"conv_s32", &LdTuning::conv_s32}, {"conv_s32_min_tiles", &LdTuning::conv_s32_min_tiles}, {"conv_big4_min", &LdTuning::conv_big4_min},
     {"gn_frags_per_block", &LdTuning::gn_frags_per_block}, {"fold_split_min", &LdTuning::fold_split_min},
-    {"attn_split_max_wgs", &LdTuning::attn_split_max_wgs}, {"attn_split_min_n", &LdTuning::attn_split_min_n}, {"lead_args", &LdTuning::lead_args}, {"attn_xcd_map", &LdTuning::attn_xcd_map}};
+    {"attn_split_max_wgs", &LdTuning::attn_split_max_wgs}, {"attn_split_min_n", &LdTuning::attn_split_min_n}, {"lead_args", &LdTuning::lead_args}, {"attn_xcd_map", &LdTuning::attn_xcd_map},
+    {"c1_big_min", &LdTuning::c1_big_min}};
 constexpr int g_tuning_n = sizeof(g_tuning_entries) / sizeof(g_tuning_entries[0]);
 void tuning_env_once() {
   // the ONE place the library reads tuning from the environment: LD_<NAME IN CAPITALS>, once per process
@@ -258,6 +260,15 @@ void ld_count(int which) {
 extern "C" long long ld_counter(int which) {
   return (which >= 0 && which < LD_COUNTER_MAX) ? g_counters[which].load(std::memory_order_relaxed) : -1;
 }
+
+// ---- which tile variant the calling thread's last ld_conv3x3 / ld_conv1x1 launched (diagnostic, like the counters) ----
+namespace {
+thread_local long long g_last_route[LD_ROUTE_MAX] = {-1, -1};
+}
+void ld_route_set(int op, long long word) {
+  if (op >= 0 && op < LD_ROUTE_MAX) g_last_route[op] = word;
+}
+extern "C" long long ld_last_route(int op) { return (op >= 0 && op < LD_ROUTE_MAX) ? g_last_route[op] : -1; }
 
 hipError_t ld_allow_lds_ptr(const void* kernel, size_t bytes) {
   int dev = 0;

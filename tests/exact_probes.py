@@ -36,10 +36,29 @@ FINAL_CASES = [(32, 1), (32, 3), (64, 1), (64, 3),             # cin, cout at 9 
                (8, 2), (8, 4), (24, 4), (40, 3)]               # ... a partial pass of the 4 x 16 B channel loop, cout 2 and 4
 ATTN_SIZES = [49, 324, 400, 1024, 4096]
 LINATTN_SHAPES = [(32, 28, 28), (64, 14, 14), (32, 64, 96)]    # C, H, W
+# ---- the shapes of tests/test_hip_conv_tiles.py (every tile variant of ld_conv3x3 / ld_conv1x1, forced through the routing table)
+TILE3_RAGGED32 = [(2, 64, 32, 40, 24), (1, 32, 96, 33, 20)]    # ragged in both axes for 8- and 16-row tiles; Cout % 64 != 0, one row past two 16-row tiles
+TILE3_RAGGED64 = [BIG64_SHAPE, (2, 64, 64, 17, 23)]
+TILE3_WHOLE = {32: (1, 128, 32, 32, 48), 64: (1, 128, 64, 32, 48)}   # whole tiles only: every workgroup takes the FULL emit path
+TILE3_SK_SHAPES = [(1, 256, 64, 16, 16), (1, 96, 32, 13, 18)]    # eight chunks; an odd chunk count on a ragged map
+TILE3_CAT = (2, 64, 32, 40, 24)                                  # B, c1 (half resolution), c2, H, W of conv3x3_concat_upsample
+TILE3_CAT_COUTS = [32, 96, 128]
+TILE3_ADDEND_SHAPES = [(2, 64, 32, 40, 24), (2, 64, 128, 40, 24), (2, 64, 32, 17, 23)]
+TILE1_SHAPES = [(2, 64, 64, 17, 23), (2, 96, 128, 17, 23), (2, 64, 96, 17, 23)]   # 391 pixels: one 256-pixel tile + 135, the last 16-pixel group holds 7
+TILE1_GROUP_SHAPES = [(1, 160, 32, 20, 28), (1, 416, 64, 17, 23), (2, 128, 64, 9, 11)]   # 5 and 13 chunks (partial groups); below one tile
+TILE1_CAT = (2, 64, 32, 17, 23)                                  # B, c1, c2, H, W of conv1x1_concat
+TILE1_UNSHUFFLE = (2, 32, 17, 23)                                # B, c, H, W of conv1x1_unshuffle
+TILE1_VARIANT_COUTS = [64, 128]
 # ---- the shapes of tests/test_hip_attention_heads.py (head counts other than the model's default of 4)
 OTHER_HEADS = [1, 2, 8]
 ATTN_HEADS_SIZES = [49, 324]                                   # one ragged key tile; three tiles, two key groups
 KVCTX_HEADS_SHAPES = [(32, 28, 28), (64, 14, 14), (128, 7, 7)] # C, H, W: 3 pixel chunks; one ragged tile; 49 pixels, four K-chunks
+
+
+def tile_groups(cout):
+    """Statistics groups of the tile tests: the model's 8, but 12 at Cout = 96 -- ld_conv3x3 takes group widths that divide
+    32 (a workgroup's channel tile holds whole groups), and 96 / 8 = 12 does not (docs/findings.md 142)."""
+    return 8 if 32 % (cout // 8) == 0 else 12
 
 
 def ints(shape, key, lo, hi):
@@ -116,12 +135,23 @@ def conv3x3(B, cin, cout, H, W, key=1000, frac=False, groups=8):
     return NS(x=x, w=w, b=b, ref=ref, stats=stats)
 
 
-def conv3x3_concat_upsample(B=2, c1=64, c2=32, cout=32, H=12, W=12, key=1100):
+def conv3x3_addend(B, cin, cout, H, W, key=1300, groups=8):
+    """conv3x3 plus ``add``, an integer tensor in [-4, 4] of the output's shape (ld_conv3x3_args.addend): the addend
+    enters BEFORE the statistics, so ``stats`` are those of conv + bias + add."""
+    x, w, b = trits((B, cin, H, W), key), trits((cout, cin, 3, 3), key + 1), bias_for(cout, key + 2)
+    add = ints((B, cout, H, W), key + 3, -4, 4)
+    ref, stats = _conv(x, w, b, 1, residual=add, groups=groups)
+    plain, plain_stats = _conv(x, w, b, 1, groups=groups)
+    assert not torch.equal(ref, plain) and not torch.equal(stats, plain_stats)      # a dropped addend shows in both
+    return NS(x=x, w=w, b=b, add=add, ref=ref, stats=stats)
+
+
+def conv3x3_concat_upsample(B=2, c1=64, c2=32, cout=32, H=12, W=12, key=1100, groups=8):
     """Two sources: c1 channels at half resolution (nearest x2 on load) ++ c2 channels."""
     x1, x2 = trits((B, c1, H // 2, W // 2), key), trits((B, c2, H, W), key + 1)
     w, b = trits((cout, c1 + c2, 3, 3), key + 2), bias_for(cout, key + 3)
     xc = torch.cat([F.interpolate(x1, scale_factor=2, mode="nearest"), x2], 1)
-    ref, stats = _conv(xc, w, b, 1, groups=8)
+    ref, stats = _conv(xc, w, b, 1, groups=groups)
     return NS(x1=x1, x2=x2, w=w, b=b, ref=ref, stats=stats)
 
 

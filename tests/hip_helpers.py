@@ -79,8 +79,8 @@ def make_src(t, c, stride=0, ups=0, gn=None, act=0, film=None, film_b=0, film_t=
     return s
 
 
-def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_ptr=None, side=None):
-    """``side`` = (packed 1x1 weight, bias): returns (out, side_out)."""
+def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_ptr=None, side=None, addend=None):
+    """``side`` = (packed 1x1 weight, bias): returns (out, side_out).  ``addend``: NHWC device tensor in the storage dtype."""
     a = cabi.Conv3x3Args()
     for i, s in enumerate(srcs):
         a.src[i] = s
@@ -92,6 +92,7 @@ def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_p
         a.out_stats, a.out_groups = stats.data_ptr(), groups
     a.B, a.H, a.W, a.Cout, a.dtype = B, H, W, cout, cabi.dtype_code(dtype)
     a.t_ptr = cabi.ptr(t_ptr)
+    a.addend = cabi.ptr(addend)
     side_out = None
     if side is not None:
         side_out = nans(B, H, W, cout, dtype=TDT[dtype])
@@ -117,6 +118,23 @@ def conv1x1(srcs, wpacked, B, H, W, cout, dtype, bias=None, epi=0, unshuffle=0, 
     a.B, a.H, a.W, a.Cout, a.dtype = B, H, W, cout, cabi.dtype_code(dtype)
     cabi.check(cabi.lib().ld_conv1x1(C.byref(a), st()), "conv1x1")
     return out
+
+
+ROUTE3_FAMILY = {0: "generic", 1: "lean", 2: "persistent"}
+ROUTE1_LEAD = {0: "none", 1: "klead", 2: "tlead"}
+EPI_GN_TAIL_RES = 6          # conv1x1.hip's internal instantiation of LD_EPI_GN_TAIL with `residual` set
+
+
+def last_route(op):
+    """ld_last_route decoded (the bit layout of include/localdiff_hip.h): None before the thread's first launch, else a dict --
+    ROUTE_CONV3X3: family, MT, NW, raw, sk, side; ROUTE_CONV1X1: MT, NW, epi, G, lead."""
+    w = int(cabi.lib().ld_last_route(op))
+    if w < 0:
+        return None
+    if op == cabi.ROUTE_CONV3X3:
+        return dict(family=ROUTE3_FAMILY[w & 15], MT=(w >> 4) & 15, NW=(w >> 8) & 15, raw=bool((w >> 12) & 1), sk=bool((w >> 13) & 1),
+                    side=bool((w >> 14) & 1))
+    return dict(MT=w & 15, NW=(w >> 4) & 15, epi=(w >> 8) & 15, G=(w >> 12) & 15, lead=ROUTE1_LEAD[(w >> 16) & 3])
 
 
 SENTINEL = -1024.0

@@ -532,6 +532,13 @@ CONV_CASES = [
     _cv(BIG64_SHAPE[1], BIG64_SHAPE[2], BIG64_SHAPE[3], BIG64_SHAPE[4], B=BIG64_SHAPE[0], route="big64", film="batch"),
     _cv(96, 32, 13, 18, B=1, route="sk", film="shared"),
     _cv(256, 64, 16, 16, B=2, route="sk", G=16, film="batch", layout="last"),
+    # the general (GroupNorm-prologue) instantiations of the 32-channel x 16-row tile <2,4> ("big32") and of the 64-channel x
+    # 8-row tile <4,2> ("rows8x64"), which no default threshold reaches at these sizes: ragged maps with H >= 16
+    _cv(64, 32, 17, 23, route="big32", src="gn+raw", film="shared"),
+    _cv(64, 96, 18, 22, route="big32", src="ups", film="table"),
+    _cv(32, 32, 20, 28, route="big32", film="batch", layout="last"),
+    _cv(64, 64, 17, 23, route="rows8x64", src="raw+gn", film="batch"),
+    _cv(128, 64, 20, 28, B=1, route="rows8x64", src="ups", G=16, film="shared", layout="last"),
     _cv(32, 32, 32, 32, B=2, route="c32", film="shared"),
     _cv(32, 32, 48, 32, route="s32", film=None),
     _cv(32, 32, 48, 32, route="s32", film="shared", layout="last"),

@@ -54,6 +54,53 @@ def test_conv1x1_variant_probes():
     assert torch.equal(unet_ref.pixel_unshuffle_conv(sd, "d", p.x), p.ref)      # the oracle's rearrangement
 
 
+TILE3_ALL = sorted(set(P.TILE3_RAGGED32 + P.TILE3_RAGGED64 + list(P.TILE3_WHOLE.values()) + P.TILE3_SK_SHAPES))
+
+
+@pytest.mark.parametrize("shape", TILE3_ALL)
+@pytest.mark.parametrize("frac", [False, True])
+def test_conv3x3_tile_probes(shape, frac):
+    """The shapes of tests/test_hip_conv_tiles.py: ragged for 8- and 16-row tiles, whole tiles only, eight K-chunks."""
+    p = P.conv3x3(*shape, frac=frac, groups=P.tile_groups(shape[2]))
+    assert float(p.ref.abs().max()) > 8
+    assert p.stats.shape[1] == (12 if shape[2] == 96 else 8) and 32 % (shape[2] // p.stats.shape[1]) == 0
+
+
+def test_conv3x3_tile_variant_probes():
+    B, c1, c2, H, W = P.TILE3_CAT
+    for cout in P.TILE3_CAT_COUTS:
+        p = P.conv3x3_concat_upsample(B, c1, c2, cout, H, W, groups=P.tile_groups(cout))
+        assert p.ref.shape == (B, cout, H, W) and p.x1.shape == (B, c1, H // 2, W // 2)
+    for shape in P.TILE3_ADDEND_SHAPES:
+        p = P.conv3x3_addend(*shape)
+        assert float(p.add.abs().max()) == 4.0 and P.is_integer(p.add)
+        for dt in ("bf16", "fp16"):
+            P.check_representable(p.add, dt)
+        # the statistics are taken AFTER the addend
+        assert torch.equal(p.stats, P.gn_stats_ref(F.conv2d(p.x.double(), p.w.double(), p.b.double(), padding=1) + p.add.double(), 8))
+
+
+@pytest.mark.parametrize("shape", P.TILE1_SHAPES)
+def test_conv1x1_tile_probes(shape):
+    """391 pixels: a 256-pixel tile plus 135, a 16-pixel group of 7 at the end -- plain, rounding, residual, per-batch weights."""
+    assert shape[3] * shape[4] == 391
+    P.conv1x1(*shape)
+    P.conv1x1(*shape, frac=True)
+    P.conv1x1(*shape, residual=True)
+    P.conv1x1(*shape, residual=True, per_batch=True)
+
+
+def test_conv1x1_tile_variant_probes():
+    for shape in P.TILE1_GROUP_SHAPES:
+        P.conv1x1(*shape)
+    B, c1, c2, H, W = P.TILE1_CAT
+    Bu, cu, Hu, Wu = P.TILE1_UNSHUFFLE
+    for cout in P.TILE1_VARIANT_COUTS:
+        P.conv1x1_concat(B, c1, c2, cout, H, W)
+        p = P.conv1x1_unshuffle(Bu, cu, cout, Hu, Wu)
+        assert p.x.shape == (Bu, cu, 2 * Hu, 2 * Wu)
+
+
 @pytest.mark.parametrize("cin,ks,H,W", P.IMAGE_CASES)
 def test_conv_image_probes(cin, ks, H, W):
     P.conv_image(cin, ks, H, W)

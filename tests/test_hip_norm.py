@@ -1,6 +1,7 @@
 """Parity of the GroupNorm / FiLM path with its fp64 form (tests/norm_ref.py, proved on the CPU by
 tests/test_norm_ref.py) at the five sites that share build_gn_coef / affine_act_n: ld_gn_apply (lead kernel and the four
-generic instantiations), the prologue of the generic 3x3 kernel (also the 64 x 16-row tile and split-K halves), the
+generic instantiations), the prologue of the generic 3x3 kernel (every tile: 32 x 8 rows by default, 64 x 16, 32 x 16 and
+64 x 8 rows forced and confirmed with ld_last_route; split-K halves), the
 persistent and the lean 3x3 kernels, and the LD_EPI_GN_TAIL epilogue of ld_conv1x1.
 
 The rule is norm_ref.compare, per (sample, group): fp32 storage within max(4 d, one fp32 ulp of the group's largest
@@ -134,6 +135,14 @@ ROUTES = {   # route -> (tuning entries, expected (c32, generic, s32) launches)
     "sk": (dict(conv_sk=2, conv_s32=0, conv_c32=0), (0, 1, 0)),
     "c32": (dict(conv_c32=1, conv_c32_min_tiles=1, conv_s32=0), (1, 0, 0)),
     "s32": (dict(conv_s32=7, conv_s32_min_tiles=1, conv_c32=0), (0, 0, 1)),
+    "big32": (dict(conv_big_min=1, conv_mt4_min_wgs=1 << 40, conv_s32=0, conv_c32=0, conv_sk=0), (0, 1, 0)),
+    "rows8x64": (dict(conv_mt4_min_wgs=1, conv_big4_min=1 << 40, conv_s32=0, conv_c32=0, conv_sk=0), (0, 1, 0)),
+}
+# route -> what ld_last_route must report for it (the routes whose tile does not depend on the case's shape)
+TILES = {
+    "big64": dict(family="generic", MT=4, NW=4, raw=False, sk=False, side=False),
+    "big32": dict(family="generic", MT=2, NW=4, raw=False, sk=False, side=False),
+    "rows8x64": dict(family="generic", MT=4, NW=2, raw=False, sk=False, side=False),
 }
 
 
@@ -160,6 +169,8 @@ def run_conv(k, dtype, route, t=0):
         before = counters()
         out = hh.conv3x3(conv_sources(k, dtype), w, bias, c.B, c.H, c.W, c.cout, dtype, t_ptr=t_tensor(c.film, t))
         assert launched(before) == want, (route, launched(before))
+        if route in TILES:
+            assert hh.last_route(cabi.ROUTE_CONV3X3) == TILES[route], (route, hh.last_route(cabi.ROUTE_CONV3X3))
     return hh.nchw(out)
 
 

@@ -371,7 +371,7 @@ def test_full_map_pixel_count_for_an_upsampled_source_is_rejected():
             bad = _fails(k, as_stored(_pre("conv", k, "npix_full"), dt), dt)
             assert bool(bad[_norm_groups("conv", k, _all(k))].all()), (c.id, dt)
             n += 1
-    assert n == 3
+    assert n == 9                             # three upsampled cases (generic, big32, rows8x64) in three storage types
 
 
 def test_padding_that_receives_the_activated_shift_is_rejected():
