@@ -1186,6 +1186,35 @@ int ld_dn_wgrad_f16(const float* dy, const float* a, float* work, float* dw, int
                     int splits, void* stream);
 int ld_dn_pack_conv_f16(const float* w_oihw, void* fwd_f16, void* dgr_f16, int co, int cop, int ci, int cip, int k, void* stream);
 
+/* ---- device-resident training data (data.py's MNIST, MvtecDatasetSR and MedDataset_png as Trainer builds them): csrc/dataset.hip
+ * One launch per batch: B rows of a device table choose B images of a device store and their augmentation; hr and lr come out as
+ * contiguous fp32 NCHW, 16-byte aligned.  The rotation is torchvision's tensor rotate (NEAREST, expand = False, fill = None) about
+ * the image centre, a positive angle counter-clockwise, followed by the vertical flip; (cos 1, sin 0, flip 0) is the identity
+ * exactly.  Every operation is a single correctly rounded fp32 operation (IEEE division, nothing contracted), no floating-point
+ * atomics, nothing allocates, nothing synchronises; a refused call returns LD_EINVAL before anything is launched.  The HOST
+ * validates the table's indices against N (the kernels only clamp them). */
+typedef struct ld_ds_row {
+  int32_t src;             /* index of the image in the store, 0 <= src < N */
+  float cos_a, sin_a;      /* of the rotation angle, computed in double and rounded */
+  int32_t flip;            /* non-zero: reverse the rows after the rotation */
+} ld_ds_row;
+#define LD_DS_MIN_PARTS 16 /* row bands per image of ld_ds_mri_batch's minimum */
+/* data.MNIST (data.py:814-836): store u8 [N, S, S] (S even; 28), hr / lr [B, 1, S, S].  hr = 2 (x / 255) of the transformed image;
+ * lr = its even rows (all columns) brought back to S rows by bilinear interpolation (align_corners = False), then 2 (. / 255). */
+int ld_ds_mnist_batch(const void* store_u8, int N, int S, const ld_ds_row* table, int B, float* hr, float* lr, void* stream);
+/* MvtecDatasetSR (data.py:287-307, train, no denoise, no mask_train): store u8 [N, C, S, S], C 1 or 3, S even; hr / lr [B, C, S, S].
+ * hr = (x / 255) 2; lr = the even rows and columns of hr (nearest to S / 2), bilinear back to S x S (align_corners = False):
+ * columns first, then rows. */
+int ld_ds_sr_batch(const void* store_u8, int N, int C, int S, const ld_ds_row* table, int B, float* hr, float* lr, void* stream);
+/* MedDataset_png (data.py:369-442): two fp32 stores [N, R, R] of finite values; hr [B, 1, crop, crop] from target, lr from cond.
+ * Centre crop (top = left = round((R - crop) / 2), half to even), the row's rotation and flip inside the crop for both (corners
+ * fill with 0), (x - mean) / std with the modality's constants (std > 0), and with translate_zero + |min| of that image.  The
+ * minimum takes a first launch that leaves LD_DS_MIN_PARTS partial minima per image in work (B * 2 * LD_DS_MIN_PARTS floats;
+ * may be NULL without translate_zero).  crop a multiple of 4, crop <= R. */
+int ld_ds_mri_batch(const float* target, const float* cond, int N, int R, int crop, const ld_ds_row* table, int B, float mean_target,
+                    float std_target, float mean_cond, float std_cond, int translate_zero, float* work, float* hr, float* lr,
+                    void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

@@ -33,7 +33,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
            "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "TimeMLP", "TrainableUnet", "DenoiserTrainer", "coreset",
-           "configure_runtime"]
+           "DeviceDataset", "BatchSource", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -85,4 +85,7 @@ def __getattr__(name):
     if name == "DenoiserTrainer":
         from .denoiser_train import DenoiserTrainer
         return DenoiserTrainer
+    if name in ("DeviceDataset", "BatchSource"):
+        from . import dataset
+        return getattr(dataset, name)
     raise AttributeError(name)

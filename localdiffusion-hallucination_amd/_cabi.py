@@ -92,6 +92,12 @@ class DnScalerState(C.Structure):
                 ("inv_scale", f32), ("step_size", f32), ("bc2_sqrt", f32)]
 
 
+class DsRow(C.Structure):
+    """``ld_ds_row``: one sample of a ``DeviceDataset`` batch (store index, cos / sin of its angle, flip flag)."""
+    _fields_ = [("src", i32), ("cos_a", f32), ("sin_a", f32), ("flip", i32)]
+
+
+DS_MIN_PARTS = 16      # LD_DS_MIN_PARTS
 DN_OPT_CHUNK, DN_OPT_ADAM, DN_OPT_MAX_WORLD = 4096, 1, 64     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM, LD_DN_OPT_MAX_WORLD
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
@@ -293,6 +299,9 @@ _SIGS = {
     "ld_dn_conv_f16": (C.c_int, [C.POINTER(PcConvArgs), vp, vp]),
     "ld_dn_wgrad_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_dn_pack_conv_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ld_ds_mnist_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "ld_ds_sr_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "ld_ds_mri_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, f32, f32, f32, C.c_int, vp, vp, vp, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

@@ -44,6 +44,11 @@ every scaling and unscaling is exact and ``(g * inv_scale) * coef`` could as wel
 other ``scaler_kwargs`` factors the order is torch's.  Data parallel: every rank reduces the same gathered bits in rank order,
 so ``found_inf`` and the scale are the same on all ranks with nothing new on the wire.
 
+Data.  ``train_step`` and ``fit`` take a list of ``(hr, lr)`` batches, trained on as they are at every step, or a
+``dataset.BatchSource`` over a ``DeviceDataset`` -- the reference's ``DataLoader(shuffle=True)`` and augmentation
+(ddpm.py:1538-1553): the source is asked for ``batches(self.step)`` at every step, and because its plan is a pure function of
+``(seed, step)`` a resumed run and every rank of a data-parallel run see the same global batches.
+
 NOT covered: 16-bit storage, more than one node, ragged shards (a batch size that is no multiple of the world size), a sharded
 evaluation (every rank evaluates every test batch), 16-bit gradients on the wire, FID, writing the kernel-layout weight copies from the optimiser launch
 (the modules repack after a step, as they do under ``torch.optim.Adam``), handing padded tensors between modules.
@@ -56,6 +61,7 @@ import torch
 
 from . import _cabi as cabi
 from . import checkpoint
+from .dataset import BatchSource
 from .trainable import (AMP_ATTN_TYPES, SWITCHES, check_amp_attn_precision, check_amp_precision, check_storage_precision, check_switch,
                         stream)
 from .unet_grad import TrainableUnet
@@ -559,22 +565,39 @@ class DenoiserTrainer:
                 tdist.all_gather_into_tensor(self._gathered.view(-1), self._send, group=self.group)
         return self._gathered
 
-    def train_step(self, batches):
+    def train_step(self, batches, t=None, noise=None):
         """The reference's step: ``accumulate(hr, lr, scale=1 / len(batches))`` over all ``(hr, lr)`` batches, ``apply()``;
         returns the summed loss (the reference's ``total_loss``) on the device.  ``data_parallel`` (``split_batches=True``):
         every rank is handed the same global batches and takes its rows of each, the scale is ``1 / (world * len(batches))``
-        and the loss is the sum over the ranks; a batch size that is no multiple of ``world`` is a ``ValueError``."""
-        batches = list(batches)
-        if not batches:
+        and the loss is the sum over the ranks; a batch size that is no multiple of ``world`` is a ``ValueError``.
+
+        ``batches``: a list of ``(hr, lr)``, or a ``dataset.BatchSource``, which is asked for ``batches(self.step)`` -- the
+        DataLoader's fresh shuffle and augmentation at every step -- and walked lazily: batch k + 1 is made after batch k has
+        been accumulated, and ``len()`` needs no batch.  ``t`` / ``noise``: None (drawn, as ``accumulate`` draws them) or one
+        entry per batch for the GLOBAL batch (a rank takes its rows)."""
+        if isinstance(batches, BatchSource):
+            batches = batches.batches(self.step)
+            sizes = list(batches.sizes)
+        else:
+            batches = list(batches)
+            sizes = [int(hr.shape[0]) for hr, _ in batches]
+        n = len(batches)
+        if not n:
             raise ValueError("DenoiserTrainer: no batches")
+        for name, given in (("t", t), ("noise", noise)):
+            if given is not None and len(given) != n:
+                raise ValueError(f"DenoiserTrainer: {n} batches need {n} entries of {name}, got {len(given)}")
+        t = [None] * n if t is None else list(t)
+        noise = [None] * n if noise is None else list(noise)
         if self.data_parallel:
-            rows = [shard_rows(int(hr.shape[0]), self.world, self.rank) for hr, _ in batches]      # (before any GPU call)
-            for (hr, lr), (lo, hi) in zip(batches, rows):
-                self.accumulate(hr[lo:hi], lr[lo:hi], scale=1.0 / (self.world * len(batches)))
+            rows = [shard_rows(size, self.world, self.rank) for size in sizes]      # (before any GPU call)
+            for (hr, lr), (lo, hi), tk, nk in zip(batches, rows, t, noise):
+                self.accumulate(hr[lo:hi], lr[lo:hi], scale=1.0 / (self.world * n), t=None if tk is None else tk[lo:hi],
+                                noise=None if nk is None else nk[lo:hi])
             return self.apply()
         total = None
-        for hr, lr in batches:
-            value = self.accumulate(hr, lr, scale=1.0 / len(batches))
+        for (hr, lr), tk, nk in zip(batches, t, noise):
+            value = self.accumulate(hr, lr, scale=1.0 / n, t=tk, noise=nk)
             total = value if total is None else total + value
         self.apply()
         return total
@@ -713,7 +736,8 @@ class DenoiserTrainer:
 
     # ------------------------------------------------------------------ the loop
     def fit(self, batches, test_batches, num_steps, save_and_sample_every, out_dir, min_max_val=None):
-        """``Trainer.train`` (ddpm.py:1532-1606) until ``step == num_steps``: ``train_step(batches)``; every
+        """``Trainer.train`` (ddpm.py:1532-1606) until ``step == num_steps``: ``train_step(batches)`` (a list, trained on as it is
+        at every step, or a ``BatchSource``, reshuffled and re-augmented at every step); every
         ``save_and_sample_every`` steps ``evaluate(test_batches)`` and, at a new best, ``save`` to
         ``<out_dir>/model-best<step rounded up to 100 (mnist) or 500>.pt``.  ``train_loss.csv`` and ``loss.csv`` have the
         layout pandas gives the reference's frames (an index column, ``epoch``, ``loss``); ``train_loss.csv`` holds every
@@ -725,7 +749,8 @@ class DenoiserTrainer:
         if min_max_val is None:
             min_max_val = (0.0, 1.0) if data == "mnist" else (-1.0, 1.0) if data == "mri" else (0.0, 2.0)
         os.makedirs(out_dir, exist_ok=True)
-        batches, test_batches = list(batches), list(test_batches)
+        batches = batches if isinstance(batches, BatchSource) else list(batches)      # (a source makes each step's anew)
+        test_batches = list(test_batches)
         train_rows, eval_rows, best = [], [], 1e10
 
         def write(name, rows):

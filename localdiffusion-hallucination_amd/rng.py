@@ -75,6 +75,11 @@ def uniform(shape, seed, stream, lo=0.0, hi=1.0):
     return (lo + (hi - lo) * u).astype(np.float32).reshape(shape)
 
 
+def bits64(n, seed, stream):
+    """The first ``n`` 64-bit hashes of a draw (uint64): what ``randn`` and ``uniform`` are made from."""
+    return _hash(seed, stream, int(n))
+
+
 def fnv1a64(text):
     """FNV-1a hash of a parameter name -> 64-bit stream id for procedural weights."""
     h = 0xCBF29CE484222325
