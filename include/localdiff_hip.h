@@ -1214,6 +1214,19 @@ int ld_ds_sr_batch(const void* store_u8, int N, int C, int S, const ld_ds_row* t
 int ld_ds_mri_batch(const float* target, const float* cond, int N, int R, int crop, const ld_ds_row* table, int B, float mean_target,
                     float std_target, float mean_cond, float std_cond, int translate_zero, float* work, float* hr, float* lr,
                     void* stream);
+/* The two labelled data sets, for SegTrainer and MnistClassifierTrainer; the same table, rotation, flip and contract as above.
+ * MedSegDataset (data.py:676-743) behind the .mha decode: image fp32 [N, R, R] of finite values, label_u8 [N, R, R]; x and target
+ * fp32 [B, 1, crop, crop], 16-byte aligned.  ld_ds_mri_batch's centre crop, the row's rotation and flip inside the crop for both
+ * (the reference has its flips commented out: (cos 1, sin 0, flip 0) is the reference); x = (v - mean) / std with v = 0 outside
+ * the rotated image, target = label > 0 ? 1 : 0 and 0 outside.  One launch of B * 2 planes.  crop a multiple of 4, 4 <= crop <= R;
+ * std positive and finite, mean a number. */
+int ld_ds_seg_batch(const float* image, const void* label_u8, int N, int R, int crop, const ld_ds_row* table, int B, float mean,
+                    float std, float* x, float* target, void* stream);
+/* data.MNIST with its third return value (data.py:814-836): store u8 [N, S, S] (S even, 2..16384), labels_u8 [N]; x [B, 1, S, S]
+ * is ld_ds_mnist_batch's hr (16-byte aligned; no lr is made), label [B] int64 (8-byte aligned), label[b] = labels_u8[src_b],
+ * written by one thread per sample.  The HOST validates the labels' range; the kernel copies them. */
+int ld_ds_mnist_cls_batch(const void* store_u8, const void* labels_u8, int N, int S, const ld_ds_row* table, int B, float* x,
+                          long long* label, void* stream);
 
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH

@@ -5,6 +5,9 @@
 //   ld_ds_mnist_batch   u8 [N, S, S]      hr = 2 (x / 255); lr = the even ROWS of the transformed image, bilinear back to S rows
 //   ld_ds_sr_batch      u8 [N, C, S, S]   hr = (x / 255) 2; lr = its even rows and columns, bilinear back to S x S
 //   ld_ds_mri_batch     fp32 [N, R, R] x2 centre crop, the same rotation and flip for both, (x - mean) / std, + |min| of the image
+// and the two labelled data sets (MedSegDataset for SegTrainer, MNIST with its labels for MnistClassifierTrainer):
+//   ld_ds_seg_batch       fp32 + u8 [N, R, R]  centre crop, the same rotation and flip for both; x = (v - mean) / std, target = label > 0
+//   ld_ds_mnist_cls_batch u8 [N, S, S] + u8 [N] x = ld_ds_mnist_batch's hr; label = the sample's class as int64 (no lr)
 //
 // A thread produces four consecutive pixels of a plane (one 16-byte store per output); a plane has a multiple of four
 // pixels (S even, crop a multiple of 4), so a group may straddle two rows and every pixel computes its own coordinates.
@@ -185,12 +188,71 @@ __global__ __launch_bounds__(DS_BLOCK) void ds_mri_kernel(const float* __restric
   ds_put4((mod ? lr : hr) + (size_t)b * crop * crop + 4 * (size_t)g, v);
 }
 
-int ds_check_common(const char* name, const void* store, int N, const void* table, int B, const void* hr, const void* lr) {
+// ------------------------------------------------------------------------------------------------ seg
+// MedSegDataset.__getitem__: plane b * 2 is the image (fp32, normalised), plane b * 2 + 1 the label (u8 -> {0, 1}).  ONE launch
+// of B * 2 planes rather than one per output: a batch is launch-bound (a few us of kernel under tens of us of launch), the
+// plane's kind is uniform over a block (no divergence), and both planes of a sample read the same table row and compute the
+// same source coordinates, so image and label cannot drift apart -- the arrangement ds_mri_kernel has for its two modalities.
+__global__ __launch_bounds__(DS_BLOCK) void ds_seg_kernel(const float* __restrict__ image, const unsigned char* __restrict__ label,
+                                                         const DsRow* __restrict__ table, float* x, float* target, int R, int crop,
+                                                         int top, int N, float mean, float sd, int groups, int bpp) {
+  const int plane = blockIdx.x / bpp;                          // b * 2 + (0: image, 1: label)
+  const int g = (blockIdx.x - plane * bpp) * DS_BLOCK + threadIdx.x;
+  if (g >= groups) return;
+  const int b = plane >> 1;
+  DsF32 T;
+  T.r = table[b];
+  T.R = R; T.crop = crop; T.top = top;
+  const size_t base = (size_t)ds_index(T.r, N) * R * R;
+  T.img = image + base;
+  const unsigned char* lab = label + base;
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int p = 4 * g + e, i = p / crop, j = p - i * crop;
+    if (plane & 1) {                                           // (uniform)
+      int sy, sx;
+      v[e] = (ds_source(T.r, i, j, crop, crop, sy, sx) && lab[(size_t)(top + sy) * R + top + sx] > 0) ? 1.0f : 0.0f;
+    } else {
+      v[e] = __fdiv_rn(__fsub_rn(T.at(i, j), mean), sd);       // (0 outside the rotated image, then normalised)
+    }
+  }
+  ds_put4(((plane & 1) ? target : x) + (size_t)b * crop * crop + 4 * (size_t)g, v);
+}
+
+// ------------------------------------------------------------------------------------------------ mnist with labels
+// ds_mnist_kernel without lr; the sample's label is written by the owner of pixel group 0 of the sample's first block
+__global__ __launch_bounds__(DS_BLOCK) void ds_mnist_cls_kernel(const unsigned char* __restrict__ store,
+                                                               const unsigned char* __restrict__ labels,
+                                                               const DsRow* __restrict__ table, float* x, long long* label, int S, int N,
+                                                               int groups, int bpp) {
+  const int b = blockIdx.x / bpp;
+  const int g = (blockIdx.x - b * bpp) * DS_BLOCK + threadIdx.x;
+  if (g >= groups) return;
+  DsU8 T;
+  T.r = table[b];
+  T.S = S;
+  const int src = ds_index(T.r, N);
+  T.img = store + (size_t)src * S * S;
+  float h[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int p = 4 * g + e, i = p / S;
+    h[e] = __fmul_rn(2.0f, __fdiv_rn(T.at(i, p - i * S), 255.0f));
+  }
+  ds_put4(x + (size_t)b * S * S + 4 * (size_t)g, h);
+  if (g == 0) label[b] = (long long)labels[src];
+}
+
+// the second output is written with 16-byte stores too, or (lr_mask = 7) is ld_ds_mnist_cls_batch's int64 labels
+int ds_check_common(const char* name, const void* store, int N, const void* table, int B, const void* hr, const void* lr,
+                    unsigned lr_mask = 15) {
   LD_REQUIRE(store && table && hr && lr, "%s: null pointer", name);
   LD_REQUIRE(N >= 1, "%s: the store holds N = %d images", name, N);
   LD_REQUIRE(B >= 1, "%s: B = %d (an empty batch)", name, B);
-  LD_REQUIRE(((uintptr_t)hr & 15) == 0 && ((uintptr_t)lr & 15) == 0 && ((uintptr_t)table & 3) == 0,
-             "%s: hr and lr must be 16-byte aligned, the table 4-byte", name);
+  LD_REQUIRE(((uintptr_t)hr & 15) == 0 && ((uintptr_t)lr & lr_mask) == 0 && ((uintptr_t)table & 3) == 0,
+             lr_mask == 15 ? "%s: hr and lr must be 16-byte aligned, the table 4-byte"
+                           : "%s: x must be 16-byte aligned, label 8-byte, the table 4-byte", name);
   return 0;
 }
 
@@ -257,5 +319,37 @@ extern "C" int ld_ds_mri_batch(const float* target, const float* cond, int N, in
             (const float*)(translate_zero ? work : nullptr), hr, lr, R, crop, top, N, mean_target, std_target, mean_cond, std_cond, groups,
             bpp);
   LD_LAUNCH_CHECK("ds_mri_kernel");
+  return 0;
+}
+
+extern "C" int ld_ds_seg_batch(const float* image, const void* label_u8, int N, int R, int crop, const ld_ds_row* table, int B,
+                               float mean, float sd, float* x, float* target, void* stream) {
+  if (int rc = ds_check_common("ld_ds_seg_batch", image, N, table, B, x, target)) return rc;
+  LD_REQUIRE(label_u8, "ld_ds_seg_batch: null pointer");
+  LD_REQUIRE(R >= 1 && R <= 16384, "ld_ds_seg_batch: R = %d (1..16384)", R);
+  LD_REQUIRE(crop >= 4 && crop <= R, "ld_ds_seg_batch: crop = %d does not fit R = %d", crop, R);
+  LD_REQUIRE(crop % 4 == 0, "ld_ds_seg_batch: crop = %d must be a multiple of 4", crop);
+  LD_REQUIRE(sd > 0.0f && sd <= 3.0e38f && mean == mean, "ld_ds_seg_batch: std must be positive and finite, mean a number");
+  int groups, bpp;
+  unsigned blocks;
+  if (int rc = ds_grid("ld_ds_seg_batch", (long)B * 2, (long)crop * crop, groups, bpp, blocks)) return rc;
+  const int d = R - crop, top = (d & 1) ? ((d / 2) & 1 ? d / 2 + 1 : d / 2) : d / 2;      // ld_ds_mri_batch's CenterCrop
+  LD_LAUNCH(ds_seg_kernel, dim3(blocks), dim3(DS_BLOCK), 0, (hipStream_t)stream, image, (const unsigned char*)label_u8, table, x, target,
+            R, crop, top, N, mean, sd, groups, bpp);
+  LD_LAUNCH_CHECK("ds_seg_kernel");
+  return 0;
+}
+
+extern "C" int ld_ds_mnist_cls_batch(const void* store_u8, const void* labels_u8, int N, int S, const ld_ds_row* table, int B, float* x,
+                                     long long* label, void* stream) {
+  if (int rc = ds_check_common("ld_ds_mnist_cls_batch", store_u8, N, table, B, x, label, 7)) return rc;
+  LD_REQUIRE(labels_u8, "ld_ds_mnist_cls_batch: null pointer");
+  LD_REQUIRE(S >= 2 && S % 2 == 0 && S <= 16384, "ld_ds_mnist_cls_batch: S = %d must be even (2..16384)", S);
+  int groups, bpp;
+  unsigned blocks;
+  if (int rc = ds_grid("ld_ds_mnist_cls_batch", B, (long)S * S, groups, bpp, blocks)) return rc;
+  LD_LAUNCH(ds_mnist_cls_kernel, dim3(blocks), dim3(DS_BLOCK), 0, (hipStream_t)stream, (const unsigned char*)store_u8,
+            (const unsigned char*)labels_u8, table, x, label, S, N, groups, bpp);
+  LD_LAUNCH_CHECK("ds_mnist_cls_kernel");
   return 0;
 }

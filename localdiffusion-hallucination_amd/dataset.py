@@ -3,7 +3,8 @@ the store in device memory and a step's batches produced there by ``csrc/dataset
 ``translate_zero``) from a few bytes of host-drawn parameters, so the host stays off the training step's critical path.
 
 ``DeviceDataset`` holds a raw store on the GPU and turns indices (and, under ``augmentations``, an angle and a flip bit per
-sample: ``RandomRotation(15)`` + ``RandomVerticalFlip()``, data.py:372-376 / 783-786) into an ``(hr, lr)`` batch:
+sample: ``RandomRotation(15)`` + ``RandomVerticalFlip()``, data.py:372-376 / 783-786) into an ``(hr, lr)`` batch for the
+denoiser, or an ``(input, target)`` / ``(input, label)`` batch for the two labelled trainers:
 
 * ``DeviceDataset.mnist``  ``data.MNIST`` (data.py:814-836): u8 [N, S, S]; hr = 2 x / 255, lr from the even ROWS (data.py:825
   slices dims 0, 1, 2 of the [1, 1, S, S] image, as ``evalio.mnist_pairs`` pins), bilinear back to S rows;
@@ -11,20 +12,29 @@ sample: ``RandomRotation(15)`` + ``RandomVerticalFlip()``, data.py:372-376 / 783
   already resized (the PIL ``Resize`` is a one-off host step); hr = (x / 255) 2, lr = nearest to S / 2, bilinear back.  The
   reference does not augment this data set; the angle and the flip are honoured as an extension when ``augmentations=True``;
 * ``DeviceDataset.mri``    ``MedDataset_png`` (data.py:369-442): two fp32 stores [N, R, R]; centre crop, the SAME rotation and
-  flip for both, (x - mean) / std, and with ``translate_zero`` + |min| of the cropped, transformed, normalised image.
+  flip for both, (x - mean) / std, and with ``translate_zero`` + |min| of the cropped, transformed, normalised image;
+* ``DeviceDataset.seg``    ``MedSegDataset`` (data.py:676-743, what ``train_seg.py:51-54`` and so ``SegTrainer`` read) behind the
+  ``.mha`` decode: an fp32 store [N, R, R] and a u8 store of ``labels > 0``; centre crop, (x - mean) / std, target = 0 / 1.  The
+  reference has its flips commented out (data.py:709-710); the angle and the flip -- the same for image and label -- are
+  honoured as an extension when ``augmentations=True``.  ``evalio.lesion_slices`` is its slice filter (data.py:695-698);
+* ``DeviceDataset.mnist_cls``  ``data.MNIST`` with its third return value, the label (what ``train_mnist_cls.py:68-71`` and so
+  ``MnistClassifierTrainer`` read): the mnist store and a u8 store of the labels, validated on the host once; ``batch`` gives
+  ``(x, label)`` with x = mnist's hr and label int64 [B].  No lr is made: the classifier never reads it.
 
 The rotation is torchvision's tensor ``rotate`` (``NEAREST``, ``expand=False``, ``fill=None``) restated from its source; the
 package is not available where this was built, so the restatement could not be run against it (it was checked against
 ``F.grid_sample`` on ``_gen_affine_grid``'s grid: tests/dataset_ref.py).  cos / sin are computed in double on the host and rounded
-to fp32; every device operation is a single correctly rounded fp32 operation, so the mnist and mri batches are those of the same
-chain on a CPU, bit for bit, and only the SR path's two-axis bilinear may differ by rounding (ATen may contract it).
+to fp32; every device operation is a single correctly rounded fp32 operation, so the mnist, mri, seg and mnist_cls batches are
+those of the same chain on a CPU, bit for bit, and only the SR path's two-axis bilinear may differ by rounding (ATen may
+contract it).
 
 ``BatchSource`` is the ``DataLoader``: ``plan(step)`` is a pure function of ``(seed, step)``, so a run resumed at step k, every
 rank of a data-parallel run, and a test on the CPU all see the batches an uninterrupted single-GPU run sees at step k.
+``SegTrainer.fit`` and ``MnistClassifierTrainer.fit`` take a source too and ask it for ``batches(epoch)``: all three trainers
+take their batches the same way, from one seeded plan.
 
 NOT covered: ``MvtecDatasetGray``, the salt-and-pepper ``denoise`` mode, ``mask_train`` / ``select_patch``, the PIL resize, the
-nii / OCT / ImageNet loaders, ``MedSegDataset`` for ``SegTrainer`` and the labels for ``MnistClassifierTrainer`` (the last two are
-the obvious follow-up on the same kernels).
+nii / OCT / ImageNet loaders, the ``.mha`` decode in front of ``seg``, and a PatchCore bank built from a source.
 """
 import math
 
@@ -86,9 +96,17 @@ def _host_u8(images, ndim, what):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
+def _crop_arg(what, crop, size):
+    if not isinstance(crop, int) or isinstance(crop, bool) or crop < 4 or crop > size:
+        raise ValueError(f"DeviceDataset.{what}: crop = {crop!r} does not fit the {size} x {size} slices")
+    if crop % 4:
+        raise ValueError(f"DeviceDataset.{what}: crop = {crop} must be a multiple of 4")
+
+
 class DeviceDataset:
-    """A raw store on the GPU and the kernel that makes ``(hr, lr)`` batches from it.  Build one with ``mnist``, ``sr`` or
-    ``mri``; ``len()``, ``channels``, ``image_size`` (of a batch), ``kind`` and ``augmentations`` say what it is."""
+    """A raw store on the GPU and the kernel that makes batches from it: ``(hr, lr)`` for ``mnist``, ``sr`` and ``mri``,
+    ``(x, target)`` for ``seg``, ``(x, label)`` for ``mnist_cls``.  ``len()``, ``channels``, ``image_size`` (of a batch),
+    ``kind`` and ``augmentations`` say what it is."""
 
     def __init__(self, kind, stores, channels, image_size, augmentations, device, **params):
         device = torch.device(device)
@@ -132,10 +150,7 @@ class DeviceDataset:
         if host[0].shape != host[1].shape:
             raise ValueError(f"DeviceDataset.mri: target {tuple(host[0].shape)} and cond {tuple(host[1].shape)} differ")
         size = int(host[0].shape[-1])
-        if not isinstance(crop, int) or isinstance(crop, bool) or crop < 4 or crop > size:
-            raise ValueError(f"DeviceDataset.mri: crop = {crop!r} does not fit the {size} x {size} slices")
-        if crop % 4:
-            raise ValueError(f"DeviceDataset.mri: crop = {crop} must be a multiple of 4")
+        _crop_arg("mri", crop, size)
         consts = {}
         for name, v in (("mean_target", mean_target), ("std_target", std_target), ("mean_cond", mean_cond), ("std_cond", std_cond)):
             v = float(np.float32(v))
@@ -144,31 +159,87 @@ class DeviceDataset:
             consts[name] = v
         return cls("mri", tuple(host), 1, crop, augmentations, device, translate_zero=bool(translate_zero), size=size, **consts)
 
+    @classmethod
+    def seg(cls, images, labels, *, mean, std, crop=224, augmentations=False, device="cuda"):
+        """``images``: [N, R, R] slices (converted to fp32, finite); ``labels``: [N, R, R] of any real or bool dtype, stored
+        once as u8 of ``labels > 0``; ``mean`` / ``std``: the config's ``mean_flair`` / ``std_flair``.  ``batch`` gives
+        ``(x, target)``, both fp32 [B, 1, crop, crop].  (``SegUNet`` wants multiples of 16: the trainer's own check.)"""
+        img = images.detach().cpu().numpy() if torch.is_tensor(images) else np.asarray(images)
+        lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        if img.ndim != 3 or img.shape[0] < 1 or img.shape[1] != img.shape[2]:
+            raise ValueError(f"DeviceDataset.seg: images must be [N, R, R] with N >= 1, got {img.shape}")
+        if lab.shape != img.shape:
+            raise ValueError(f"DeviceDataset.seg: images {img.shape} and labels {lab.shape} differ")
+        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.floating) or lab.dtype == np.bool_):
+            raise ValueError(f"DeviceDataset.seg: labels must be real or bool, got {lab.dtype}")
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if not np.isfinite(img).all():
+            raise ValueError("DeviceDataset.seg: images hold a non-finite value")
+        if np.issubdtype(lab.dtype, np.floating) and np.isnan(lab).any():
+            raise ValueError("DeviceDataset.seg: labels hold a NaN")
+        size = int(img.shape[-1])
+        _crop_arg("seg", crop, size)
+        consts = {}
+        for name, v in (("mean", mean), ("std", std)):
+            v = float(np.float32(v))
+            if not math.isfinite(v) or (name == "std" and not v > 0.0):
+                raise ValueError(f"DeviceDataset.seg: {name} = {v!r} must be finite{' and positive' if name == 'std' else ''}")
+            consts[name] = v
+        lab = np.ascontiguousarray(lab > 0).astype(np.uint8)
+        return cls("seg", (torch.from_numpy(img), torch.from_numpy(lab)), 1, crop, augmentations, device, size=size, **consts)
+
+    @classmethod
+    def mnist_cls(cls, images_u8, labels, *, augmentations=False, device="cuda"):
+        """``images_u8``: uint8 [N, S, S] as for ``mnist``; ``labels``: an integer array [N], every value in 0..9 (checked here,
+        once, so that ``MnistClassifierTrainer``'s ``bad_label`` flag never fires on a source).  ``batch`` gives ``(x, label)``:
+        x = ``mnist``'s hr, label int64 [B] on the device."""
+        x = _host_u8(images_u8, 3, "mnist_cls")
+        y = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        if y.ndim != 1 or y.shape[0] != x.shape[0]:
+            raise ValueError(f"DeviceDataset.mnist_cls: {x.shape[0]} images need {x.shape[0]} labels, got shape {y.shape}")
+        if not np.issubdtype(y.dtype, np.integer):
+            raise ValueError(f"DeviceDataset.mnist_cls: labels must be integers, got {y.dtype}")
+        if int(y.min()) < 0 or int(y.max()) > 9:
+            raise ValueError(f"DeviceDataset.mnist_cls: a label lies outside 0..9 (min {int(y.min())}, max {int(y.max())})")
+        return cls("mnist_cls", (x, torch.from_numpy(np.ascontiguousarray(y.astype(np.uint8)))), 1, x.shape[-1], augmentations, device)
+
     def __len__(self):
         return self._n
 
+    def _out_spec(self, B):
+        """(shape, dtype) of the two tensors ``batch`` returns."""
+        shape = (B, self.channels, self.image_size, self.image_size)
+        if self.kind == "mnist_cls":
+            return (shape, torch.float32), ((B,), torch.int64)
+        return (shape, torch.float32), (shape, torch.float32)
+
     def batch(self, indices, angles_deg=None, flips=None, out=None):
-        """``(hr, lr)`` fp32 [B, channels, image_size, image_size] on the device for the images ``indices`` (a sequence of
+        """``(hr, lr)`` -- ``(x, target)`` for ``seg`` -- fp32 [B, channels, image_size, image_size], or ``(x, label)`` with
+        label int64 [B] for ``mnist_cls``, on the device for the images ``indices`` (a sequence of
         ints, repeats allowed), sample k rotated by ``angles_deg[k]`` degrees (positive: counter-clockwise) and then flipped
         vertically where ``flips[k]``.  Without ``augmentations`` both must be ``None``.  ``ValueError`` -- before anything
         is uploaded or launched -- for an index outside ``[0, len)``, an empty batch, or parameters that do not fit.  The table
         goes up from pinned memory without waiting and the launch follows it on the current stream: no host synchronisation.
-        ``out``: a ready ``(hr, lr)`` pair of contiguous fp32 device tensors of the batch's shape to write into."""
+        ``out``: a ready pair of contiguous device tensors of the batch's shapes and dtypes to write into (two fp32 tensors;
+        an fp32 and an int64 tensor for ``mnist_cls``), checked before anything is uploaded."""
         if not self.augmentations and (angles_deg is not None or flips is not None):
             raise ValueError("DeviceDataset.batch: angles / flips given, but the data set was built with augmentations=False")
         rows = table_rows(indices, self._n, angles_deg, flips)
         B, dev, lib = rows.size, self.device, cabi.lib()
-        shape = (B, self.channels, self.image_size, self.image_size)
+        spec = self._out_spec(B)
         if out is not None:
-            for t in out:
-                if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
-                        and tuple(t.shape) == shape):
-                    raise ValueError(f"DeviceDataset.batch: out must be two contiguous fp32 tensors {shape} on {dev}")
+            out = tuple(out)
+            if len(out) != 2 or not all(torch.is_tensor(t) and t.dtype == dt and t.is_contiguous() and t.device == dev
+                                        and tuple(t.shape) == shape for t, (shape, dt) in zip(out, spec)):
+                if self.kind == "mnist_cls":
+                    raise ValueError(f"DeviceDataset.batch: out must be a contiguous fp32 tensor {spec[0][0]} and a contiguous int64 "
+                                     f"tensor {spec[1][0]} on {dev}")
+                raise ValueError(f"DeviceDataset.batch: out must be two contiguous fp32 tensors {spec[0][0]} on {dev}")
         with torch.cuda.device(dev):
             pinned = torch.empty(rows.nbytes, dtype=torch.uint8, pin_memory=True)
             pinned.numpy()[:] = rows.view(np.uint8)
             table = pinned.to(dev, non_blocking=True)          # (the pinned block is not reused before the copy has run)
-            hr, lr = out if out is not None else (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(2))
+            hr, lr = out if out is not None else (torch.empty(shape, dtype=dt, device=dev) for shape, dt in spec)
             st = torch.cuda.current_stream(dev).cuda_stream
             if self.kind == "mnist":
                 rc = lib.ld_ds_mnist_batch(self._stores[0].data_ptr(), self._n, self.image_size, table.data_ptr(), B,
@@ -176,6 +247,13 @@ class DeviceDataset:
             elif self.kind == "sr":
                 rc = lib.ld_ds_sr_batch(self._stores[0].data_ptr(), self._n, self.channels, self.image_size, table.data_ptr(), B,
                                         hr.data_ptr(), lr.data_ptr(), st)
+            elif self.kind == "seg":
+                p = self.params
+                rc = lib.ld_ds_seg_batch(self._stores[0].data_ptr(), self._stores[1].data_ptr(), self._n, p["size"], self.image_size,
+                                         table.data_ptr(), B, p["mean"], p["std"], hr.data_ptr(), lr.data_ptr(), st)
+            elif self.kind == "mnist_cls":
+                rc = lib.ld_ds_mnist_cls_batch(self._stores[0].data_ptr(), self._stores[1].data_ptr(), self._n, self.image_size,
+                                               table.data_ptr(), B, hr.data_ptr(), lr.data_ptr(), st)
             else:
                 p = self.params
                 work = torch.empty(B * 2 * cabi.DS_MIN_PARTS, dtype=torch.float32, device=dev) if p["translate_zero"] else None
@@ -257,5 +335,5 @@ class BatchSource:
         return {"indices": perm[:m], "angles_deg": angles, "flips": flips}
 
     def batches(self, step):
-        """The step's ``(hr, lr)`` batches: a sized, lazy iterable (``StepBatches``)."""
+        """The step's batches, each what the data set's ``batch`` returns: a sized, lazy iterable (``StepBatches``)."""
         return StepBatches(self.dataset, self.batch_size, self.n_batches, self.plan(step))

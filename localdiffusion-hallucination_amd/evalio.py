@@ -56,6 +56,19 @@ def mnist_pairs(images_u8):
     return 2.0 * (x / 255.0), 2.0 * (lr / 255.0)
 
 
+def lesion_slices(labels):
+    """Indices of the slices of ``labels`` [N, H, W] that hold more than one distinct value -- ``MedSegDataset.__init__``'s
+    filter ``len(np.unique(slice)) > 1`` (data.py:695-698): an all-background slice, or one label throughout, is left out.
+    Host-side; applied once to images and labels before a ``DeviceDataset.seg`` store is built."""
+    a = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if a.ndim != 3:
+        raise ValueError(f"lesion_slices: labels must be [N, H, W], got {a.shape}")
+    flat = a.reshape(a.shape[0], -1)
+    if flat.shape[1] == 0:
+        return np.zeros(0, dtype=np.int64)
+    return np.nonzero((flat != flat[:, :1]).any(axis=1))[0].astype(np.int64)
+
+
 def band_mask(n, h, w, ncols=7):
     """The released script's manual OOD mask: ones in the first ``ncols`` columns (test.py:379-381)."""
     m = torch.zeros(n, 1, h, w)

@@ -26,6 +26,7 @@ import torch
 from torch import nn
 
 from . import _cabi as cabi
+from .dataset import BatchSource
 
 N_CLASSES, HIDDEN, FEATURES = 10, 128, 64 * 7 * 7
 CS = 64                               # channel stride of pool1's output: conv1's 32 channels, the upper 32 zero
@@ -327,17 +328,27 @@ class MnistClassifierTrainer:
         ``torch.save(model.state_dict(), out_path)`` when it is strictly better than the best so far (:114-116); the CSV
         row ``epoch, train_loss, accuracy`` -- where, as in the reference, whose ``loss_lst`` is never cleared (:85, 95,
         100), ``train_loss`` is the mean over ALL steps since the start, not over the epoch.  Losses come to the host once
-        per epoch.  -> {'best_acc', 'best_epoch', 'rows'}."""
+        per epoch.  -> {'best_acc', 'best_epoch', 'rows'}.
+
+        Either may be a ``dataset.BatchSource`` over a ``DeviceDataset.mnist_cls``.  As ``train_batches`` it is asked for
+        ``batches(epoch)`` -- the epoch's shuffle and augmentation -- and walked lazily: batch k + 1 is made after batch k's step
+        was enqueued, and nothing new synchronises inside an epoch.  As ``test_batches`` it is walked as ``batches(0)`` at every
+        epoch, so every epoch tests on the same batches.  ``fit`` over sources is bit-identical to
+        ``fit(lambda e: list(source.batches(e)), list(test.batches(0)), ...)``."""
         best, best_epoch, rows, losses = 0.0, None, [], []
         for e in range(int(epochs)):
             self.model.train()
-            dev_losses = [self.step(x, y) for x, y in (train_batches(e) if callable(train_batches) else train_batches)]
+            if isinstance(train_batches, BatchSource):
+                epoch_batches = train_batches.batches(e)
+            else:
+                epoch_batches = train_batches(e) if callable(train_batches) else train_batches
+            dev_losses = [self.step(x, y) for x, y in epoch_batches]
             if dev_losses:
                 losses += [float(v) for v in torch.stack(dev_losses).cpu().tolist()]
             self.check_labels()
             loss_mean = sum(losses) / len(losses) if losses else float("nan")
             self.model.eval()
-            counts = [self.evaluate(x, y) for x, y in test_batches]
+            counts = [self.evaluate(x, y) for x, y in (test_batches.batches(0) if isinstance(test_batches, BatchSource) else test_batches)]
             total = sum(n for _, n in counts)
             correct = int(torch.stack([c for c, _ in counts]).sum().item()) if counts else 0
             acc = 100 * correct / total if total else 0.0

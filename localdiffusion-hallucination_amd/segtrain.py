@@ -24,6 +24,7 @@ import os
 import torch
 
 from . import _cabi as cabi
+from .dataset import BatchSource
 from .segnet import BN_EPS, SegUNet
 from .weights import SEG_WIDTHS
 
@@ -362,13 +363,23 @@ class SegTrainer:
         ``train_batches`` is a callable epoch -> such a sequence (a new batch composition per epoch, as the reference's
         ``DataLoader(shuffle=True)`` gives); ``out_path`` receives ``torch.save(model.state_dict())`` whenever the mean validation dice improves (the file
         ``checkpoint.load_seg_checkpoint`` and test.py:219 read).  With ``log`` (a directory) train.csv / val.csv are
-        rewritten every epoch.  -> {'best_dice', 'best_epoch', 'train', 'val'}."""
+        rewritten every epoch.  -> {'best_dice', 'best_epoch', 'train', 'val'}.
+
+        Either may be a ``dataset.BatchSource`` over a ``DeviceDataset.seg``.  As ``train_batches`` it is asked for
+        ``batches(epoch)`` -- the epoch's shuffle and augmentation -- and walked lazily: batch k + 1 is made after batch k's step
+        was enqueued, and nothing new synchronises inside an epoch.  As ``val_batches`` it is walked as ``batches(0)`` at every
+        epoch, so every epoch validates on the same batches.  ``fit`` over sources is bit-identical to
+        ``fit(lambda e: list(source.batches(e)), list(val.batches(0)), ...)``."""
         best, best_epoch, train_rows, val_rows = 0.0, None, [], []
         for e in range(int(epochs)):
             self.net.train()
-            losses = [self.step(x, t) for x, t in (train_batches(e) if callable(train_batches) else train_batches)]
+            if isinstance(train_batches, BatchSource):
+                epoch_batches = train_batches.batches(e)
+            else:
+                epoch_batches = train_batches(e) if callable(train_batches) else train_batches
+            losses = [self.step(x, t) for x, t in epoch_batches]
             train_rows.append((e, float(torch.stack(losses).mean()) if losses else float("nan")))
-            scores = [self.evaluate(x, t) for x, t in val_batches]
+            scores = [self.evaluate(x, t) for x, t in (val_batches.batches(0) if isinstance(val_batches, BatchSource) else val_batches)]
             dice = sum(s[0] for s in scores) / max(1, len(scores))
             bce = sum(s[1] for s in scores) / max(1, len(scores))
             val_rows.append((e, dice, bce))
