@@ -587,11 +587,29 @@ int ld_seg_loss(const float* logits, const float* target, double* work, float* o
 /* outc backward: dw [C] = sum_p dz[p] x[p, c], db [1] = sum dz, dx [M, C] = dz[p] w[c].  C a multiple of 64. */
 int ld_seg_head_backward(const float* dz, const float* x, const float* w, double* work, float* dw, float* db, float* dx,
                          int64_t M, int C, void* stream);
-/* torch.optim.Adam's update (no weight decay, no amsgrad) of one parameter tensor seen as [d0][d1][d2] (contiguous, m
- * and v alike), whose gradient element sits at i0 s0 + i1 s1 + i2 s2 of grad.  step_size = lr / (1 - beta1^t) and
- * bc2_sqrt = sqrt(1 - beta2^t) come from the host in double; 1 - beta is rounded to fp32 once, as torch does. */
-int ld_seg_adam(float* param, const float* grad, float* m, float* v, int d0, int d1, int d2, int64_t s0, int64_t s1,
-                int64_t s2, double beta1, double beta2, double eps, double step_size, double bc2_sqrt, void* stream);
+/* torch.optim.Adam's update (no weight decay, no amsgrad) of `count` parameter tensors, 1 .. LD_SEG_ADAM_MAX, in
+ * ceil(count / LD_SEG_ADAM_GROUP) launches: a group's table travels by value as the kernel argument (152-byte entries, 16
+ * within the 4 KB argument block); nothing is allocated, and the whole table is validated before the first launch.  Each
+ * tensor is seen as [d0][d1][d2] (param, m, v contiguous); its gradient element sits at i0 gs0 + i1 gs1 + i2 gs2 of grad;
+ * the updated value is also written to mirror0 / mirror1 (or NULL) at off + i0 s0 + i1 s1 + i2 s2 as ld_seg_permute3
+ * would: the kernel-layout weight copies stay current without a repack.  step_size = lr / (1 - beta1^t) and bc2_sqrt =
+ * sqrt(1 - beta2^t) come from the host in double; 1 - beta is rounded to fp32 once, as torch does. */
+#define LD_SEG_ADAM_GROUP 16
+#define LD_SEG_ADAM_MAX 1024
+typedef struct ld_seg_adam_tensor {
+  float* param;
+  const float* grad;
+  float* m;
+  float* v;
+  int32_t d0, d1, d2;
+  int64_t gs0, gs1, gs2;
+  float* mirror0;
+  int64_t m0_off, m0_s0, m0_s1, m0_s2;
+  float* mirror1;
+  int64_t m1_off, m1_s0, m1_s1, m1_s2;
+} ld_seg_adam_tensor;
+int ld_seg_adam(const ld_seg_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
+                double bc2_sqrt, void* stream);
 /* out[off + i0 s0 + i1 s1 + i2 s2] = in[(i0 d1 + i1) d2 + i2]: the weight layouts of the training step from the
  * parameters' own (OIHW -> OHWI; OIHW -> the data gradient's [Cin][2 - ky][2 - kx][Cout] with a negative stride). */
 int ld_seg_permute3(const float* in, float* out, int d0, int d1, int d2, int64_t off, int64_t s0, int64_t s1, int64_t s2,
@@ -732,7 +750,7 @@ int ld_clf_decide(const float* pred_score, float threshold, int32_t* decision, i
  * cross-entropy (mean), Adam.  fp32, activations NHWC.  conv2 and its two gradients are ld_pc_conv / ld_seg_wgrad launches
  * on a pooled map that carries conv1's 32 channels with a stride of 64 (the upper 32 stay zero); fc1 reads the features in
  * NHWC order (y, x, c), its weight repacked from the reference's (c, y, x).  Every reduction adds in a fixed order (no
- * floating-point atomics). */
+ * floating-point atomics).  The optimiser step is ld_seg_adam, whose mirrors keep the repacked weights current. */
 /* conv1 + bias + ReLU + MaxPool2d(2): x [B, 28, 28] (one channel), w [32][9], bias [32] -> out [B, 14, 14] pixels of 64
  * floats (only the first 32 are written) and idx [B, 14, 14, 32] (or NULL): the position 0..3 of the first maximum of each
  * 2x2 window in row-major order. */
@@ -763,24 +781,6 @@ int ld_mc_small_grads(const float* dz, const float* h, const float* dh, const fl
 int64_t ld_mc_conv1_wgrad_work_floats(int B);
 int ld_mc_conv1_wgrad(const float* x, const float* p1, const float* dp1, const unsigned char* idx, float* work, float* gw,
                       float* gb, int B, void* stream);
-/* ld_seg_adam's update over up to LD_MC_ADAM_MAX tensors in one launch.  Each is seen as [d0][d1][d2] (param, m, v
- * contiguous); its gradient element sits at i0 gs0 + i1 gs1 + i2 gs2 of grad; the updated value is also written to
- * mirror0 / mirror1 (or NULL) at off + i0 s0 + i1 s1 + i2 s2: the kernel-layout copies of the weight. */
-#define LD_MC_ADAM_MAX 8
-typedef struct ld_mc_adam_tensor {
-  float* param;
-  const float* grad;
-  float* m;
-  float* v;
-  int32_t d0, d1, d2;
-  int64_t gs0, gs1, gs2;
-  float* mirror0;
-  int64_t m0_off, m0_s0, m0_s1, m0_s2;
-  float* mirror1;
-  int64_t m1_off, m1_s0, m1_s1, m1_s2;
-} ld_mc_adam_tensor;
-int ld_mc_adam(const ld_mc_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
-               double bc2_sqrt, void* stream);
 
 /* ---- training the denoiser, first slice (backward half): csrc/denoiser_grad.hip ----------------------------
  * The gradient of the training loss with respect to the denoiser's output, and the pieces of a trainable ResnetBlock

@@ -76,7 +76,7 @@ class ClfResizeArgs(C.Structure):
                 ("std", f32 * 3), ("pred", vp), ("threshold", f32), ("decision", vp), ("n_decision", i32)]
 
 
-class McAdamTensor(C.Structure):
+class SegAdamTensor(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("m", vp), ("v", vp), ("d0", i32), ("d1", i32), ("d2", i32), ("gs0", i64),
                 ("gs1", i64), ("gs2", i64), ("mirror0", vp), ("m0_off", i64), ("m0_s0", i64), ("m0_s1", i64), ("m0_s2", i64),
                 ("mirror1", vp), ("m1_off", i64), ("m1_s0", i64), ("m1_s1", i64), ("m1_s2", i64)]
@@ -98,6 +98,7 @@ class DsRow(C.Structure):
 
 
 DS_MIN_PARTS = 16      # LD_DS_MIN_PARTS
+SEG_ADAM_GROUP, SEG_ADAM_MAX = 16, 1024     # LD_SEG_ADAM_GROUP, LD_SEG_ADAM_MAX
 DN_OPT_CHUNK, DN_OPT_ADAM, DN_OPT_MAX_WORLD = 4096, 1, 64     # LD_DN_OPT_CHUNK, LD_DN_OPT_ADAM, LD_DN_OPT_MAX_WORLD
 
 # name -> (restype, argtypes); must list every function include/localdiff_hip.h declares
@@ -197,8 +198,7 @@ _SIGS = {
     "ld_seg_cat_d2s_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_seg_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, vp]),
     "ld_seg_head_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, vp]),
-    "ld_seg_adam": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, C.c_double, C.c_double, C.c_double,
-                    C.c_double, C.c_double, vp]),
+    "ld_seg_adam": (C.c_int, [C.POINTER(SegAdamTensor), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ld_seg_permute3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, vp]),
     "ld_pc_conv": (C.c_int, [C.POINTER(PcConvArgs), vp]),
     "ld_pc_stem": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
@@ -228,7 +228,6 @@ _SIGS = {
     "ld_mc_small_grads": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ld_mc_conv1_wgrad_work_floats": (i64, [C.c_int]),
     "ld_mc_conv1_wgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
-    "ld_mc_adam": (C.c_int, [C.POINTER(McAdamTensor), C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ld_p_losses_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, vp, C.c_int, i64, C.c_int, vp]),
     "ld_p_losses_grad_scaled": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, C.c_int, i64, C.c_int, vp]),
     "ld_dn_gn_work_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),

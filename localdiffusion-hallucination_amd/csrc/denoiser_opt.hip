@@ -12,7 +12,7 @@
 // waves in order, one partial per workgroup, and a second launch of one workgroup adds the partials the same way (thread t
 // takes partials t, t + 256, .. in index order, then the tree and the waves): an order that depends on the sizes alone.  No
 // atomics, nothing allocates, the norm never leaves the device: the step reads it from memory.  Adam's arithmetic is
-// seg_adam_kernel's (segtrain.hip), applied to g * coef.
+// ld_adam_update (adam.hip.h, shared with ld_seg_adam), applied to g * coef.
 //
 // Data-parallel training puts ld_dn_opt_reduce in the place of ld_dn_opt_sqnorm: the ranks all-gather their flat gradients,
 // and one launch adds the copies in rank order (plain fp32, left to right) while it gathers the norm's partials, so every
@@ -25,6 +25,7 @@
 // which does not advance on a skip) in the state; ld_dn_opt_step_scaled is the step above reading them there.  The host
 // never sees any of it, so a step still does not wait for the GPU.
 #include "common.hip.h"
+#include "adam.hip.h"
 #include "dn_common.hip.h"
 
 namespace {
@@ -106,15 +107,10 @@ struct OptScalars {
   int ema_mode;
 };
 
-// torch.optim.Adam on g * coef (seg_adam_kernel's arithmetic): p, m, v are updated in place
+// torch.optim.Adam on g * coef (ld_seg_adam's arithmetic): p, m, v are updated in place
 __device__ __forceinline__ void opt_adam(float& p, float g, float& m, float& v, float coef, const OptScalars& s) {
   g = g * coef;                                                   // clip_grad_norm_: g.mul_(clip_coef_clamped)
-  const float mi = m + s.omb1 * (g - m);                          // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = v * s.beta2 + s.omb2 * g * g;                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-  m = mi;
-  v = vi;
-  const float denom = sqrtf(vi) / s.bc2_sqrt + s.eps;
-  p = p + (-s.step_size) * (mi / denom);
+  ld_adam_update(p, g, m, v, s.omb1, s.beta2, s.omb2, s.eps, s.step_size, s.bc2_sqrt);
 }
 // ema.lerp_(p, w) as ATen evaluates it: e + w (p - e) below w = 0.5, p - (p - e)(1 - w) from there on (w = 1 gives p)
 __device__ __forceinline__ float opt_lerp(float e, float p, float w) {

@@ -18,9 +18,9 @@
 //   conv1 weight / bias gradient                        mc_conv1_wgrad_kernel: the gradient is non-zero only at the pooled
 //                                                      positions, so it is a gather over the pooled map; fixed slabs of
 //                                                      pixels per workgroup, added in order by mc_conv1_wgrad_final_kernel
-//   Adam                                                mc_adam_kernel: all eight tensors in one launch, reading each
-//                                                      gradient through its kernel layout's strides and writing the
-//                                                      updated value into the kernel-layout copies as well
+//   Adam                                                ld_seg_adam (segtrain.hip): all eight tensors in one launch,
+//                                                      reading each gradient through its kernel layout's strides and
+//                                                      writing the updated value into the kernel-layout copies as well
 //
 // No reduction uses floating-point atomics: two steps from the same state give the same bits.
 #include "common.hip.h"
@@ -312,35 +312,6 @@ __global__ void mc_conv1_wgrad_final_kernel(const float* __restrict__ part, int 
   if (t < 9) gw[c * 9 + t] = s;
   else gb[c] = s;
 }
-
-// ------------------------------------------------------------------------------------------------ Adam over all tensors
-struct McAdamDev {
-  ld_mc_adam_tensor t[LD_MC_ADAM_MAX];
-  long start[LD_MC_ADAM_MAX + 1];
-  int count;
-  float omb1, beta2, omb2, eps, step_size, bc2_sqrt;
-};
-
-// the arithmetic of seg_adam_kernel (torch.optim.Adam, no weight decay, no amsgrad)
-__global__ void mc_adam_kernel(McAdamDev d) {
-  const long gi = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= d.start[d.count]) return;
-  int k = 0;
-  while (gi >= d.start[k + 1]) ++k;
-  const ld_mc_adam_tensor& t = d.t[k];
-  const long i = gi - d.start[k];
-  const long i2 = i % t.d2, r = i / t.d2, i0 = r / t.d1, i1 = r % t.d1;
-  const float g = t.grad[i0 * t.gs0 + i1 * t.gs1 + i2 * t.gs2];
-  const float mi = t.m[i] + d.omb1 * (g - t.m[i]);
-  const float vi = t.v[i] * d.beta2 + d.omb2 * g * g;
-  t.m[i] = mi;
-  t.v[i] = vi;
-  const float denom = sqrtf(vi) / d.bc2_sqrt + d.eps;
-  const float p = t.param[i] + (-d.step_size) * (mi / denom);
-  t.param[i] = p;
-  if (t.mirror0) t.mirror0[t.m0_off + i0 * t.m0_s0 + i1 * t.m0_s1 + i2 * t.m0_s2] = p;
-  if (t.mirror1) t.mirror1[t.m1_off + i0 * t.m1_s0 + i1 * t.m1_s1 + i2 * t.m1_s2] = p;
-}
 }  // namespace
 
 extern "C" int ld_mc_conv1(const float* x, const float* w, const float* bias, float* out, unsigned char* idx, int B,
@@ -449,38 +420,5 @@ extern "C" int ld_mc_conv1_wgrad(const float* x, const float* p1, const float* d
   LD_LAUNCH(mc_conv1_wgrad_kernel, dim3((unsigned)slabs), dim3(256), 0, st, x, p1, dp1, idx, work, npix);
   LD_LAUNCH(mc_conv1_wgrad_final_kernel, dim3(mc_blocks(MC_C1 * 10)), dim3(256), 0, st, (const float*)work, slabs, gw, gb);
   LD_LAUNCH_CHECK("mc_conv1_wgrad");
-  return LD_OK;
-}
-
-extern "C" int ld_mc_adam(const ld_mc_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
-                          double bc2_sqrt, void* stream) {
-  LD_REQUIRE(tensors && count >= 1 && count <= LD_MC_ADAM_MAX, "ld_mc_adam: %d tensors (1..%d)", count, LD_MC_ADAM_MAX);
-  LD_REQUIRE(bc2_sqrt > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "ld_mc_adam: betas / bias correction");
-  McAdamDev d;
-  d.count = count;
-  d.start[0] = 0;
-  for (int k = 0; k < count; ++k) {
-    const ld_mc_adam_tensor& t = tensors[k];
-    LD_REQUIRE(t.d0 > 0 && t.d1 > 0 && t.d2 > 0, "ld_mc_adam: tensor %d has an empty shape", k);
-    LD_REQUIRE(t.param && t.grad && t.m && t.v, "ld_mc_adam: tensor %d has a null pointer", k);
-    LD_REQUIRE(t.gs0 >= 0 && t.gs1 >= 0 && t.gs2 >= 0, "ld_mc_adam: tensor %d has a negative gradient stride", k);
-    auto lowest = [&](int64_t off, int64_t s0, int64_t s1, int64_t s2) {
-      return off + (s0 < 0 ? s0 * (t.d0 - 1) : 0) + (s1 < 0 ? s1 * (t.d1 - 1) : 0) + (s2 < 0 ? s2 * (t.d2 - 1) : 0);
-    };
-    LD_REQUIRE(!t.mirror0 || lowest(t.m0_off, t.m0_s0, t.m0_s1, t.m0_s2) >= 0, "ld_mc_adam: tensor %d: mirror0 index below 0", k);
-    LD_REQUIRE(!t.mirror1 || lowest(t.m1_off, t.m1_s0, t.m1_s1, t.m1_s2) >= 0, "ld_mc_adam: tensor %d: mirror1 index below 0", k);
-    d.t[k] = t;
-    d.start[k + 1] = d.start[k] + (long)t.d0 * t.d1 * t.d2;
-  }
-  LD_REQUIRE((d.start[count] + 255) / 256 < (1L << 31), "ld_mc_adam: %ld elements", d.start[count]);
-  d.omb1 = (float)(1.0 - beta1);
-  d.beta2 = (float)beta2;
-  d.omb2 = (float)(1.0 - beta2);
-  d.eps = (float)eps;
-  d.step_size = (float)step_size;
-  d.bc2_sqrt = (float)bc2_sqrt;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LD_LAUNCH(mc_adam_kernel, dim3(mc_blocks(d.start[count])), dim3(256), 0, st, d);
-  LD_LAUNCH_CHECK("mc_adam");
   return LD_OK;
 }

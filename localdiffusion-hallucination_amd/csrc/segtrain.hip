@@ -15,6 +15,7 @@
 //     maximum in row-major order, ATen's rule) fused with the add of the skip gradient, the concat with depth-to-space and
 //     its split, the loss (BCE-with-logits with pos_weight + one dice term per batch) and dz, the head's dX, Adam.
 #include "common.hip.h"
+#include "adam.hip.h"
 
 namespace {
 typedef __attribute__((ext_vector_type(16))) float sg_f32x16;
@@ -388,21 +389,30 @@ __global__ void seg_head_dx_kernel(const float* __restrict__ dz, const float* __
 }
 
 // ------------------------------------------------------------------------------------------------ optimiser, layouts
-// torch.optim.Adam (no weight decay, no amsgrad), one parameter tensor seen as [d0][d1][d2]; its gradient element sits at
-// i0 s0 + i1 s1 + i2 s2 of grad (the kernels' weight-gradient layouts differ from the parameter's own).  1 - beta is
-// rounded to fp32 from the host's double, as torch rounds the Python scalar (1 - 0.999f is 4.7e-5 off 0.001f)
-__global__ void seg_adam_kernel(float* param, const float* __restrict__ grad, float* m, float* v, long n, int d1, int d2, long s0,
-                                long s1, long s2, float omb1, float beta2, float omb2, float eps, float step_size, float bc2_sqrt) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long i2 = i % d2, r = i / d2;
-  const float g = grad[(r / d1) * s0 + (r % d1) * s1 + i2 * s2];
-  const float mi = m[i] + omb1 * (g - m[i]);                  // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = v[i] * beta2 + omb2 * g * g;               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-  m[i] = mi;
-  v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  param[i] = param[i] + (-step_size) * (mi / denom);
+// torch.optim.Adam (ld_adam_update) over a group of tensors, the table by value as the kernel argument.  Tensor k owns
+// elements [start[k], start[k + 1]) of the launch; its gradient is read through the strides of the weight-gradient layout
+// and the updated value also goes to the mirrors (the kernel-layout copies), both in seg_permute3_kernel's index arithmetic
+struct SgAdamDev {
+  ld_seg_adam_tensor t[LD_SEG_ADAM_GROUP];
+  long start[LD_SEG_ADAM_GROUP + 1];
+  int count;
+  float omb1, beta2, omb2, eps, step_size, bc2_sqrt;
+};
+static_assert(sizeof(SgAdamDev) <= 4096, "a group's table travels by value: the kernel-argument block holds 4 KB");
+
+__global__ void seg_adam_kernel(SgAdamDev d) {
+  const long gi = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= d.start[d.count]) return;
+  int k = 0;
+  while (gi >= d.start[k + 1]) ++k;
+  const ld_seg_adam_tensor& t = d.t[k];
+  const long i = gi - d.start[k];
+  const long i2 = i % t.d2, r = i / t.d2, i0 = r / t.d1, i1 = r % t.d1;
+  float p = t.param[i], m = t.m[i], v = t.v[i];
+  ld_adam_update(p, t.grad[i0 * t.gs0 + i1 * t.gs1 + i2 * t.gs2], m, v, d.omb1, d.beta2, d.omb2, d.eps, d.step_size, d.bc2_sqrt);
+  t.m[i] = m; t.v[i] = v; t.param[i] = p;
+  if (t.mirror0) t.mirror0[t.m0_off + i0 * t.m0_s0 + i1 * t.m0_s1 + i2 * t.m0_s2] = p;
+  if (t.mirror1) t.mirror1[t.m1_off + i0 * t.m1_s0 + i1 * t.m1_s1 + i2 * t.m1_s2] = p;
 }
 
 // out[off + i0 s0 + i1 s1 + i2 s2] = in[(i0 d1 + i1) d2 + i2]
@@ -599,19 +609,37 @@ extern "C" int ld_seg_head_backward(const float* dz, const float* x, const float
   return LD_OK;
 }
 
-extern "C" int ld_seg_adam(float* param, const float* grad, float* m, float* v, int d0, int d1, int d2, int64_t s0, int64_t s1,
-                           int64_t s2, double beta1, double beta2, double eps, double step_size, double bc2_sqrt,
-                           void* stream) {
-  LD_REQUIRE(d0 > 0 && d1 > 0 && d2 > 0, "ld_seg_adam: shape %d x %d x %d", d0, d1, d2);
-  LD_REQUIRE(s0 >= 0 && s1 >= 0 && s2 >= 0, "ld_seg_adam: negative gradient stride");
+extern "C" int ld_seg_adam(const ld_seg_adam_tensor* tensors, int count, double beta1, double beta2, double eps, double step_size,
+                           double bc2_sqrt, void* stream) {
+  LD_REQUIRE(tensors && count >= 1 && count <= LD_SEG_ADAM_MAX, "ld_seg_adam: %d tensors (1..%d)", count, LD_SEG_ADAM_MAX);
   LD_REQUIRE(bc2_sqrt > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
-             "ld_seg_adam: beta1 %g beta2 %g eps %g sqrt(1 - beta2^t) %g", beta1, beta2, eps, bc2_sqrt);
-  LD_REQUIRE(param && grad && m && v, "ld_seg_adam: null pointer");
-  const long n = (long)d0 * d1 * d2;
-  LD_REQUIRE((n + 255) / 256 < (1L << 31), "ld_seg_adam: %ld elements", n);
+             "ld_seg_adam: betas / bias correction: beta1 %g beta2 %g eps %g sqrt(1 - beta2^t) %g", beta1, beta2, eps, bc2_sqrt);
+  for (int k = 0; k < count; ++k) {                            // the whole table first: a refused call has changed nothing
+    const ld_seg_adam_tensor& t = tensors[k];
+    LD_REQUIRE(t.d0 > 0 && t.d1 > 0 && t.d2 > 0, "ld_seg_adam: tensor %d has an empty shape", k);
+    LD_REQUIRE(t.param && t.grad && t.m && t.v, "ld_seg_adam: tensor %d has a null pointer", k);
+    LD_REQUIRE(t.gs0 >= 0 && t.gs1 >= 0 && t.gs2 >= 0, "ld_seg_adam: tensor %d has a negative gradient stride", k);
+    auto lowest = [&](int64_t off, int64_t s0, int64_t s1, int64_t s2) {
+      return off + (s0 < 0 ? s0 * (t.d0 - 1) : 0) + (s1 < 0 ? s1 * (t.d1 - 1) : 0) + (s2 < 0 ? s2 * (t.d2 - 1) : 0);
+    };
+    LD_REQUIRE(!t.mirror0 || lowest(t.m0_off, t.m0_s0, t.m0_s1, t.m0_s2) >= 0, "ld_seg_adam: tensor %d: mirror0 index below 0", k);
+    LD_REQUIRE(!t.mirror1 || lowest(t.m1_off, t.m1_s0, t.m1_s1, t.m1_s2) >= 0, "ld_seg_adam: tensor %d: mirror1 index below 0", k);
+    LD_REQUIRE((long)t.d0 * t.d1 <= ((1L << 31) / LD_SEG_ADAM_GROUP - 1) * 256 / t.d2,     // a group fits the grid's 2^31
+               "ld_seg_adam: tensor %d: %d x %d x %d elements", k, t.d0, t.d1, t.d2);
+  }
+  SgAdamDev d;
+  d.omb1 = (float)(1.0 - beta1); d.beta2 = (float)beta2; d.omb2 = (float)(1.0 - beta2);
+  d.eps = (float)eps; d.step_size = (float)step_size; d.bc2_sqrt = (float)bc2_sqrt;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LD_LAUNCH(seg_adam_kernel, dim3(sg_blocks(n)), dim3(256), 0, st, param, grad, m, v, n, d1, d2, (long)s0, (long)s1, (long)s2,
-            (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)step_size, (float)bc2_sqrt);
+  for (int k0 = 0; k0 < count; k0 += LD_SEG_ADAM_GROUP) {
+    d.count = count - k0 < LD_SEG_ADAM_GROUP ? count - k0 : LD_SEG_ADAM_GROUP;
+    d.start[0] = 0;
+    for (int k = 0; k < d.count; ++k) {
+      d.t[k] = tensors[k0 + k];
+      d.start[k + 1] = d.start[k] + (long)d.t[k].d0 * d.t[k].d1 * d.t[k].d2;
+    }
+    LD_LAUNCH(seg_adam_kernel, dim3(sg_blocks(d.start[d.count])), dim3(256), 0, st, d);
+  }
   LD_LAUNCH_CHECK("seg_adam");
   return LD_OK;
 }

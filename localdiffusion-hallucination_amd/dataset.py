@@ -337,3 +337,11 @@ class BatchSource:
     def batches(self, step):
         """The step's batches, each what the data set's ``batch`` returns: a sized, lazy iterable (``StepBatches``)."""
         return StepBatches(self.dataset, self.batch_size, self.n_batches, self.plan(step))
+
+
+def epoch_batches(batches, epoch=0):
+    """What a trainer's ``fit`` walks: a ``BatchSource``'s lazy ``batches(epoch)``, a callable's ``batches(epoch)``, else the
+    sequence itself.  Evaluation passes no epoch: a source is walked as ``batches(0)`` every time."""
+    if isinstance(batches, BatchSource):
+        return batches.batches(epoch)
+    return batches(epoch) if callable(batches) else batches

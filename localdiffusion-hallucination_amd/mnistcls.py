@@ -20,13 +20,14 @@ Not covered: the commented-out VGG16 variant, augmentations, 16-bit storage, mor
 """
 import csv
 import ctypes as C
-import math
 
 import torch
 from torch import nn
 
 from . import _cabi as cabi
-from .dataset import BatchSource
+from .dataset import epoch_batches
+from .segtrain import RED_WORK_BYTES
+from .strided_adam import StridedAdam
 
 N_CLASSES, HIDDEN, FEATURES = 10, 128, 64 * 7 * 7
 CS = 64                               # channel stride of pool1's output: conv1's 32 channels, the upper 32 zero
@@ -95,7 +96,7 @@ class _Packed:
                       "dp2": torch.empty((B, FEATURES), **f32), "da2": torch.empty((B, 14, 14, 64), **f32),
                       "dp1": torch.empty((B, 14, 14, CS), **f32), "splits2": splits,
                       "wg_work": torch.empty(splits * 64 * 9 * CS, **f32),
-                      "red_work": torch.empty(2048 * 2 * 64, dtype=torch.float64, device=dev),      # LD_SEG_RED_WORK_BYTES
+                      "red_work": torch.empty(RED_WORK_BYTES // 8, dtype=torch.float64, device=dev),
                       "c1_work": torch.empty(int(lib.ld_mc_conv1_wgrad_work_floats(B)), **f32)})
         return p
 
@@ -207,10 +208,12 @@ class MnistClassifierTrainer:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         if not isinstance(model, MnistClassifier):
             raise TypeError("MnistClassifierTrainer trains a MnistClassifier")
-        self.model, self.lr, self.betas, self.eps = model, float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.t = 0
-        self._moments = None
+        self.model, self.adam = model, StridedAdam(lr, betas, eps)
         self._grads = None
+
+    @property
+    def t(self):                  # optimisation steps taken
+        return self.adam.t
 
     # ------------------------------------------------------------------ inputs
     def _label(self, x, label):
@@ -287,25 +290,9 @@ class MnistClassifierTrainer:
         return g["loss"][0].clone(), out
 
     def _adam(self, pk, g):
-        named = list(self.model.named_parameters())
-        if self._moments is None or self._moments[named[0][0]][0].device != pk.dev:
-            self._moments = {n: (torch.zeros_like(prm), torch.zeros_like(prm)) for n, prm in named}
-        self.t += 1
-        b1, b2 = self.betas
-        step_size = self.lr / (1.0 - b1 ** self.t)           # bias corrections in double on the host
-        bc2_sqrt = math.sqrt(1.0 - b2 ** self.t)
-        arr = (cabi.McAdamTensor * len(named))()
         mirrors = {"conv2.weight": pk.conv2_mirrors(), "fc1.weight": (pk.fc1_mirror(),)}
-        for a, (n, prm) in zip(arr, named):
-            (a.d0, a.d1, a.d2), (a.gs0, a.gs1, a.gs2) = self._VIEWS[n]
-            m, v = self._moments[n]
-            a.param, a.grad, a.m, a.v = prm.data_ptr(), g[n].data_ptr(), m.data_ptr(), v.data_ptr()
-            for k, (buf, off, s0, s1, s2) in enumerate(mirrors.get(n, ())):
-                if k == 0:
-                    a.mirror0, a.m0_off, a.m0_s0, a.m0_s1, a.m0_s2 = buf.data_ptr(), off, s0, s1, s2
-                else:
-                    a.mirror1, a.m1_off, a.m1_s0, a.m1_s1, a.m1_s2 = buf.data_ptr(), off, s0, s1, s2
-        cabi.check(cabi.lib().ld_mc_adam(arr, len(named), b1, b2, self.eps, step_size, bc2_sqrt, _st(pk.dev)), "mc_adam")
+        self.adam.step([(n, prm, g[n]) + self._VIEWS[n] + (mirrors.get(n, ()),) for n, prm in self.model.named_parameters()],
+                       pk.dev)
 
     def step(self, x, label):
         """One optimisation step (train_mnist_cls.py:91-96) -> the loss before the step as a device scalar; no host
@@ -338,17 +325,13 @@ class MnistClassifierTrainer:
         best, best_epoch, rows, losses = 0.0, None, [], []
         for e in range(int(epochs)):
             self.model.train()
-            if isinstance(train_batches, BatchSource):
-                epoch_batches = train_batches.batches(e)
-            else:
-                epoch_batches = train_batches(e) if callable(train_batches) else train_batches
-            dev_losses = [self.step(x, y) for x, y in epoch_batches]
+            dev_losses = [self.step(x, y) for x, y in epoch_batches(train_batches, e)]
             if dev_losses:
                 losses += [float(v) for v in torch.stack(dev_losses).cpu().tolist()]
             self.check_labels()
             loss_mean = sum(losses) / len(losses) if losses else float("nan")
             self.model.eval()
-            counts = [self.evaluate(x, y) for x, y in (test_batches.batches(0) if isinstance(test_batches, BatchSource) else test_batches)]
+            counts = [self.evaluate(x, y) for x, y in epoch_batches(test_batches)]
             total = sum(n for _, n in counts)
             correct = int(torch.stack([c for c, _ in counts]).sum().item()) if counts else 0
             acc = 100 * correct / total if total else 0.0

@@ -18,14 +18,14 @@ Not covered: 16-bit storage while training, ``bilinear=True``, more than one cla
 """
 import csv
 import ctypes as C
-import math
 import os
 
 import torch
 
 from . import _cabi as cabi
-from .dataset import BatchSource
+from .dataset import epoch_batches
 from .segnet import BN_EPS, SegUNet
+from .strided_adam import StridedAdam
 from .weights import SEG_WIDTHS
 
 BN_MOMENTUM = 0.1
@@ -49,11 +49,16 @@ class _Conv:
         self.wb = None if first else torch.empty(self.cin * 9 * self.cout, **f32)   # [ci][2-ky][2-kx][co]
         self.gw = torch.empty(self.cout * 9 * self.cin_k, **f32)              # like wf
         self.ggamma, self.gbeta = torch.empty(self.cout, **f32), torch.empty(self.cout, **f32)
+        # the weight seen as [cout][cin][9] in each kernel layout: (buffer, offset, s0, s1, s2); gw has wf's strides.  inc's
+        # first convolution has no wb, and nothing writes lanes cin..63 of its wf: they stay zero
+        self.mirrors = ((self.wf, 0, 9 * self.cin_k, 1, self.cin_k),)
+        if self.wb is not None:
+            self.mirrors += ((self.wb, 8 * self.cout, 1, 9 * self.cout, -self.cout),)
 
 
 class _TrainState:
-    """Per-module training state: kernel-layout weights (repacked after every optimiser step), gradient buffers and the
-    per-(B, H, W) plans with the saved activations."""
+    """Per-module training state: kernel-layout weights (packed here, then kept current by the optimiser's mirrors),
+    gradient buffers and the per-(B, H, W) plans with the saved activations."""
 
     def __init__(self, net, dev):
         for p in list(net.parameters()) + list(net.buffers()):
@@ -69,9 +74,11 @@ class _TrainState:
         self.ups = []
         for u in (net.up1, net.up2, net.up3, net.up4):
             cin, cout = u.up.weight.shape[0], u.up.weight.shape[1]
-            self.ups.append({"m": u.up, "cin": cin, "cout": cout,
-                             "wf": torch.empty(4 * cout * cin, **f32),         # [(p1, p2, c)][ci]: the GEMM's OHWI weight
-                             "wb": torch.empty(cin * 4 * cout, **f32),         # [ci][(p1, p2, c)]: the data gradient's
+            wf = torch.empty(4 * cout * cin, **f32)                           # [(p1, p2, c)][ci]: the GEMM's OHWI weight
+            wb = torch.empty(cin * 4 * cout, **f32)                           # [ci][(p1, p2, c)]: the data gradient's
+            self.ups.append({"m": u.up, "cin": cin, "cout": cout, "wf": wf, "wb": wb,
+                             # the weight seen as [cin][cout][4] in each layout, as _Conv.mirrors; gw has wf's strides
+                             "mirrors": ((wf, 0, 1, cin, cout * cin), (wb, 0, 4 * cout, 1, cout)),
                              "bias4": torch.empty(4 * cout, **f32),
                              "gw": torch.empty(4 * cout * cin, **f32), "gb": torch.empty(cout, **f32)})
         self.ghw, self.ghb = torch.empty(SEG_WIDTHS[0], **f32), torch.empty(1, **f32)
@@ -84,20 +91,17 @@ class _TrainState:
 
     # ------------------------------------------------------------------ weights in kernel layout
     def pack(self):
+        """Every kernel-layout copy from the parameters' own layout (construction; the optimiser step keeps them current)."""
         lib, st = cabi.lib(), _st(self.dev)
-        for pair in self.convs:
-            for cv in pair:
-                w = cv.conv.weight
-                co, ci, ck = cv.cout, cv.cin, cv.cin_k
-                cabi.check(lib.ld_seg_permute3(w.data_ptr(), cv.wf.data_ptr(), co, ci, 9, 0, 9 * ck, 1, ck, st), "seg_permute3")
-                if cv.wb is not None:
-                    cabi.check(lib.ld_seg_permute3(w.data_ptr(), cv.wb.data_ptr(), co, ci, 9, 8 * co, 1, 9 * co, -co, st),
-                               "seg_permute3")
+        for _, prm, _, dims, _, mirrors in self.named_grads():
+            for buf, off, s0, s1, s2 in mirrors:
+                cabi.check(lib.ld_seg_permute3(prm.data_ptr(), buf.data_ptr(), *dims, off, s0, s1, s2, st), "seg_permute3")
+        self.pack_bias4()
+
+    def pack_bias4(self):
+        """The transposed convolutions' bias repeated for the four (p1, p2): one source element in four places, so no mirror."""
         for u in self.ups:
-            w, ci, co = u["m"].weight, u["cin"], u["cout"]
-            cabi.check(lib.ld_seg_permute3(w.data_ptr(), u["wf"].data_ptr(), ci, co, 4, 0, 1, ci, co * ci, st), "seg_permute3")
-            cabi.check(lib.ld_seg_permute3(w.data_ptr(), u["wb"].data_ptr(), ci, co, 4, 0, 4 * co, 1, co, st), "seg_permute3")
-            u["bias4"].view(4, co).copy_(u["m"].bias.detach().view(1, co).expand(4, co))
+            u["bias4"].view(4, u["cout"]).copy_(u["m"].bias.detach().view(1, u["cout"]).expand(4, u["cout"]))
 
     # ------------------------------------------------------------------ buffers per input shape
     def plan(self, B, H, W):
@@ -233,27 +237,28 @@ class _TrainState:
                                                     prev["gout"].data_ptr(), B, h, wd, blk["cin"], st), "seg_pool_backward")
 
     def named_grads(self):
-        """(parameter name, parameter, gradient buffer, (d0, d1, d2), gradient strides) in ``named_parameters()`` order."""
+        """(parameter name, parameter, gradient buffer, (d0, d1, d2), gradient strides, mirrors) in ``named_parameters()``
+        order: what ``StridedAdam.step`` takes."""
         by_param = {}
+
+        def flat(prm, g):
+            by_param[id(prm)] = (g, (1, 1, prm.numel()), (0, 0, 1), ())
         for pair in self.convs:
             for cv in pair:
-                by_param[id(cv.conv.weight)] = (cv.gw, (cv.cout, cv.cin, 9), (9 * cv.cin_k, 1, cv.cin_k))
-                by_param[id(cv.bn.weight)] = (cv.ggamma, (1, 1, cv.cout), (0, 0, 1))
-                by_param[id(cv.bn.bias)] = (cv.gbeta, (1, 1, cv.cout), (0, 0, 1))
+                by_param[id(cv.conv.weight)] = (cv.gw, (cv.cout, cv.cin, 9), cv.mirrors[0][2:], cv.mirrors)
+                flat(cv.bn.weight, cv.ggamma)
+                flat(cv.bn.bias, cv.gbeta)
         for u in self.ups:
-            ci, co = u["cin"], u["cout"]
-            by_param[id(u["m"].weight)] = (u["gw"], (ci, co, 4), (1, ci, co * ci))
-            by_param[id(u["m"].bias)] = (u["gb"], (1, 1, co), (0, 0, 1))
-        by_param[id(self.net.outc.conv.weight)] = (self.ghw, (1, 1, SEG_WIDTHS[0]), (0, 0, 1))
-        by_param[id(self.net.outc.conv.bias)] = (self.ghb, (1, 1, 1), (0, 0, 1))
+            by_param[id(u["m"].weight)] = (u["gw"], (u["cin"], u["cout"], 4), u["mirrors"][0][2:], u["mirrors"])
+            flat(u["m"].bias, u["gb"])
+        flat(self.net.outc.conv.weight, self.ghw)
+        flat(self.net.outc.conv.bias, self.ghb)
         return [(n, prm) + by_param[id(prm)] for n, prm in self.net.named_parameters()]
 
     def grads_own_layout(self):
         out = {}
-        for name, prm, g, dims, strides in self.named_grads():
+        for name, prm, g, dims, strides, _ in self.named_grads():
             out[name] = torch.as_strided(g, dims, strides).reshape(prm.shape).clone()
-            if out[name].shape != prm.shape:
-                raise RuntimeError(name)
         return out
 
 
@@ -298,10 +303,12 @@ class SegTrainer:
         if net.compute_dtype != "fp32":
             raise ValueError(f"SegTrainer runs in fp32 only (compute_dtype {net.compute_dtype!r}); 16-bit storage while "
                              "training is not covered")
-        self.net, self.lr, self.betas, self.eps = net, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.net, self.adam = net, StridedAdam(lr, betas, eps)
         self.pos_weight, self.dice_eps = float(pos_weight), float(dice_eps)
-        self.t = 0
-        self._moments = None
+
+    @property
+    def t(self):                  # optimisation steps taken
+        return self.adam.t
 
     def _target(self, x, target):
         if tuple(target.shape) != (x.shape[0], 1, x.shape[2], x.shape[3]):
@@ -327,19 +334,8 @@ class SegTrainer:
         """One optimisation step -> the loss (before the step) as a device scalar; no host synchronisation."""
         st = self._forward_backward(x, target, update_running=True)
         loss = st.loss_out[0].clone()
-        grads = st.named_grads()
-        if self._moments is None:
-            self._moments = {n: (torch.zeros_like(prm), torch.zeros_like(prm)) for n, prm, *_ in grads}
-        self.t += 1
-        b1, b2 = self.betas
-        step_size = self.lr / (1.0 - b1 ** self.t)           # bias corrections in double on the host
-        bc2_sqrt = math.sqrt(1.0 - b2 ** self.t)
-        lib, stream = cabi.lib(), _st(st.dev)
-        for n, prm, g, dims, strides in grads:
-            m, v = self._moments[n]
-            cabi.check(lib.ld_seg_adam(prm.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), *dims, *strides, b1, b2,
-                                       self.eps, step_size, bc2_sqrt, stream), "seg_adam")
-        st.pack()
+        self.adam.step(st.named_grads(), st.dev)             # its mirrors keep wf / wb current: no repack
+        st.pack_bias4()
         self.net._prep, self.net._plans = None, {}          # eval-mode cache: repack on next use
         return loss
 
@@ -373,13 +369,9 @@ class SegTrainer:
         best, best_epoch, train_rows, val_rows = 0.0, None, [], []
         for e in range(int(epochs)):
             self.net.train()
-            if isinstance(train_batches, BatchSource):
-                epoch_batches = train_batches.batches(e)
-            else:
-                epoch_batches = train_batches(e) if callable(train_batches) else train_batches
-            losses = [self.step(x, t) for x, t in epoch_batches]
+            losses = [self.step(x, t) for x, t in epoch_batches(train_batches, e)]
             train_rows.append((e, float(torch.stack(losses).mean()) if losses else float("nan")))
-            scores = [self.evaluate(x, t) for x, t in (val_batches.batches(0) if isinstance(val_batches, BatchSource) else val_batches)]
+            scores = [self.evaluate(x, t) for x, t in epoch_batches(val_batches)]
             dice = sum(s[0] for s in scores) / max(1, len(scores))
             bce = sum(s[1] for s in scores) / max(1, len(scores))
             val_rows.append((e, dice, bce))

@@ -284,31 +284,82 @@ def test_loss_and_head_backward(B, H):
     assert rel_err(to_nchw(dx), gx) <= TOL
 
 
+def adam_call(entries, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """One ld_seg_adam call at step t over (param, grad, m, v, dims, grad strides, mirrors) entries."""
+    arr = (cabi.SegAdamTensor * len(entries))()
+    for a, (p, g, m, v, dims, gs, mirrors) in zip(arr, entries):
+        a.param, a.grad, a.m, a.v = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+        (a.d0, a.d1, a.d2), (a.gs0, a.gs1, a.gs2) = dims, gs
+        for k, (buf, off, s0, s1, s2) in enumerate(mirrors):
+            if k == 0:
+                a.mirror0, a.m0_off, a.m0_s0, a.m0_s1, a.m0_s2 = buf.data_ptr(), off, s0, s1, s2
+            else:
+                a.mirror1, a.m1_off, a.m1_s0, a.m1_s1, a.m1_s2 = buf.data_ptr(), off, s0, s1, s2
+    cabi.check(cabi.lib().ld_seg_adam(arr, len(entries), b1, b2, eps, lr / (1.0 - b1 ** t), float(np.sqrt(1.0 - b2 ** t)), st()),
+               "seg_adam")
+
+
 def test_adam_three_steps_against_torch_optim():
-    """allclose(rtol=2.4e-7, atol=1e-8): two ulps of the parameter plus 1e-5 of lr.  One tensor in a convolution's layouts
-    (parameter OIHW, gradient OHWI), one flat."""
-    lib = cabi.lib()
-    co, ci = 8, 5
+    """allclose(rtol=2.4e-7, atol=1e-8): two ulps of the parameter plus 1e-5 of lr.  One call over two tensors: one in a
+    convolution's layouts (parameter OIHW, gradient OHWI) with two mirrors -- OHWI with the input channels padded from 5 to
+    8 (pre-zeroed) and the data gradient's flipped, transposed layout (negative stride, offset 8 co) -- and one flat.  The
+    mirrors are bitwise what ld_seg_permute3 makes of the updated parameter."""
+    co, ci, cp = 8, 5, 8
     p_conv, p_flat = rnd((co, ci, 3, 3), 23), rnd((300,), 24)
     theirs = [p_conv.clone().requires_grad_(True), p_flat.clone().requires_grad_(True)]
     opt = torch.optim.Adam(theirs, lr=1e-3)
     mine = [p_conv.to(DEV), p_flat.to(DEV)]
     mom = [(torch.zeros_like(p), torch.zeros_like(p)) for p in mine]
+    wf, wb = torch.zeros(co * 9 * cp, device=DEV), torch.zeros(ci * 9 * co, device=DEV)
+    mirrors = ((wf, 0, 9 * cp, 1, cp), (wb, 8 * co, 1, 9 * co, -co))
     for t in range(1, 4):
         grads = [rnd((co, ci, 3, 3), 30 + t) * 10.0 ** (-t), rnd((300,), 40 + t)]
         for p, g in zip(theirs, grads):
             p.grad = g.clone()
         opt.step()
-        step_size, bc2 = 1e-3 / (1.0 - 0.9 ** t), float(np.sqrt(1.0 - 0.999 ** t))
         g_ohwi = grads[0].permute(0, 2, 3, 1).contiguous().to(DEV)
-        cabi.check(lib.ld_seg_adam(mine[0].data_ptr(), g_ohwi.data_ptr(), mom[0][0].data_ptr(), mom[0][1].data_ptr(), co, ci, 9,
-                                   9 * ci, 1, ci, 0.9, 0.999, 1e-8, step_size, bc2, st()), "seg_adam")
         g_flat = grads[1].to(DEV)
-        cabi.check(lib.ld_seg_adam(mine[1].data_ptr(), g_flat.data_ptr(), mom[1][0].data_ptr(), mom[1][1].data_ptr(), 1, 1, 300,
-                                   0, 0, 1, 0.9, 0.999, 1e-8, step_size, bc2, st()), "seg_adam")
+        adam_call([(mine[0], g_ohwi, *mom[0], (co, ci, 9), (9 * ci, 1, ci), mirrors),
+                   (mine[1], g_flat, *mom[1], (1, 1, 300), (0, 0, 1), ())], t)
     for m, th in zip(mine, theirs):
         assert torch.allclose(m.cpu(), th.detach(), rtol=2.4e-7, atol=1e-8), float((m.cpu() - th.detach()).abs().max())
         assert not torch.equal(m.cpu(), p_conv if m.dim() == 4 else p_flat)
+    for buf, off, *strides in mirrors:
+        assert torch.equal(buf, permute3(mine[0], buf.numel(), (co, ci, 9), off, strides))
+    assert torch.equal(wf.view(co, 9, cp)[:, :, :ci].cpu(), mine[0].cpu().permute(0, 2, 3, 1).reshape(co, 9, ci))
+    assert not wf.view(co, 9, cp)[:, :, ci:].any()                 # the padded lanes are still zero
+
+
+def test_adam_groups_are_the_same_update_as_one_tensor_per_call():
+    """LD_SEG_ADAM_GROUP + 1 tensors in one call (two launches; sizes across the 256-thread block edges, one [3][5][7] with
+    a permuted gradient) against clones updated one tensor per call: the arithmetic is per element, so bitwise."""
+    sizes = [1, 255, 256, 257, (3, 5, 7)] + [2 + 37 * k for k in range(cabi.SEG_ADAM_GROUP - 4)]
+    assert len(sizes) == cabi.SEG_ADAM_GROUP + 1
+
+    def entries():
+        out = []
+        for k, n in enumerate(sizes):
+            dims = n if isinstance(n, tuple) else (1, 1, n)
+            numel = dims[0] * dims[1] * dims[2]
+            g = rnd((numel,), 500 + k).to(DEV)
+            gs = (1, 21, 3) if isinstance(n, tuple) else (0, 0, 1)      # [3][5][7] read from a [5][7][3] buffer
+            out.append((rnd((numel,), 400 + k).to(DEV), g, torch.zeros(numel, device=DEV), torch.zeros(numel, device=DEV), dims,
+                        gs, ()))
+        return out
+    together, apart = entries(), entries()
+    for t in (1, 2):
+        adam_call(together, t)
+        for e in apart:
+            adam_call([e], t)
+    for k, (a, b) in enumerate(zip(together, apart)):
+        for x, y, what in zip(a[:4], b[:4], ("param", "grad", "m", "v")):
+            assert torch.equal(x, y), (k, what)
+        assert not torch.equal(a[0].cpu(), rnd((a[0].numel(),), 400 + k))
+    # the permuted gradient was read through its strides: the first step's m is (1 - beta1) g
+    g357 = together[4][1].view(5, 7, 3).permute(2, 0, 1).reshape(-1)
+    m1 = torch.zeros_like(g357)
+    adam_call([(together[4][0].clone(), together[4][1], m1, torch.zeros_like(g357), (3, 5, 7), (1, 21, 3), ())], 1)
+    assert torch.equal(m1, g357 * float(np.float32(1.0 - 0.9)))
 
 
 # ------------------------------------------------------------------------------------------------ whole net
@@ -399,6 +450,48 @@ def test_six_adam_steps_follow_the_fp64_run():
     print(f"six steps: losses {['%.5f' % l for l in losses]}, |err| to fp64 {['%.1e' % e for e in errs]} (bound {bound:.1e})")
     assert all(np.isfinite(losses)) and max(errs) <= bound and losses[-1] < 0.8 * losses[0]
     assert tr.t == 6 and int(net.inc.double_conv[1].num_batches_tracked) == 6
+
+
+def packed_copies(state):
+    out = {}
+    for i, pair in enumerate(state.convs):
+        for j, cv in enumerate(pair):
+            out[f"conv {i}.{j} wf"] = cv.wf
+            if cv.wb is not None:
+                out[f"conv {i}.{j} wb"] = cv.wb
+    for i, u in enumerate(state.ups):
+        out.update({f"up {i} {k}": u[k] for k in ("wf", "wb", "bias4")})
+    return out
+
+
+def assert_packed_weights_are_current(net):
+    """Every kernel-layout copy equals a repack from the parameters, bit for bit; inc's padded lanes are zero."""
+    state = net._train
+    kept = {k: v.clone() for k, v in packed_copies(state).items()}
+    assert len(kept) == 18 + 17 + 4 * 3
+    state.pack()
+    for k, v in packed_copies(state).items():
+        assert torch.equal(v, kept[k]), k
+    inc = state.convs[0][0]
+    assert inc.cin_k == 64 and not inc.wf.view(inc.cout, 9, 64)[:, :, inc.cin:].any()
+    assert torch.equal(inc.wf.view(inc.cout, 9, 64)[:, :, :inc.cin],
+                       inc.conv.weight.detach().permute(0, 2, 3, 1).reshape(inc.cout, 9, inc.cin))
+
+
+def test_steps_keep_the_packed_weights_current():
+    """No repack follows a step: after two of them every wf / wb / bias4 is what pack() makes of the parameters, and a fresh
+    module loaded from state_dict() (packed at construction) gives the same train-mode logits."""
+    g, sd, batches = g19()
+    x, t = batches[0][0].to(DEV), batches[0][1].to(DEV)
+    net = g19_net(sd)
+    tr = ldh.SegTrainer(net)
+    tr.step(x, t)
+    tr.step(x, t)
+    fresh = ldh.SegUNet()
+    fresh.load_state_dict({k: v.detach().cpu().clone() for k, v in net.state_dict().items()})
+    logits = net(x)
+    assert torch.equal(fresh.to(DEV).train()(x), logits)
+    assert_packed_weights_are_current(net)
 
 
 def test_train_mode_forward_equals_the_trainers_forward():
@@ -492,6 +585,7 @@ def test_three_channels_and_a_non_square_input_against_fp64():
     assert max(rel.values()) <= loose, (max(rel, key=rel.get), max(rel.values()))
     before = net.inc.double_conv[0].weight.detach().clone()
     tr.step(x.to(DEV), t.to(DEV))
+    assert_packed_weights_are_current(net)                      # cin = 3 padded to 64: the mirror writes 3 lanes of 64
     moved = (net.inc.double_conv[0].weight.detach() - before).cpu()
     g0 = grads64["inc.double_conv.0.weight"]
     big = g0.abs() > 1e-2 * g0.abs().max()                      # Adam's first step: -lr g / (|g| + eps), about -lr sign(g)

@@ -2,6 +2,7 @@
 (tests/segtrain_ref.py) in fp64 against the reference's own fp64 run (golden G19), argument validation of every new
 entry point, SegTrainer's refusals and its epoch bookkeeping with the GPU calls stubbed, and the weight-gradient
 kernel's matrix-core instruction in the compiled code."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -103,6 +104,17 @@ def test_adam_restatement_matches_torch_optim():
 def test_argument_validation_of_every_new_entry_point_needs_no_gpu():
     lib = cabi.lib()
     one = 4096        # a non-null "pointer": validation happens before any use
+
+    def adam(count=None, beta1=0.9, bc2_sqrt=0.03, second=None, **fields):
+        """ld_seg_adam on a table of valid [2][2][2] entries (one, or two with ``second``) with the given fields changed."""
+        arr = (cabi.SegAdamTensor * 2)()
+        for a, changed in zip(arr, (fields, second or {})):
+            a.param = a.grad = a.m = a.v = one
+            a.d0 = a.d1 = a.d2 = 2
+            for k, v in changed.items():
+                setattr(a, k, v)
+        n = (2 if second else 1) if count is None else count
+        return lib.ld_seg_adam(arr, n, beta1, 0.999, 1e-8, 1e-3, bc2_sqrt, None)
     bad = [
         ("ld_seg_wgrad", lambda: lib.ld_seg_wgrad(one, one, one, one, 1, 16, 16, 48, 64, 3, 1, None), b"Cin"),
         ("ld_seg_wgrad", lambda: lib.ld_seg_wgrad(one, one, one, one, 1, 16, 16, 64, 64, 2, 1, None), b"ksize"),
@@ -121,8 +133,16 @@ def test_argument_validation_of_every_new_entry_point_needs_no_gpu():
         ("ld_seg_loss", lambda: lib.ld_seg_loss(one, one, one, one, None, 0, 10.0, 1e-5, None), b"0 logits"),
         ("ld_seg_loss", lambda: lib.ld_seg_loss(one, None, one, one, None, 16, 10.0, 1e-5, None), b"null"),
         ("ld_seg_head_backward", lambda: lib.ld_seg_head_backward(one, one, one, one, one, one, one, 16, 60, None), b"C 60"),
-        ("ld_seg_adam", lambda: lib.ld_seg_adam(one, one, one, one, 0, 1, 4, 0, 0, 1, 0.9, 0.999, 1e-8, 1e-3, 0.03, None), b"shape"),
-        ("ld_seg_adam", lambda: lib.ld_seg_adam(one, one, one, one, 1, 1, 4, 0, 0, 1, 0.9, 0.999, 1e-8, 1e-3, 0.0, None), b"beta"),
+        ("ld_seg_adam", lambda: adam(count=0), b"tensors"),
+        ("ld_seg_adam", lambda: adam(count=cabi.SEG_ADAM_MAX + 1), b"tensors"),
+        ("ld_seg_adam", lambda: adam(d0=0), b"empty shape"),
+        ("ld_seg_adam", lambda: adam(param=None), b"null"),
+        ("ld_seg_adam", lambda: adam(gs1=-1), b"negative gradient stride"),
+        ("ld_seg_adam", lambda: adam(mirror0=one, m0_s2=-1), b"mirror0"),
+        ("ld_seg_adam", lambda: adam(mirror1=one, m1_off=3, m1_s0=-4), b"mirror1"),
+        ("ld_seg_adam", lambda: adam(beta1=1.5), b"betas"),
+        ("ld_seg_adam", lambda: adam(bc2_sqrt=0.0), b"betas"),
+        ("ld_seg_adam", lambda: adam(second=dict(d2=0)), b"tensor 1 has an empty shape"),      # the whole table, not the first entry
         ("ld_seg_permute3", lambda: lib.ld_seg_permute3(one, one, 2, 2, 9, 0, 1, 18, -2, None), b"negative"),
         ("ld_seg_permute3", lambda: lib.ld_seg_permute3(one, one, 2, 0, 9, 0, 1, 18, 2, None), b"shape"),
     ]
@@ -136,6 +156,22 @@ def test_argument_validation_of_every_new_entry_point_needs_no_gpu():
     assert lib.ld_seg_wgrad_splits(32, 256, 256, 64, 64, 3) == 228
     assert lib.ld_seg_wgrad_splits(2, 16, 16, 1024, 1024, 3) == 1
     assert 1 <= lib.ld_seg_wgrad_splits(1, 16, 16, 64, 64, 3) <= 8        # never more splits than chunks of 32 pixels
+
+
+def test_struct_layout_matches_the_header():
+    src = open(os.path.join(ROOT, "include", "localdiff_hip.h")).read()
+    body = re.search(r"typedef struct ld_seg_adam_tensor \{(.*?)\} ld_seg_adam_tensor;", src, flags=re.S).group(1)
+    fields = []
+    for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
+        decl = decl.strip()
+        if decl:
+            names = decl.split(",")
+            fields.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)$", names[0].strip())[0])
+            fields += [n.strip() for n in names[1:]]
+    assert [f[0] for f in cabi.SegAdamTensor._fields_] == fields
+    assert C.sizeof(cabi.SegAdamTensor) == 152                 # the header's "152-byte entry"
+    for name, value in (("GROUP", cabi.SEG_ADAM_GROUP), ("MAX", cabi.SEG_ADAM_MAX)):
+        assert int(re.search(rf"#define LD_SEG_ADAM_{name} (\d+)", src).group(1)) == value
 
 
 def test_reduction_scratch_size_matches_the_header():
