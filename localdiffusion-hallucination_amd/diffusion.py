@@ -12,9 +12,14 @@ BRANCH -> (FUSE) -> JOINT is explicit, and the one flag whose flipped value surv
 ``sample()`` call (``mask_x``) is carried on the object (``_mask_x_get/_mask_x_set``, golden G14).
 No tensor leaves the GPU inside the loop (the reference
 ping-pongs ``.cpu()``/``.to(device)`` every step, :700-708, :865-869), the conditioning encoder
-runs once per phase instead of once per step (its input is constant over t, :434), both branches
+runs once per phase instead of once per step (its input is constant over t, :434), all branches
 are evaluated as ONE batched denoiser call, and the dead OOD-branch evaluation for non-MRI data
 (:704-708) is skipped.  ``np.save`` debugging side effects (:793-794, :866-868) are not reproduced.
+
+One state machine serves every reverse process: ``_branch_phase`` (units of K branches down to the exchange),
+``_fuse_joint`` (fusion step + remaining steps) and ``_gated_joint_steps`` (the classifier gate), ancestral and DDIM
+alike.  ``p_sample_loop`` / ``ddim_sample`` run them over all units on one set of buffers -- a ``[B,1,H,W]`` mask m, the
+reference's two branches, as K = 2 with masks [m, 1 - (m >= 1)] --, ``kmask_branch_units`` / ``kmask_fuse_joint`` per rank.
 
 Noise: ``noise_source='device'`` draws z_t with the counter-based generator on the GPU
 (``ld_randn``); ``'host'`` uploads the same stream from ``rng.py`` (bit-identical to the golden
@@ -430,6 +435,74 @@ class _DdimBranches:
 
 def gd_key(gd):
     return (gd.noise_seed, gd.noise_offset, gd.objective)
+
+
+class _BranchUnits:
+    """Branch-patches [u_lo, u_hi) of a branch phase (unit u = k * B + b: branch k of image b): one denoiser plan for all of
+    them and the (state, prediction) views of every run of units that share k.  ``cond_k`` [K,B,Cc,H,W] is the conditioning
+    per branch (ld_branch_conditions_k), ``m0`` [B,1,H,W] the OOD mask.  Branch 0 is the OOD-style branch: with mask_x its
+    prediction is replaced by the range minimum outside m_0 (ld_mask_out, ddpm.py:698-703) -- or, for the datasets of
+    :704-708, by its conditioning: those units skip the denoiser (the ``n0`` leading rows; their states live outside the plan)."""
+
+    def __init__(self, gd, cond_k, m0, mask_x, u_lo, u_hi):
+        self.gd, self.cond_k, self.m0, self.mask_x, self.u_lo, self.u_hi = gd, cond_k, m0, mask_x, u_lo, u_hi
+        B, (H, W) = cond_k.shape[1], cond_k.shape[3:]
+        n_units = u_hi - u_lo
+        self.replaced = gd._replaced_out(mask_x)
+        self.n0 = max(0, min(u_hi, B) - u_lo) if self.replaced else 0
+        # (a shard without evaluated units has no plan; it walks the loop all the same: that is where `where` is decided)
+        self.plan = gd.model.plan(n_units - self.n0, H, W, table_T=gd.num_timesteps_ori) if n_units > self.n0 else None
+        self.x_skipped = None
+        # runs of units that share k: rows [i0, i1) of the local list <-> images [b0, b1)
+        self.runs, i = [], 0
+        while i < n_units:
+            k, b0 = divmod(u_lo + i, B)
+            j = min(n_units, i + B - b0)
+            self.runs.append((k, i, j, b0, b0 + (j - i)))
+            i = j
+
+    def encode(self):
+        """Evaluate the conditioning encoder for the units the denoiser runs on."""
+        if self.plan is not None:
+            ck = self.cond_k
+            self.plan.cond_in.copy_(ck.reshape(-1, *ck.shape[2:])[self.u_lo + self.n0:self.u_hi])
+            self.plan.run_cond(self.gd._st())
+
+    def load(self, states):
+        """Unit (k, b) starts from ``states[k][b]``.  The skipped units take their slice of ``states[0]`` itself, not a copy:
+        it is stepped in place."""
+        for k, i0, i1, b0, b1 in self.runs:
+            if i1 <= self.n0:
+                self.x_skipped = states[0][b0:b1]
+            else:
+                self.rows(i0, i1)[0].copy_(states[k][b0:b1])
+        self.views = [self.rows(i0, i1) for _, i0, i1, _, _ in self.runs]
+
+    def rows(self, i0, i1):
+        """(state, prediction) views of local rows [i0, i1) (a run never straddles the skipped / evaluated boundary)."""
+        n0 = self.n0
+        if i1 <= n0:
+            return self.x_skipped[i0:i1], self.cond_k[0][self.u_lo + i0:self.u_lo + i1]
+        return self.plan.x_in[i0 - n0:i1 - n0], self.plan.model_out[i0 - n0:i1 - n0]
+
+    def branches(self):
+        """(x_first, x_rest, x0_first, x0_rest) of a phase that holds every unit: what the fusion kernels read."""
+        B = self.cond_k.shape[1]
+        (xf, mf), (xr, mr) = self.rows(0, B), self.rows(B, self.u_hi)
+        return xf, xr, mf, mr
+
+    def evaluate(self, t, lo):
+        """One denoiser evaluation of the units at timestep t, and mask_x on the OOD predictions."""
+        lib, st = cabi.lib(), self.gd._st()
+        if self.plan is not None:
+            self.plan.set_step(t)
+            self.plan.run_main(st)
+        if self.mask_x and not self.replaced:
+            HW = self.m0.shape[2] * self.m0.shape[3]
+            for (k, i0, i1, b0, b1), (_, mv) in zip(self.runs, self.views):
+                if k == 0:
+                    cabi.check(lib.ld_mask_out(mv.data_ptr(), self.m0.data_ptr() + b0 * HW * self.m0.element_size(), lo,
+                                               b1 - b0, self.gd.channels, HW, st), "mask_out")
 
 
 class GaussianDiffusion(nn.Module):
@@ -965,275 +1038,229 @@ class GaussianDiffusion(nn.Module):
         cur.wait_stream(gs)
         return draw + (t_start - t) + n_steps
 
-    # ------------------------------------------------------------------ DDPM loop
-    @torch.inference_mode()
-    def p_sample_loop(self, cond_img, mask, min_max_val, shape, return_all_timesteps=False,
-                      return_all_outputs=False):
-        self._sync_model()
+    # ------------------------------------------------------------------ the pieces every reverse process is made of
+    def _refuse_branch_history(self):
+        """ddpm.py:963 / :1072 stack `imgs`, which holds per-branch lists for every branch step (:865, :1043, :1069):
+        torch.stack raises on them in the reference as well."""
+        raise TypeError("return_all_timesteps is only defined for the single-branch reverse process "
+                        "(the reference's torch.stack(imgs) fails on the per-branch lists, ddpm.py:865,963,1069-1072)")
+
+    def _start(self, shape, gt):
+        """x_T of the WHOLE image batch (every branch of image b starts from x_T[b], ddpm.py:955-957) and the first t: T - 1,
+        or under use_gt (ancestral sampling only) q_sample of ``gt`` at use_gt_timestep and that timestep - 1 (:937-944)."""
         lib, st, dev = cabi.lib(), self._st(), self.device
-        B, C, H, W = shape
-        HW, n = H * W, B * C * H * W
-        lo, hi = float(min_max_val[0]), float(min_max_val[1])
-        T = self.num_timesteps
-        branch, fuse, mask_x = self._flags(mask)
-        obj = cabi.OBJ[self.objective]
-        sched = self._sched_table()
-        cond = cond_img.to(dev, torch.float32).contiguous()
-        if mask is not None:
-            mask = mask.to(dev, torch.float32).contiguous()
-        start_t = T - 1
         x_T = torch.empty(shape, dtype=torch.float32, device=dev)
         self._noise(x_T, 0)
-        if (bool(self.config["start_intermediate"]) or self.start_intermediate) and self.config.get("use_gt", False):
-            t0 = int(self.config["use_gt_timestep"])              # ddpm.py:937-944
-            hr = self.hr.to(dev, torch.float32).contiguous()
-            cabi.check(lib.ld_q_sample(hr.data_ptr(), x_T.data_ptr(), x_T.data_ptr(),
-                                       float(self.sqrt_alphas_cumprod[t0]),
-                                       float(self.sqrt_one_minus_alphas_cumprod[t0]), n, st), "q_sample")
+        start_t = self.num_timesteps - 1
+        if (not self.is_ddim_sampling and (bool(self.config["start_intermediate"]) or self.start_intermediate)
+                and self.config.get("use_gt", False)):
+            t0 = int(self.config["use_gt_timestep"])
+            hr = gt.to(dev, torch.float32).contiguous()
+            cabi.check(lib.ld_q_sample(hr.data_ptr(), x_T.data_ptr(), x_T.data_ptr(), float(self.sqrt_alphas_cumprod[t0]),
+                                       float(self.sqrt_one_minus_alphas_cumprod[t0]), x_T.numel(), st), "q_sample")
             start_t = t0 - 1
-        z = torch.empty(shape, dtype=torch.float32, device=dev)
-        if branch and mask is not None and mask.shape[1] > 1:        # K-mask generalisation
-            if return_all_timesteps:
-                # as for two branches: ddpm.py:963 stacks `imgs`, which holds per-branch lists for every branch step
-                raise TypeError("return_all_timesteps is only defined for the single-branch reverse process "
-                                "(the reference's torch.stack(imgs) fails on the per-branch lists, ddpm.py:865,963)")
-            return self._p_sample_loop_kmask(cond, mask, lo, hi, shape, x_T, z, start_t, fuse, mask_x,
-                                             return_all_outputs=return_all_outputs)
-        x0_buf = torch.empty(shape, dtype=torch.float32, device=dev) if return_all_outputs else None
-        if return_all_timesteps and branch:
-            # ddpm.py:963 stacks `imgs`, which holds [x_out, x_in] lists for every branch step (:865): torch.stack
-            # raises on them in the reference as well
-            raise TypeError("return_all_timesteps is only defined for the single-branch reverse process "
-                            "(the reference's torch.stack(imgs) fails on the per-branch lists, ddpm.py:865,963)")
-        hist_x, hist_x0 = [x_T.clone()] if return_all_timesteps else None, []
-        x0_pair = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(2)] if (return_all_outputs and branch) else None
-        draw = 1
-        t = start_t
-        xs = None
-        gate = bool(self.config.get("classifier", False)) and branch and fuse     # ddpm.py:883
-        if gate:
-            self.call_classifier()
-        x_branchout = None
-        # ---------------- BRANCH phase
-        if branch:
-            assert self.objective == "pred_x0", "branch mode exists only for pred_x0 (ddpm.py:739-749)"
-            assert mask is not None
-            if mask_x:
-                assert len(torch.unique((mask >= 1.0).float())) == 2, "mask should be binary"   # ddpm.py:698
-            lo_clip = 0.5 if self.config["data"] == "mnist" else 0.95
-            cond_out, cond_in = torch.empty_like(cond), torch.empty_like(cond)
-            cabi.check(lib.ld_branch_conditions(cond.data_ptr(), mask.data_ptr(), cond_out.data_ptr(),
-                                                cond_in.data_ptr(), lo_clip, B, cond.shape[1], HW, st), "branch_conditions")
-            replaced = self._replaced_out(mask_x)
-            nb = B if replaced else 2 * B
-            plan = self.model.plan(nb, H, W, table_T=self.num_timesteps_ori)
-            if replaced:
-                plan.cond_in.copy_(cond_in)
-            else:
-                plan.cond_in[:B].copy_(cond_out)
-                plan.cond_in[B:].copy_(cond_in)
-            plan.run_cond(st)
-            # x_out lives in its own buffer when the OOD branch is not evaluated
-            x_in_view = plan.x_in if replaced else plan.x_in[B:]
-            x_out_view = torch.empty(shape, dtype=torch.float32, device=dev) if replaced else plan.x_in[:B]
-            x_out_view.copy_(x_T)
-            x_in_view.copy_(x_T)
-            mo_in = plan.model_out if replaced else plan.model_out[B:]
-            mo_out = cond_out if replaced else plan.model_out[:B]
-            # the steps before the fusion time: the OOD and the IND branch as two concurrent sub-batches (same
-            # draw for both, ld_mask_out folded into the OOD branch's final step)
-            n_plain = (t - int(self.config["start_timestep"])) if fuse else t + 1
-            if (not replaced and self.sub_batches > 1 and (B >= self.min_sub_batch or self._sub_ok(B, H, W))
-                    and self.noise_source == "device"
-                    and not return_all_timesteps and not return_all_outputs and n_plain >= 4
-                    and C == plan.model_out.shape[1] and not self.use_graph):
-                key = (id(plan), "branch", bool(mask_x))
-                if key not in self._subs:
-                    self._subs[key] = _SubBatches(self, plan, 2, shared_noise=True, masked=(0,) if mask_x else (),
-                                                  instance_base=100)
-                if mask_x:
-                    self._subs[key].set_mask(mask)
-                draw = self._subs[key].run(t, n_plain, lo, hi, draw)
-                t -= n_plain
-            while t >= 0:
-                plan.set_step(t)
-                plan.run_main(st)
-                if mask_x and not replaced:
-                    cabi.check(lib.ld_mask_out(mo_out.data_ptr(), mask.data_ptr(), lo, B, C, HW, st), "mask_out")
-                if t > 0:
-                    self._noise(z, draw)
-                    draw += 1
-                if fuse and t <= int(self.config["start_timestep"]):
-                    jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-                    x0f = torch.empty(shape, dtype=torch.float32, device=dev)
-                    if gate:                               # self.x_branchout, ddpm.py:799
-                        m1 = (mask >= 1.0).float()
-                        x_branchout = [x_out_view * m1, x_in_view * (1.0 - m1)]
-                    cabi.check(lib.ld_fuse_ddpm(x_out_view.data_ptr(), x_in_view.data_ptr(), mo_out.data_ptr(),
-                                                mo_in.data_ptr(), mask.data_ptr(), jp.x_in.data_ptr(),
-                                                x0f.data_ptr(), lo, hi, B, C, HW, st), "fuse_ddpm")
-                    self._mask_x_set(False)                # ddpm.py:781
-                    jp.set_step(t)
-                    cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0f.data_ptr(), z.data_ptr(),
-                                                     jp.x_in.data_ptr(), sched.data_ptr(), jp.t_dev.data_ptr(), n, st),
-                               "posterior_step")
-                    if return_all_outputs:
-                        hist_x0.append(x0f.cpu())
-                    if return_all_timesteps:
-                        hist_x.append(jp.x_in.clone())
-                    t -= 1
-                    branch = False
-                    break
-                plan.set_step(t)
-                for bi, (xv, mv) in enumerate(((x_out_view, mo_out), (x_in_view, mo_in))):
-                    cabi.check(lib.ld_ddpm_step(xv.data_ptr(), mv.data_ptr(), z.data_ptr(), xv.data_ptr(),
-                                                cabi.ptr(x0_pair[bi]) if x0_pair else None,
-                                                sched.data_ptr(), plan.t_dev.data_ptr(), lo, hi, obj, n, st), "ddpm_step")
-                if return_all_outputs:                     # branching_out(), ddpm.py:869
-                    hist_x0.append([x0_pair[0].cpu(), x0_pair[1].cpu()])
-                t -= 1
-            if branch:                                     # never fused
-                xs = [x_out_view.clone(), x_in_view.clone()]
-        # ---------------- JOINT phase
-        if xs is None:
-            jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-            if t == start_t:                               # no branch phase ran: start from x_T
-                jp.x_in.copy_(x_T)
-            jp.cond_in.copy_(cond)
-            def after(_t):
-                if return_all_outputs:
-                    hist_x0.append(x0_buf.cpu())
-                if return_all_timesteps:
-                    hist_x.append(jp.x_in.clone())
-            cb = after if (return_all_outputs or return_all_timesteps) else None
-            if gate and x_branchout is not None:
-                jp.run_cond(st)
-                if x0_buf is None:
-                    x0_buf = torch.empty(shape, dtype=torch.float32, device=dev)
-                self._gated_joint_steps(jp, t, lo, hi, z, draw, x0_buf, x_branchout, cond, cond_out, cond_in,
-                                        mask, mask_x, after if (return_all_outputs or return_all_timesteps) else None)
-            else:
-                self.encode_cond(jp, t + 1, x0_buf, cb)
-                self.run_joint_steps(jp, t, t + 1, lo, hi, z, draw, x0_buf=x0_buf, after=cb)
-            ret = jp.x_in.clone()
-        else:
-            ret = xs
-        if return_all_timesteps and not isinstance(ret, list):
-            ret = torch.stack(hist_x, dim=1)
-        start_int = bool(self.config["start_intermediate"]) or self.start_intermediate
-        if (not start_int) and self.branch_out:            # ddpm.py:964-970
-            ret = torch.stack(ret, dim=0) if isinstance(ret, list) else torch.stack((ret, ret), dim=0)
-        if return_all_outputs:
-            return ret, hist_x0, []
-        return ret
+        return x_T, start_t
 
-    def _kmask_setup(self, cond, masks, lo, shape, mask_x):
-        """Conditioning, plan and state / prediction views of a K-branch run (shared by the DDPM and the DDIM loop)."""
-        lib, st, dev = cabi.lib(), self._st(), self.device
-        B, C, H, W = shape
-        K, HW = masks.shape[1], H * W
+    def _reverse_pairs(self, start_t, fuse):
+        """Every reverse step as (t, t_next) -- t_next < 0 marks the last one, the only one without a draw -- and the fusion
+        time: the branches are recomposed at the first step with t <= it (ddpm.py:779, :987, :1021; -1 without fusion)."""
+        if self.is_ddim_sampling:
+            times, pairs = schedule.ddim_time_pairs(self.num_timesteps, self.sampling_timesteps)
+            return pairs, times[-int(self.config["start_timestep"]) - 2] if fuse else -1
+        return [(t, t - 1) for t in range(start_t, -1, -1)], int(self.config["start_timestep"]) if fuse else -1
+
+    def _ddim_scalars(self, t, t_next):
+        a, an = self.alphas_cumprod[t], self.alphas_cumprod[t_next]
+        sigma = self.ddim_sampling_eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()     # ddpm.py:1017-1018
+        return float(an.sqrt()), float((1 - an - sigma ** 2).sqrt()), float(sigma)
+
+    def _ddim_row(self, t, t_next):
+        """{sr, srm1, sab, s1mab, san, c, sigma, last} of one pair: ld_ddim_step's scalars, a row of ld_ddim_step_at's table."""
+        san, c, sigma = (0.0, 0.0, 0.0) if t_next < 0 else self._ddim_scalars(t, t_next)
+        return [float(self.sqrt_recip_alphas_cumprod[t]), float(self.sqrt_recipm1_alphas_cumprod[t]),
+                float(self.sqrt_alphas_cumprod[t]), float(self.sqrt_one_minus_alphas_cumprod[t]), san, c, sigma,
+                1.0 if t_next < 0 else 0.0]
+
+    def _ddim_branches(self, B, H, W, mask_x, pairs, shared=True):
+        return _DdimBranches(self, B, H, W, mask_x, [p[0] for p in pairs], [self._ddim_row(*p) for p in pairs], shared=shared)
+
+    def _reverse_step(self, xv, mv, zz, t, t_next, lo, hi, x0=None):
+        """x_t -> x_{t_next} in place from the prediction ``mv`` with the draw ``zz`` (not read by the last step): the
+        ancestral update (ddpm.py:817-858; ``x0``: where to leave the clamped prediction) or the DDIM one (:1005-1020)."""
+        lib, st, obj = cabi.lib(), self._st(), cabi.OBJ[self.objective]
+        zp = None if t_next < 0 else zz.data_ptr()
+        if self.is_ddim_sampling:
+            sr, srm1, sab, s1mab, san, c, sigma, last = self._ddim_row(t, t_next)
+            cabi.check(lib.ld_ddim_step(xv.data_ptr(), mv.data_ptr(), zp, xv.data_ptr(), sr, srm1, sab, s1mab, san, c, sigma,
+                                        lo, hi, obj, int(last), xv.numel(), st), "ddim_step")
+        else:               # row mode: the kernel gets the step's row of the table and adds the draw iff it gets one
+            sched = self._sched_table()
+            row = sched.data_ptr() + t * sched.stride(0) * sched.element_size()
+            cabi.check(lib.ld_ddpm_step(xv.data_ptr(), mv.data_ptr(), zp, xv.data_ptr(), cabi.ptr(x0), row, None, lo, hi,
+                                        obj, xv.numel(), st), "ddpm_step")
+
+    # ------------------------------------------------------------------ BRANCH phase
+    # SURVEY 8e "Collective": in the reference's fusion mode the exchange sits at t = start_timestep (ddpm.py:779-810,
+    # :1021-1042): every branch contributes its state x_t and its prediction x0_hat, then the remaining steps run on the
+    # recomposed image.  The unit of work before that point is a BRANCH-PATCH u = k * B + b (branch k of image b, the layout
+    # of _BranchUnits' plan); after it, an image.  _branch_phase runs units [u_lo, u_hi) up to the exchange, _fuse_joint
+    # recomposes images and finishes them.  sample() runs both over the full ranges on the same buffers;
+    # dist.sample_kmask_sharded runs them per rank with ONE gather between them (kmask_branch_units / kmask_fuse_joint).
+    def _branch_phase(self, cond, masks, mask_x, fuse, x_T, start_t, lo, hi, z, u_lo, u_hi, x0_units=None, on_step=None,
+                      fast=False):
+        """Units [u_lo, u_hi) of the K-branch reverse process (masks [B,K,H,W]; ddpm.py:672-708, 852-858, 1005-1020) from
+        x_T down to the exchange.  All branches of an image share each step's draw (``z``, drawn for the whole batch).
+        Returns ``(units, where, fused)``: ``where`` = (t -- DDIM: pair index -- of the fusion step, next draw), the states
+        NOT yet stepped there (ddpm.py:779-797 recomposes x_t and x0_hat of the same t) and the fusion step's draw in ``z``;
+        never fused: (-1 -- DDIM: number of pairs --, next draw) and the final states.  ``x0_units`` [n_units,C,H,W]
+        receives every branch step's clamped x0 (``on_step`` runs after each: return_all_outputs, ddpm.py:869).
+        ``fast``: the concurrent sub-batch runners may take the leading steps (_branch_fast_path)."""
+        B, K = masks.shape[:2]
         assert self.objective == "pred_x0", "branch mode exists only for pred_x0 (ddpm.py:739-749)"
         m0 = masks[:, 0:1].contiguous()
         if mask_x:
             assert len(torch.unique((m0 >= 1.0).float())) == 2, "mask should be binary"   # ddpm.py:698
         lo_clip = 0.5 if self.config["data"] == "mnist" else 0.95
-        cond_k = torch.empty((K,) + tuple(cond.shape), dtype=torch.float32, device=dev)
-        cabi.check(lib.ld_branch_conditions_k(cond.data_ptr(), masks.data_ptr(), cond_k.data_ptr(), lo_clip, B,
-                                              cond.shape[1], K, HW, st), "branch_conditions_k")
-        replaced = self._replaced_out(mask_x)
-        nb = (K - 1) * B if replaced else K * B
-        plan = self.model.plan(nb, H, W, table_T=self.num_timesteps_ori)
-        plan.cond_in.copy_((cond_k[1:] if replaced else cond_k).reshape(nb, *cond.shape[1:]))
-        plan.run_cond(st)
-        x_first = torch.empty(shape, dtype=torch.float32, device=dev) if replaced else plan.x_in[:B]
-        x_rest = plan.x_in if replaced else plan.x_in[B:]
-        mo_first = cond_k[0] if replaced else plan.model_out[:B]
-        mo_rest = plan.model_out if replaced else plan.model_out[B:]
-        return plan, m0, cond_k, replaced, x_first, x_rest, mo_first, mo_rest
-
-    def _p_sample_loop_kmask(self, cond, masks, lo, hi, shape, x_T, z, start_t, fuse, mask_x, return_all_outputs=False):
-        """Branch -> fusion -> joint with K >= 2 masks [B,K,H,W] (the reference's loop, ddpm.py:672-708,
-        769-810, 852-858, has K = 2).  Branch 0 is the OOD-style branch (hard-masked conditioning; with mask_x its
-        prediction is replaced by the range minimum outside m_0, or by its conditioning for the datasets of :704-708),
-        branches 1..K-1 are IND-style (conditioning floored at 0.95 / 0.5).  All branches share each step's draw; at
-        t <= start_timestep they are recomposed (x0 = clamp(sum_k x0_k m_k), x_t = first non-zero of x_t,k m_k) and the
-        remaining steps run on the fused image.  Without fusion the K branch states come back as [K,B,C,H,W].
-        ``return_all_outputs``: (ret, x_start_lst, []) -- a K-list of x0 per branch step (ddpm.py:869), the fused /
-        single x0 otherwise (:879, 922).  config['classifier']: the joint steps run under the gate of fusion()
-        (:883-916) with a K-branch redo.  oracle/diffusion_ref.py::p_sample_loop_kmask is the restatement; for K = 2 and
-        m_1 = 1 - (m_0 >= 1) both are bitwise the two-branch path."""
-        lib, st, dev = cabi.lib(), self._st(), self.device
-        B, C, H, W = shape
-        K, HW, n = masks.shape[1], H * W, B * C * H * W
-        sched, obj = self._sched_table(), cabi.OBJ[self.objective]
-        masks = masks.to(dev, torch.float32).contiguous()
-        plan, m0, cond_k, replaced, x_first, x_rest, mo_first, mo_rest = self._kmask_setup(cond, masks, lo, shape, mask_x)
-        x_first.copy_(x_T)
-        x_rest.copy_(x_T.repeat(K - 1, 1, 1, 1))
-        gate = bool(self.config.get("classifier", False)) and fuse
-        if gate:
-            self.call_classifier()
-        hist_x0 = []
-        x0_k = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(K)] if return_all_outputs else None
-        t, draw = start_t, 1
-        fused, kept = False, None
-        while t >= 0:
-            plan.set_step(t)
-            plan.run_main(st)
-            if mask_x and not replaced:
-                cabi.check(lib.ld_mask_out(mo_first.data_ptr(), m0.data_ptr(), lo, B, C, HW, st), "mask_out")
-            if t > 0:
+        cond_k = torch.empty((K,) + tuple(cond.shape), dtype=torch.float32, device=cond.device)
+        cabi.check(cabi.lib().ld_branch_conditions_k(cond.data_ptr(), masks.data_ptr(), cond_k.data_ptr(), lo_clip, B,
+                                                     cond.shape[1], K, cond.shape[2] * cond.shape[3], self._st()),
+                   "branch_conditions_k")
+        bu = _BranchUnits(self, cond_k, m0, mask_x, u_lo, u_hi)
+        bu.encode()
+        bu.load([x_T] * K)
+        ddim = self.is_ddim_sampling
+        pairs, t_fuse = self._reverse_pairs(start_t, fuse)
+        idx = self._branch_fast_path(bu, pairs, t_fuse, lo, hi) if fast else 0
+        draw = 1 + sum(1 for _, t_next in pairs[:idx] if t_next >= 0)
+        zs = [z[b0:b1] for _, _, _, b0, b1 in bu.runs]
+        while idx < len(pairs):
+            t, t_next = pairs[idx]
+            bu.evaluate(t, lo)
+            if t_next >= 0:
                 self._noise(z, draw)
                 draw += 1
-            if fuse and t <= int(self.config["start_timestep"]):
-                jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-                x0f = torch.empty(shape, dtype=torch.float32, device=dev)
-                if gate:                                       # self.x_branchout (ddpm.py:799), one state per branch
-                    bm = (masks >= 1.0).float()
-                    kept = [x_first * bm[:, 0:1]] + [x_rest[(k - 1) * B:k * B] * bm[:, k:k + 1] for k in range(1, K)]
-                cabi.check(lib.ld_fuse_ddpm_k(x_first.data_ptr(), x_rest.data_ptr(), mo_first.data_ptr(), mo_rest.data_ptr(),
-                                              masks.data_ptr(), jp.x_in.data_ptr(), x0f.data_ptr(), lo, hi, B, C, K, HW, st),
-                           "fuse_ddpm_k")
-                self._mask_x_set(False)                    # ddpm.py:781
-                jp.set_step(t)
-                cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0f.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
-                                                 sched.data_ptr(), jp.t_dev.data_ptr(), n, st), "posterior_step")
-                if return_all_outputs:
-                    hist_x0.append(x0f.cpu())
-                t -= 1
-                fused = True
-                break
-            views = [(x_first, mo_first)] + [(x_rest[(k - 1) * B:k * B], mo_rest[(k - 1) * B:k * B]) for k in range(1, K)]
-            for k, (xv, mv) in enumerate(views):               # one shared draw for every branch (ddpm.py:852-858)
-                cabi.check(lib.ld_ddpm_step(xv.data_ptr(), mv.data_ptr(), z.data_ptr(), xv.data_ptr(),
-                                            cabi.ptr(x0_k[k]) if x0_k else None,
-                                            sched.data_ptr(), plan.t_dev.data_ptr(), lo, hi, obj, n, st), "ddpm_step")
-            if return_all_outputs:                             # branching_out(), ddpm.py:869
-                hist_x0.append([b.cpu() for b in x0_k])
-            t -= 1
-        if not fused:
-            ret = torch.cat([x_first.reshape(1, *shape), x_rest.reshape(K - 1, *shape)], 0).clone()
-            return (ret, hist_x0, []) if return_all_outputs else ret
-        jp.cond_in.copy_(cond)
-        jp.run_cond(st)
-        x0_buf = torch.empty(shape, dtype=torch.float32, device=dev) if (return_all_outputs or gate) else None
-        after = (lambda _t: hist_x0.append(x0_buf.cpu())) if return_all_outputs else None
-        if gate:
-            self._gated_joint_steps_k(jp, t, lo, hi, z, draw, x0_buf, kept, cond, cond_k, masks, m0, after)
-        else:
-            self.run_joint_steps(jp, t, t + 1, lo, hi, z, draw, x0_buf=x0_buf, after=after)
-        ret = jp.x_in.clone()
-        return (ret, hist_x0, []) if return_all_outputs else ret
+            if t <= t_fuse and (t_next >= 0 or not ddim):        # (the last DDIM pair never fuses, ddpm.py:1013-1021)
+                return bu, (idx if ddim else t, draw), True
+            for (k, i0, i1, b0, b1), (xv, mv), zz in zip(bu.runs, bu.views, zs):
+                self._reverse_step(xv, mv, zz, t, t_next, lo, hi, None if x0_units is None else x0_units[i0:i1])
+            if on_step is not None:
+                on_step()
+            idx += 1
+        return bu, (len(pairs) if ddim else -1, draw), False
 
-    def _gated_joint_steps_k(self, jp, t, lo, hi, z, draw, x0_buf, kept, cond, cond_k, masks, m0, after):
-        """``_gated_joint_steps`` for K branches: a rejected joint step (score <= 0, t > 0) is replaced by a K-branch
-        evaluation + fusion at the same t from the masked branch states ``kept`` (one per branch, ddpm.py:799), with
-        mask_x forced on (:906-908)."""
+    def _branch_fast_path(self, bu, pairs, t_fuse, lo, hi):
+        """The steps before the fusion time of a single-channel-mask call with the OOD and the IND branch as two concurrent
+        sub-batches, each a replayed HIP graph of one step on its own stream (same draw for both, ld_mask_out folded into
+        the OOD branch's step): _SubBatches for the ancestral steps, _DdimBranches for the DDIM pairs.  Returns the number
+        of steps it ran (0: not worth it / not possible here)."""
+        B, C, (H, W) = bu.m0.shape[0], self.channels, bu.m0.shape[2:]
+        ddim, n_plain = self.is_ddim_sampling, 0
+        for t, t_next in pairs:
+            if t <= t_fuse or (ddim and t_next < 0):
+                break
+            n_plain += 1
+        if (bu.replaced or self.sub_batches <= 1 or not (B >= self.min_sub_batch or self._sub_ok(B, H, W))
+                or self.noise_source != "device" or n_plain < 4 or self.use_graph):
+            return 0
+        (x_out, mo_out), (x_in, _) = bu.rows(0, B), bu.rows(B, 2 * B)
+        if ddim:
+            key = ("ddim", B, H, W, bool(bu.mask_x), self.num_timesteps, self.sampling_timesteps, float(self.ddim_sampling_eta))
+            if key not in self._subs:
+                self._subs[key] = self._ddim_branches(B, H, W, bu.mask_x, pairs)
+            self._subs[key].run(x_out, x_in, bu.cond_k[0], bu.cond_k[1], bu.m0, 0, n_plain, lo, hi)
+            return n_plain
+        if C != mo_out.shape[1]:
+            return 0
+        key = (id(bu.plan), "branch", bool(bu.mask_x))
+        if key not in self._subs:
+            self._subs[key] = _SubBatches(self, bu.plan, 2, shared_noise=True, masked=(0,) if bu.mask_x else (), instance_base=100)
+        if bu.mask_x:
+            self._subs[key].set_mask(bu.m0)
+        self._subs[key].run(pairs[0][0], n_plain, lo, hi, 1)
+        return n_plain
+
+    # ------------------------------------------------------------------ FUSE step + JOINT phase
+    def _fuse_ddpm(self, fx, masks, jp, x0f, t, z, lo, hi):
+        """The fusion step at t (ddpm.py:769-810): x0 = clamp(sum_k x0_k m_k) into ``x0f``, x_t = first non-zero of x_t,k m_k,
+        then the posterior step with the draw in ``z`` into ``jp.x_in``.  ``fx``: _BranchUnits.branches()."""
+        lib, st = cabi.lib(), self._st()
+        (nl, K), C, HW = masks.shape[:2], jp.x_in.shape[1], masks.shape[2] * masks.shape[3]
+        cabi.check(lib.ld_fuse_ddpm_k(*[v.data_ptr() for v in fx], masks.data_ptr(), jp.x_in.data_ptr(), x0f.data_ptr(),
+                                      lo, hi, nl, C, K, HW, st), "fuse_ddpm_k")
+        jp.set_step(t)
+        cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0f.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
+                                         self._sched_table().data_ptr(), jp.t_dev.data_ptr(), jp.x_in.numel(), st),
+                   "posterior_step")
+
+    def _fuse_joint(self, fx, masks, cond, where, lo, hi, z, x0_buf=None, after=None, gate=None, halves=False):
+        """Recompose the images whose K branches ``fx`` holds (_BranchUnits.branches(): states and predictions AT the
+        fusion step ``where``, whose draw is in ``z``) and run their remaining steps (ddpm.py:769-810 + 874-922;
+        :1021-1042).  ``x0_buf`` / ``after(t)``: as for run_joint_steps, from the fusion step on.  ``gate``: (kept branch
+        states, the branch phase's units) -- the joint steps run under the classifier gate.  ``halves``: the remaining
+        DDIM pairs may run as two concurrent halves.  The carried mask_x is the caller's business.  -> [n,C,H,W]."""
+        nl, (H, W) = masks.shape[0], masks.shape[2:]
+        jp = self.model.plan(nl, H, W, table_T=self.num_timesteps_ori)
+        pos, draw = where
+        if self.is_ddim_sampling:
+            pairs, _ = self._reverse_pairs(None, False)
+            t, t_next = pairs[pos]
+            san, c, sigma = self._ddim_scalars(t, t_next)
+            cabi.check(cabi.lib().ld_fuse_ddim_k(*[v.data_ptr() for v in fx], masks.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
+                                                 float(self.sqrt_recip_alphas_cumprod[t]), float(self.sqrt_recipm1_alphas_cumprod[t]),
+                                                 san, c, sigma, lo, hi, nl, self.channels, masks.shape[1], H * W, self._st()),
+                       "fuse_ddim_k")
+            jp.cond_in.copy_(cond)
+            self._ddim_joint(jp, cond, pairs, pos + 1, draw, lo, hi, z, halves)
+            return jp.x_in.clone()
+        t = pos
+        self._fuse_ddpm(fx, masks, jp, x0_buf if x0_buf is not None else torch.empty_like(jp.x_in), t, z, lo, hi)
+        if after is not None:
+            after(t)
+        t -= 1
+        jp.cond_in.copy_(cond)
+        if gate is not None:
+            jp.run_cond(self._st())
+            self._gated_joint_steps(jp, t, lo, hi, z, draw, x0_buf, after, masks, cond, *gate)
+        elif t >= 0:
+            self.encode_cond(jp, t + 1, x0_buf, after)
+            self.run_joint_steps(jp, t, t + 1, lo, hi, z, draw, x0_buf=x0_buf, after=after)
+        return jp.x_in.clone()
+
+    def _ddim_joint(self, jp, cond, pairs, idx, draw, lo, hi, z, halves, hist=None):
+        """The single-branch DDIM pairs idx.. on plan ``jp`` (x_t in ``jp.x_in``, the conditioning images in ``jp.cond_in`` and
+        ``cond``; ddpm.py:1005-1020), ``hist`` collecting every x_t.  ``halves``: as two concurrent halves of the batch
+        (replayed graphs, sliced draws) where that pays."""
+        st = self._st()
+        B, _, H, W = jp.x_in.shape
+        n_left = len(pairs) - idx
+        if (halves and self.sub_batches == 2 and B % 2 == 0 and (B // 2 >= self.min_sub_batch or self._sub_ok(B // 2, H, W))
+                and self.noise_source == "device" and hist is None and n_left >= 4 and not self.use_graph):
+            key = ("ddim-joint", B, H, W, self.num_timesteps, self.sampling_timesteps, float(self.ddim_sampling_eta))
+            if key not in self._subs:
+                self._subs[key] = self._ddim_branches(B // 2, H, W, False, pairs, shared=False)
+            h = B // 2
+            self._subs[key].run(jp.x_in[:h], jp.x_in[h:], cond[:h], cond[h:], None, idx, n_left, lo, hi)
+            return
+        jp.run_cond(st)
+        for t, t_next in pairs[idx:]:
+            jp.set_step(t)
+            jp.run_main(st)
+            if t_next >= 0:
+                self._noise(z, draw)
+                draw += 1
+            self._reverse_step(jp.x_in, jp.model_out, z, t, t_next, lo, hi)
+            if hist is not None:
+                hist.append(jp.x_in.clone())
+
+    def _gated_joint_steps(self, jp, t, lo, hi, z, draw, x0_buf, after, masks, cond, kept, bu):
+        """Joint steps t..0 under the classifier gate (fusion(), ddpm.py:883-916).  Until one fused prediction
+        is accepted every joint step's x0 is scored; a rejected one (score <= 0 and t > 0) is discarded and
+        replaced by a fresh K-branch evaluation + fusion at the SAME t, started from the masked branch states
+        ``kept`` the fusion step kept (one per branch, ddpm.py:799), with mask_x forced on (:906-908).  Noise draws stay in
+        program order: the rejected step's draw, then the redo's."""
         lib, st = cabi.lib(), self._st()
         sched, obj = self._sched_table(), cabi.OBJ[self.objective]
-        B, C, H, W = jp.x_in.shape
-        K, HW, n = masks.shape[1], H * W, jp.x_in.numel()
-        bp = None
+        redo = None                                         # branch units of the redo, built on first rejection
         while t >= 0:
             jp.set_step(t)
             jp.run_main(st)
@@ -1241,128 +1268,133 @@ class GaussianDiffusion(nn.Module):
                 self._noise(z, draw)
                 draw += 1
             cabi.check(lib.ld_ddpm_step(jp.x_in.data_ptr(), jp.model_out.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
-                                        x0_buf.data_ptr(), sched.data_ptr(), jp.t_dev.data_ptr(), lo, hi, obj, n, st), "ddpm_step")
+                                        x0_buf.data_ptr(), sched.data_ptr(), jp.t_dev.data_ptr(), lo, hi, obj,
+                                        jp.x_in.numel(), st), "ddpm_step")
             if self.classifier_flag == 0:
                 self.pred_cls = float(self.classifier(x0_buf)[0])
                 self.classifier_calls += 1
             if self.pred_cls > 0.0 or t == 0:
                 self.classifier_flag = 1
             else:
-                replaced = self._replaced_out(True)
-                nb = (K - 1) * B if replaced else K * B
-                if bp is None:
-                    bp = self.model.plan(nb, H, W, table_T=self.num_timesteps_ori)
-                bp.cond_in.copy_((cond_k[1:] if replaced else cond_k).reshape(nb, *cond.shape[1:]))
-                bp.run_cond(st)
-                x_first = kept[0] if replaced else bp.x_in[:B]
-                x_rest = bp.x_in if replaced else bp.x_in[B:]
-                if not replaced:
-                    x_first.copy_(kept[0])
-                for k in range(1, K):
-                    x_rest[(k - 1) * B:k * B].copy_(kept[k])
-                mo_first = cond_k[0] if replaced else bp.model_out[:B]
-                mo_rest = bp.model_out if replaced else bp.model_out[B:]
-                bp.set_step(t)
-                bp.run_main(st)
-                if not replaced:
-                    cabi.check(lib.ld_mask_out(mo_first.data_ptr(), m0.data_ptr(), lo, B, C, HW, st), "mask_out")
+                if redo is None:
+                    redo = _BranchUnits(self, bu.cond_k, bu.m0, True, bu.u_lo, bu.u_hi)
+                redo.encode()
+                # the masked states are idempotent under the fusion's own masking, so ``kept`` stays as it is
+                redo.load(kept)
+                redo.evaluate(t, lo)
                 self._noise(z, draw)                        # t > 0 here
                 draw += 1
-                cabi.check(lib.ld_fuse_ddpm_k(x_first.data_ptr(), x_rest.data_ptr(), mo_first.data_ptr(), mo_rest.data_ptr(),
-                                              masks.data_ptr(), jp.x_in.data_ptr(), x0_buf.data_ptr(), lo, hi, B, C, K, HW, st),
-                           "fuse_ddpm_k")
-                self._mask_x_set(False)
-                if bp is jp:                                # plans are cached per batch size: restore the joint one
+                self._fuse_ddpm(redo.branches(), masks, jp, x0_buf, t, z, lo, hi)
+                self._mask_x_set(False)                     # :908 set it, the redo's fusion step (:781) clears it again
+                if redo.plan is jp:                         # plans are cached per batch size: restore the joint one
                     jp.cond_in.copy_(cond)
                     jp.run_cond(st)
-                jp.set_step(t)
-                cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0_buf.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
-                                                 sched.data_ptr(), jp.t_dev.data_ptr(), n, st), "posterior_step")
             if after is not None:
                 after(t)
             t -= 1
         return draw
 
-    def _ddim_sample_kmask(self, cond, masks, lo, hi, shape, x_T, fuse, mask_x):
-        """ddim_sample with K >= 2 masks [B,K,H,W]: every pair evaluates the K branches as one batch (clip_x_start,
-        one shared draw, ddpm.py:1005-1020), the fusion pair (t <= times[-start_timestep-2]) recomposes them with
-        ld_fuse_ddim_k, the remaining pairs run on the fused image; never fused -> a list of the K branch states.
-        oracle/diffusion_ref.py::ddim_sample_kmask is the restatement (K = 2 is the reference's path bit for bit)."""
-        lib, st, dev = cabi.lib(), self._st(), self.device
+    def _branch_fuse_joint(self, cond, mask, mask_x, fuse, x_T, start_t, lo, hi, z, x0_buf=None, after=None, hist_x0=None):
+        """BRANCH -> (FUSE -> JOINT) of one sample() call, ancestral or DDIM, on one set of buffers.  A single-channel mask
+        [B,1,H,W] is the reference's two-branch process (ddpm.py:672-708): K = 2 with masks [m, 1 - (m >= 1)]; an explicit
+        [B,K,H,W] is its K-branch generalisation (branch 0 OOD-style, branches 1..K-1 IND-style; at the
+        fusion time x0 = clamp(sum_k x0_k m_k), x_t = first non-zero of x_t,k m_k).  config['classifier']: the ancestral
+        joint steps run under the gate of fusion() (:883-916).  ``hist_x0`` collects a K-list of x0 per branch step (:869).
+        Returns the fused sample, or the list of the K final branch states when the branches were never fused.
+        oracle/diffusion_ref.py::p_sample_loop_kmask / ddim_sample_kmask are the restatements."""
+        dev = self.device
+        single = mask.shape[1] == 1
+        mask = mask.to(dev, torch.float32)
+        masks = (torch.cat([mask, 1.0 - (mask >= 1.0).float()], 1) if single else mask).contiguous()
+        B, K = masks.shape[:2]
+        gated = bool(self.config.get("classifier", False)) and fuse and not self.is_ddim_sampling     # ddpm.py:883
+        if gated:
+            self.call_classifier()
+        x0_units, on_step = None, None
+        if hist_x0 is not None:
+            x0_units = torch.empty((K * B,) + tuple(x_T.shape[1:]), dtype=torch.float32, device=dev)
+            on_step = lambda: hist_x0.append([x0_units[k * B:(k + 1) * B].cpu() for k in range(K)])
+        bu, where, fused = self._branch_phase(cond, masks, mask_x, fuse, x_T, start_t, lo, hi, z, 0, K * B, x0_units, on_step,
+                                              fast=single and hist_x0 is None)
+        fx = bu.branches()
+        if not fused:
+            return [fx[0].clone()] + [fx[1][(k - 1) * B:k * B].clone() for k in range(1, K)]
+        gate = None
+        if gated:                                           # self.x_branchout (ddpm.py:799), one state per branch
+            bm = (masks >= 1.0).float()
+            gate = ([fx[0] * bm[:, 0:1]] + [fx[1][(k - 1) * B:k * B] * bm[:, k:k + 1] for k in range(1, K)], bu)
+            x0_buf = torch.empty_like(z) if x0_buf is None else x0_buf
+        self._mask_x_set(False)                             # ddpm.py:781, :1024
+        return self._fuse_joint(fx, masks, cond, where, lo, hi, z, x0_buf, after, gate, halves=single)
+
+    # ------------------------------------------------------------------ DDPM loop
+    @torch.inference_mode()
+    def p_sample_loop(self, cond_img, mask, min_max_val, shape, return_all_timesteps=False,
+                      return_all_outputs=False):
+        self._sync_model()
+        dev = self.device
         B, C, H, W = shape
-        K, HW, n = masks.shape[1], H * W, B * C * H * W
-        T, S, eta = self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
-        obj = cabi.OBJ[self.objective]
-        masks = masks.to(dev, torch.float32).contiguous()
-        times, pairs = schedule.ddim_time_pairs(T, S)
-        t_fuse = times[-int(self.config["start_timestep"]) - 2]                 # ddpm.py:987
-        abar, sr_all, srm1_all = self.alphas_cumprod, self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
-        sab_all, s1m_all = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        lo, hi = float(min_max_val[0]), float(min_max_val[1])
+        branch, fuse, mask_x = self._flags(mask)
+        if return_all_timesteps and branch:
+            self._refuse_branch_history()
+        cond = cond_img.to(dev, torch.float32).contiguous()
+        x_T, start_t = self._start(shape, getattr(self, "hr", None))
+        z = torch.empty(shape, dtype=torch.float32, device=dev)
+        x0_buf = torch.empty(shape, dtype=torch.float32, device=dev) if return_all_outputs else None
+        hist_x, hist_x0 = [x_T.clone()] if return_all_timesteps else None, []
+        if branch:
+            assert mask is not None
+            after = (lambda _t: hist_x0.append(x0_buf.cpu())) if return_all_outputs else None
+            ret = self._branch_fuse_joint(cond, mask, mask_x, fuse, x_T, start_t, lo, hi, z, x0_buf, after,
+                                          hist_x0 if return_all_outputs else None)
+        else:
+            jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
+            jp.x_in.copy_(x_T)
+            jp.cond_in.copy_(cond)
 
-        def scalars(t, t_next):
-            a, an = abar[t], abar[t_next]
-            sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()             # ddpm.py:1017-1018
-            return float(an.sqrt()), float((1 - an - sigma ** 2).sqrt()), float(sigma)
+            def after(_t):
+                if return_all_outputs:
+                    hist_x0.append(x0_buf.cpu())
+                if return_all_timesteps:
+                    hist_x.append(jp.x_in.clone())
+            cb = after if (return_all_outputs or return_all_timesteps) else None
+            self.encode_cond(jp, start_t + 1, x0_buf, cb)
+            self.run_joint_steps(jp, start_t, start_t + 1, lo, hi, z, 1, x0_buf=x0_buf, after=cb)
+            ret = torch.stack(hist_x, dim=1) if return_all_timesteps else jp.x_in.clone()
+        start_int = bool(self.config["start_intermediate"]) or self.start_intermediate
+        if isinstance(ret, list) and mask.shape[1] > 1:     # explicit K masks, never fused: [K,B,C,H,W]
+            ret = torch.stack(ret, dim=0)
+        elif (not start_int) and self.branch_out:           # ddpm.py:964-970
+            ret = torch.stack(ret, dim=0) if isinstance(ret, list) else torch.stack((ret, ret), dim=0)
+        if return_all_outputs:
+            return ret, hist_x0, []
+        return ret
 
-        def step(xv, mv, t, t_next, zz):
-            last = 1 if t_next < 0 else 0
-            san, c, sigma = (0.0, 0.0, 0.0) if last else scalars(t, t_next)
-            cabi.check(lib.ld_ddim_step(xv.data_ptr(), mv.data_ptr(), cabi.ptr(zz), xv.data_ptr(), float(sr_all[t]),
-                                        float(srm1_all[t]), float(sab_all[t]), float(s1m_all[t]), san, c, sigma, lo, hi, obj,
-                                        last, xv.numel(), st), "ddim_step")
-        plan, m0, cond_k, replaced, x_first, x_rest, mo_first, mo_rest = self._kmask_setup(cond, masks, lo, shape, mask_x)
-        x_first.copy_(x_T)
-        x_rest.copy_(x_T.repeat(K - 1, 1, 1, 1))
+    # ------------------------------------------------------------------ DDIM loop
+    @torch.inference_mode()
+    def ddim_sample(self, cond_img, mask, min_max_val, shape, return_all_timesteps=False):
+        self._sync_model()
+        dev = self.device
+        B, C, H, W = shape
+        lo, hi = float(min_max_val[0]), float(min_max_val[1])
+        branch, fuse, mask_x = self._flags(mask)
+        if return_all_timesteps and branch:
+            self._refuse_branch_history()
+        cond = cond_img.to(dev, torch.float32).contiguous()
+        x_T, _ = self._start(shape, None)
         z = torch.zeros(shape, dtype=torch.float32, device=dev)
-        draw, idx, jp = 1, 0, None
-        while idx < len(pairs):
-            t, t_next = pairs[idx]
-            plan.set_step(t)
-            plan.run_main(st)
-            if mask_x and not replaced:
-                cabi.check(lib.ld_mask_out(mo_first.data_ptr(), m0.data_ptr(), lo, B, C, HW, st), "mask_out")
-            views = [(x_first, mo_first)] + [(x_rest[(k - 1) * B:k * B], mo_rest[(k - 1) * B:k * B]) for k in range(1, K)]
-            if t_next < 0:
-                for xv, mv in views:
-                    step(xv, mv, t, t_next, None)
-                idx += 1
-                continue
-            self._noise(z, draw)
-            draw += 1
-            if fuse and t <= t_fuse:
-                jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-                san, c, sigma = scalars(t, t_next)
-                cabi.check(lib.ld_fuse_ddim_k(x_first.data_ptr(), x_rest.data_ptr(), mo_first.data_ptr(), mo_rest.data_ptr(),
-                                              masks.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(), float(sr_all[t]),
-                                              float(srm1_all[t]), san, c, sigma, lo, hi, B, C, K, HW, st), "fuse_ddim_k")
-                self._mask_x_set(False)                    # ddpm.py:1024
-                idx += 1
-                break
-            for xv, mv in views:
-                step(xv, mv, t, t_next, z)
-            idx += 1
-        if jp is None:
-            return [x_first.clone()] + [x_rest[(k - 1) * B:k * B].clone() for k in range(1, K)]
+        if branch:                                          # fused: [B,C,H,W]; never fused: the list of ddpm.py:1069
+            assert mask is not None
+            return self._branch_fuse_joint(cond, mask, mask_x, fuse, x_T, None, lo, hi, z)
+        hist = [x_T.clone()] if return_all_timesteps else None      # imgs = [img], ddpm.py:993
+        jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
+        jp.x_in.copy_(x_T)
         jp.cond_in.copy_(cond)
-        jp.run_cond(st)
-        while idx < len(pairs):
-            t, t_next = pairs[idx]
-            jp.set_step(t)
-            jp.run_main(st)
-            if t_next >= 0:
-                self._noise(z, draw)
-                draw += 1
-            step(jp.x_in, jp.model_out, t, t_next, z if t_next >= 0 else None)
-            idx += 1
-        return jp.x_in.clone()
+        self._ddim_joint(jp, cond, self._reverse_pairs(None, False)[0], 0, 1, lo, hi, z, True, hist)
+        return torch.stack(hist, dim=1) if hist is not None else jp.x_in.clone()      # ddpm.py:1072
 
-    # ------------------------------------------------------------------ the K-mask loop in two halves (dist.sample_kmask_sharded)
-    # SURVEY 8e "Collective": in the reference's fusion mode the exchange sits at t = start_timestep (ddpm.py:779-810,
-    # :1021-1042): every branch contributes its state x_t and its prediction x0_hat, then the remaining steps run on the
-    # recomposed image.  The unit of work before that point is a BRANCH-PATCH u = k * B + b (branch k of image b, the
-    # layout of _kmask_setup's plan); after it, an image.  kmask_branch_units runs units [u_lo, u_hi) up to the exchange,
-    # kmask_fuse_joint takes the gathered (x_t, x0_hat) of ALL units and finishes images [i_lo, i_hi).  Called with the
-    # full ranges the two halves are _p_sample_loop_kmask / _ddim_sample_kmask (tests/test_hip_dist.py).
+    # ------------------------------------------------------------------ the two halves for dist.sample_kmask_sharded
     def kmask_flags(self, masks):
         """(branch, fuse, mask_x) of a K-mask call as sample() would take them now; the per-call state that outlives the
         call is moved by ``advance_call_state`` (once per rank, shard or no shard)."""
@@ -1372,26 +1404,6 @@ class GaussianDiffusion(nn.Module):
         mask_x = self._mask_x_get() or bool(c.get("ood_AD", False)) or bool(c.get("ood_confidence", False))
         return bool(c["branch_out"]) or self.branch_out, bool(c["start_intermediate"]) or self.start_intermediate, mask_x
 
-    def _kmask_start(self, shape, gt):
-        """x_T of the WHOLE image batch (every branch of image b starts from x_T[b], ddpm.py:955-957) and the first t."""
-        lib, st, dev = cabi.lib(), self._st(), self.device
-        x_T = torch.empty(shape, dtype=torch.float32, device=dev)
-        self._noise(x_T, 0)
-        start_t = self.num_timesteps - 1
-        if (not self.is_ddim_sampling and (bool(self.config["start_intermediate"]) or self.start_intermediate)
-                and self.config.get("use_gt", False)):
-            t0 = int(self.config["use_gt_timestep"])              # ddpm.py:937-944
-            hr = gt.to(dev, torch.float32).contiguous()
-            cabi.check(lib.ld_q_sample(hr.data_ptr(), x_T.data_ptr(), x_T.data_ptr(), float(self.sqrt_alphas_cumprod[t0]),
-                                       float(self.sqrt_one_minus_alphas_cumprod[t0]), x_T.numel(), st), "q_sample")
-            start_t = t0 - 1
-        return x_T, start_t
-
-    def _ddim_scalars(self, t, t_next):
-        a, an = self.alphas_cumprod[t], self.alphas_cumprod[t_next]
-        sigma = self.ddim_sampling_eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()     # ddpm.py:1017-1018
-        return float(an.sqrt()), float((1 - an - sigma ** 2).sqrt()), float(sigma)
-
     @torch.inference_mode()
     def kmask_branch_units(self, cond_img, masks, min_max_val, u_lo, u_hi, gt=None):
         """Branch phase of the K-mask reverse process for units [u_lo, u_hi) (u = k * B + b; masks [B,K,H,W]).  Returns
@@ -1399,109 +1411,20 @@ class GaussianDiffusion(nn.Module):
         x_t and x0_hat AT the fusion step (state not yet stepped: ddpm.py:779-797 recomposes x_t and x0_hat of the same t),
         without fusion the final states (row 1 unused).  ``where`` = (t or pair index of the exchange, next draw)."""
         self._sync_model()
-        lib, st, dev = cabi.lib(), self._st(), self.device
+        dev = self.device
         branch, fuse, mask_x = self.kmask_flags(masks)
-        assert branch and self.objective == "pred_x0", "branch mode exists only for pred_x0 (ddpm.py:739-749)"
+        assert branch, "kmask_branch_units: branch mode only"
         B, K, H, W = masks.shape
-        C, HW = self.channels, H * W
-        shape = (B, C, H, W)
-        lo, hi = float(min_max_val[0]), float(min_max_val[1])
-        masks = masks.to(dev, torch.float32).contiguous()
-        cond = cond_img.to(dev, torch.float32).contiguous()
-        m0 = masks[:, 0:1].contiguous()
-        if mask_x:
-            assert len(torch.unique((m0 >= 1.0).float())) == 2, "mask should be binary"   # ddpm.py:698
-        lo_clip = 0.5 if self.config["data"] == "mnist" else 0.95
-        cond_k = torch.empty((K,) + tuple(cond.shape), dtype=torch.float32, device=dev)
-        cabi.check(lib.ld_branch_conditions_k(cond.data_ptr(), masks.data_ptr(), cond_k.data_ptr(), lo_clip, B,
-                                              cond.shape[1], K, HW, st), "branch_conditions_k")
-        replaced = self._replaced_out(mask_x)
-        x_T, start_t = self._kmask_start(shape, gt)
-        n_units = u_hi - u_lo
-        n0 = max(0, min(u_hi, B) - u_lo) if replaced else 0       # leading units whose denoiser evaluation is skipped (:704-708)
-        nb = n_units - n0
-        pay = torch.empty((n_units, 2, C, H, W), dtype=torch.float32, device=dev)
-        # (a rank without units walks the same loop -- it needs `where`, and the loop is where that is decided)
-        plan = self.model.plan(nb, H, W, table_T=self.num_timesteps_ori) if nb else None
-        ub = [u % B for u in range(u_lo, u_hi)]
-        X0 = torch.empty((n0, C, H, W), dtype=torch.float32, device=dev)     # states of the skipped units
-        if n0:
-            X0.copy_(x_T[u_lo:u_lo + n0])
-        if nb:
-            idx = torch.tensor(ub[n0:], device=dev)
-            plan.x_in.copy_(x_T[idx])
-            plan.cond_in.copy_(cond_k.reshape(K * B, *cond.shape[1:])[u_lo + n0:u_hi])
-            plan.run_cond(st)
-        # runs of units that share k: rows [i0, i1) of the local list <-> images [b0, b1)
-        runs, i = [], 0
-        while i < n_units:
-            k, b0 = (u_lo + i) // B, (u_lo + i) % B
-            j = min(n_units, i + B - b0)
-            runs.append((k, i, j, b0, b0 + (j - i)))
-            i = j
-
-        def rows(i0, i1):
-            """(state, prediction) views of local rows [i0, i1) (a run never straddles the skipped / evaluated boundary)."""
-            if i1 <= n0:
-                return X0[i0:i1], cond_k[0][u_lo + i0:u_lo + i1]
-            return plan.x_in[i0 - n0:i1 - n0], plan.model_out[i0 - n0:i1 - n0]
-
-        def evaluate(t):
-            if nb:
-                plan.set_step(t)
-                plan.run_main(st)
-            if mask_x and not replaced:
-                for k, i0, i1, b0, b1 in runs:
-                    if k == 0:
-                        cabi.check(lib.ld_mask_out(rows(i0, i1)[1].data_ptr(), m0[b0:b1].data_ptr(), lo, b1 - b0, C, HW, st), "mask_out")
-
-        def finish(where):
-            for k, i0, i1, b0, b1 in runs:
-                xv, mv = rows(i0, i1)
-                pay[i0:i1, 0].copy_(xv)
-                pay[i0:i1, 1].copy_(mv)
-            return pay, where
-
+        shape = (B, self.channels, H, W)
+        x_T, start_t = self._start(shape, gt)
         z = torch.zeros(shape, dtype=torch.float32, device=dev)
-        sched, obj = self._sched_table(), cabi.OBJ[self.objective]
-        if not self.is_ddim_sampling:
-            t, draw = start_t, 1
-            while t >= 0:
-                evaluate(t)
-                if t > 0:
-                    self._noise(z, draw)
-                    draw += 1
-                if fuse and t <= int(self.config["start_timestep"]):
-                    return finish((t, draw))
-                row = sched[t:t + 1].contiguous()
-                for k, i0, i1, b0, b1 in runs:               # one shared draw for every branch of an image (ddpm.py:852-858)
-                    xv, mv = rows(i0, i1)
-                    cabi.check(lib.ld_ddpm_step(xv.data_ptr(), mv.data_ptr(), z[b0:b1].data_ptr() if t > 0 else None, xv.data_ptr(), None,
-                                                row.data_ptr(), None, lo, hi, obj, xv.numel(), st), "ddpm_step")
-                t -= 1
-            return finish((-1, draw))
-        T, S = self.num_timesteps, self.sampling_timesteps
-        times, pairs = schedule.ddim_time_pairs(T, S)
-        t_fuse = times[-int(self.config["start_timestep"]) - 2]                 # ddpm.py:987
-        draw, idx = 1, 0
-        while idx < len(pairs):
-            t, t_next = pairs[idx]
-            evaluate(t)
-            last = 1 if t_next < 0 else 0
-            if not last:
-                self._noise(z, draw)
-                draw += 1
-                if fuse and t <= t_fuse:
-                    return finish((idx, draw))
-            san, c, sigma = (0.0, 0.0, 0.0) if last else self._ddim_scalars(t, t_next)
-            for k, i0, i1, b0, b1 in runs:
-                xv, mv = rows(i0, i1)
-                cabi.check(lib.ld_ddim_step(xv.data_ptr(), mv.data_ptr(), None if last else z[b0:b1].data_ptr(), xv.data_ptr(),
-                                            float(self.sqrt_recip_alphas_cumprod[t]), float(self.sqrt_recipm1_alphas_cumprod[t]),
-                                            float(self.sqrt_alphas_cumprod[t]), float(self.sqrt_one_minus_alphas_cumprod[t]),
-                                            san, c, sigma, lo, hi, obj, last, xv.numel(), st), "ddim_step")
-            idx += 1
-        return finish((len(pairs), draw))
+        bu, where, _ = self._branch_phase(cond_img.to(dev, torch.float32).contiguous(), masks.to(dev, torch.float32).contiguous(),
+                                          mask_x, fuse, x_T, start_t, float(min_max_val[0]), float(min_max_val[1]), z, u_lo, u_hi)
+        pay = torch.empty((u_hi - u_lo, 2) + shape[1:], dtype=torch.float32, device=dev)
+        for (k, i0, i1, b0, b1), (xv, mv) in zip(bu.runs, bu.views):
+            pay[i0:i1, 0].copy_(xv)
+            pay[i0:i1, 1].copy_(mv)
+        return pay, where
 
     @torch.inference_mode()
     def kmask_fuse_joint(self, cond_img, masks, min_max_val, payload, where, i_lo, i_hi):
@@ -1510,294 +1433,23 @@ class GaussianDiffusion(nn.Module):
         ddpm.py:779-810, :1021-1042) and run their remaining steps.  The image's draws are those of the unsharded batch
         (noise stream positioned at image i_lo).  Returns [i_hi - i_lo, C, H, W]."""
         self._sync_model()
-        lib, st, dev = cabi.lib(), self._st(), self.device
+        dev = self.device
         B, K, H, W = masks.shape
-        C, HW, nl = self.channels, H * W, i_hi - i_lo
-        lo, hi = float(min_max_val[0]), float(min_max_val[1])
+        C, nl = self.channels, i_hi - i_lo
         if nl <= 0:
             return torch.empty((0, C, H, W), dtype=torch.float32, device=dev)
-        masks_l = masks[i_lo:i_hi].to(dev, torch.float32).contiguous()
-        cond_l = cond_img[i_lo:i_hi].to(dev, torch.float32).contiguous()
         pk = payload.to(dev, torch.float32).reshape(K, B, 2, C, H, W)[:, i_lo:i_hi]
-        x_first, mo_first = pk[0, :, 0].contiguous(), pk[0, :, 1].contiguous()
-        x_rest = pk[1:, :, 0].reshape((K - 1) * nl, C, H, W).contiguous()
-        mo_rest = pk[1:, :, 1].reshape((K - 1) * nl, C, H, W).contiguous()
-        jp = self.model.plan(nl, H, W, table_T=self.num_timesteps_ori)
-        shape = (nl, C, H, W)
-        z = torch.zeros(shape, dtype=torch.float32, device=dev)
-        n = nl * C * HW
+        fx = (pk[0, :, 0].contiguous(), pk[1:, :, 0].reshape((K - 1) * nl, C, H, W).contiguous(),
+              pk[0, :, 1].contiguous(), pk[1:, :, 1].reshape((K - 1) * nl, C, H, W).contiguous())
+        z = torch.zeros((nl, C, H, W), dtype=torch.float32, device=dev)
         keep = self.noise_offset
-        self.noise_offset = keep + i_lo * C * HW
+        self.noise_offset = keep + i_lo * C * H * W
         try:
-            if not self.is_ddim_sampling:
-                t, draw = where
-                if t > 0:
-                    self._noise(z, draw - 1)                   # the fusion step's draw (taken before the exchange)
-                x0f = torch.empty(shape, dtype=torch.float32, device=dev)
-                cabi.check(lib.ld_fuse_ddpm_k(x_first.data_ptr(), x_rest.data_ptr(), mo_first.data_ptr(), mo_rest.data_ptr(),
-                                              masks_l.data_ptr(), jp.x_in.data_ptr(), x0f.data_ptr(), lo, hi, nl, C, K, HW, st),
-                           "fuse_ddpm_k")
-                jp.set_step(t)
-                cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0f.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
-                                                 self._sched_table().data_ptr(), jp.t_dev.data_ptr(), n, st), "posterior_step")
-                t -= 1
-                jp.cond_in.copy_(cond_l)
-                if t >= 0:
-                    self.encode_cond(jp, t + 1)
-                    self.run_joint_steps(jp, t, t + 1, lo, hi, z, draw)
-                return jp.x_in.clone()
-            idx, draw = where
-            times, pairs = schedule.ddim_time_pairs(self.num_timesteps, self.sampling_timesteps)
-            obj = cabi.OBJ[self.objective]
-            t, t_next = pairs[idx]
-            self._noise(z, draw - 1)
-            san, c, sigma = self._ddim_scalars(t, t_next)
-            cabi.check(lib.ld_fuse_ddim_k(x_first.data_ptr(), x_rest.data_ptr(), mo_first.data_ptr(), mo_rest.data_ptr(),
-                                          masks_l.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(), float(self.sqrt_recip_alphas_cumprod[t]),
-                                          float(self.sqrt_recipm1_alphas_cumprod[t]), san, c, sigma, lo, hi, nl, C, K, HW, st), "fuse_ddim_k")
-            idx += 1
-            jp.cond_in.copy_(cond_l)
-            jp.run_cond(st)
-            while idx < len(pairs):
-                t, t_next = pairs[idx]
-                jp.set_step(t)
-                jp.run_main(st)
-                last = 1 if t_next < 0 else 0
-                if not last:
-                    self._noise(z, draw)
-                    draw += 1
-                san, c, sigma = (0.0, 0.0, 0.0) if last else self._ddim_scalars(t, t_next)
-                cabi.check(lib.ld_ddim_step(jp.x_in.data_ptr(), jp.model_out.data_ptr(), None if last else z.data_ptr(), jp.x_in.data_ptr(),
-                                            float(self.sqrt_recip_alphas_cumprod[t]), float(self.sqrt_recipm1_alphas_cumprod[t]),
-                                            float(self.sqrt_alphas_cumprod[t]), float(self.sqrt_one_minus_alphas_cumprod[t]),
-                                            san, c, sigma, lo, hi, obj, last, n, st), "ddim_step")
-                idx += 1
-            return jp.x_in.clone()
+            if self.is_ddim_sampling or where[0] > 0:
+                self._noise(z, where[1] - 1)                   # the fusion step's draw (taken before the exchange; none at t = 0)
+            return self._fuse_joint(fx, masks[i_lo:i_hi].to(dev, torch.float32).contiguous(),
+                                    cond_img[i_lo:i_hi].to(dev, torch.float32).contiguous(), where,
+                                    float(min_max_val[0]), float(min_max_val[1]), z)
         finally:
             self.noise_offset = keep
 
-    def _gated_joint_steps(self, jp, t, lo, hi, z, draw, x0_buf, x_branchout, cond, cond_out, cond_in, mask,
-                           mask_x, after):
-        """Joint steps t..0 under the classifier gate (fusion(), ddpm.py:883-916).  Until one fused prediction
-        is accepted every joint step's x0 is scored; a rejected one (score <= 0 and t > 0) is discarded and
-        replaced by a fresh two-branch evaluation + fusion at the SAME t, started from the masked branch states
-        the fusion step kept (ddpm.py:799), with mask_x forced on (:906-908).  Noise draws stay in program
-        order: the rejected step's draw, then the redo's."""
-        lib, st = cabi.lib(), self._st()
-        sched = self._sched_table()
-        obj = cabi.OBJ[self.objective]
-        B, C, H, W = jp.x_in.shape
-        HW, n = H * W, jp.x_in.numel()
-        bp = None                                           # branch plan of the redo, built on first rejection
-        while t >= 0:
-            jp.set_step(t)
-            jp.run_main(st)
-            if t > 0:
-                self._noise(z, draw)
-                draw += 1
-            cabi.check(lib.ld_ddpm_step(jp.x_in.data_ptr(), jp.model_out.data_ptr(), z.data_ptr(),
-                                        jp.x_in.data_ptr(), x0_buf.data_ptr(), sched.data_ptr(),
-                                        jp.t_dev.data_ptr(), lo, hi, obj, n, st), "ddpm_step")
-            if self.classifier_flag == 0:
-                self.pred_cls = float(self.classifier(x0_buf)[0])
-                self.classifier_calls += 1
-            if self.pred_cls > 0.0 or t == 0:
-                self.classifier_flag = 1
-            else:
-                mask_x = True
-                replaced = self._replaced_out(True)
-                if bp is None:
-                    bp = self.model.plan(B if replaced else 2 * B, H, W, table_T=self.num_timesteps_ori)
-                if replaced:
-                    bp.cond_in.copy_(cond_in)
-                else:
-                    bp.cond_in[:B].copy_(cond_out)
-                    bp.cond_in[B:].copy_(cond_in)
-                bp.run_cond(st)
-                x_in_view = bp.x_in if replaced else bp.x_in[B:]
-                x_out_view = x_branchout[0] if replaced else bp.x_in[:B]
-                if not replaced:
-                    x_out_view.copy_(x_branchout[0])
-                x_in_view.copy_(x_branchout[1])
-                mo_in = bp.model_out if replaced else bp.model_out[B:]
-                mo_out = cond_out if replaced else bp.model_out[:B]
-                bp.set_step(t)
-                bp.run_main(st)
-                if not replaced:
-                    cabi.check(lib.ld_mask_out(mo_out.data_ptr(), mask.data_ptr(), lo, B, C, HW, st), "mask_out")
-                self._noise(z, draw)                        # t > 0 here
-                draw += 1
-                # the masked states are idempotent under the fusion's own masking, so x_branchout stays as is
-                cabi.check(lib.ld_fuse_ddpm(x_out_view.data_ptr(), x_in_view.data_ptr(), mo_out.data_ptr(),
-                                            mo_in.data_ptr(), mask.data_ptr(), jp.x_in.data_ptr(),
-                                            x0_buf.data_ptr(), lo, hi, B, C, HW, st), "fuse_ddpm")
-                self._mask_x_set(False)                     # :908 set it, the redo's fusion step (:781) clears it again
-                if bp is jp:                                # plans are cached per batch size: restore the joint one
-                    jp.cond_in.copy_(cond)
-                    jp.run_cond(st)
-                jp.set_step(t)
-                cabi.check(lib.ld_posterior_step(jp.x_in.data_ptr(), x0_buf.data_ptr(), z.data_ptr(),
-                                                 jp.x_in.data_ptr(), sched.data_ptr(), jp.t_dev.data_ptr(), n, st),
-                           "posterior_step")
-            if after is not None:
-                after(t)
-            t -= 1
-        return draw
-
-    # ------------------------------------------------------------------ DDIM loop
-    @torch.inference_mode()
-    def ddim_sample(self, cond_img, mask, min_max_val, shape, return_all_timesteps=False):
-        self._sync_model()
-        lib, st, dev = cabi.lib(), self._st(), self.device
-        B, C, H, W = shape
-        HW, n = H * W, B * C * H * W
-        lo, hi = float(min_max_val[0]), float(min_max_val[1])
-        T, S, eta = self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
-        branch, fuse, mask_x = self._flags(mask)
-        if branch and mask is not None and mask.shape[1] > 1:        # K-mask generalisation (SURVEY 8f-3)
-            if return_all_timesteps:
-                raise TypeError("return_all_timesteps is only defined for the single-branch reverse process "
-                                "(the reference's torch.stack(imgs) fails on the per-branch lists, ddpm.py:1069-1072)")
-            x_T = torch.empty(shape, dtype=torch.float32, device=dev)
-            self._noise(x_T, 0)
-            return self._ddim_sample_kmask(cond_img.to(dev, torch.float32).contiguous(), mask, lo, hi, shape, x_T, fuse, mask_x)
-        obj = cabi.OBJ[self.objective]
-        times, pairs = schedule.ddim_time_pairs(T, S)
-        t_fuse = times[-int(self.config["start_timestep"]) - 2]                 # ddpm.py:987
-        cond = cond_img.to(dev, torch.float32).contiguous()
-        if mask is not None:
-            mask = mask.to(dev, torch.float32).contiguous()
-        x_T = torch.empty(shape, dtype=torch.float32, device=dev)
-        self._noise(x_T, 0)
-        z = torch.zeros(shape, dtype=torch.float32, device=dev)
-        abar = self.alphas_cumprod
-        sr_all, srm1_all = self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
-        sab_all, s1m_all = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
-
-        def scalars(t, t_next):
-            a, an = abar[t], abar[t_next]
-            sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()             # ddpm.py:1017-1018
-            c = (1 - an - sigma ** 2).sqrt()
-            return float(an.sqrt()), float(c), float(sigma)
-
-        def fwd(plan, t):
-            plan.set_step(t)
-            plan.run_main(st)
-
-        def step(xv, mv, t, t_next, zz):
-            last = 1 if t_next < 0 else 0
-            san, c, sigma = (0.0, 0.0, 0.0) if last else scalars(t, t_next)
-            cabi.check(lib.ld_ddim_step(xv.data_ptr(), mv.data_ptr(), cabi.ptr(zz), xv.data_ptr(),
-                                        float(sr_all[t]), float(srm1_all[t]), float(sab_all[t]), float(s1m_all[t]),
-                                        san, c, sigma, lo, hi, obj, last, n, st), "ddim_step")
-
-        draw, idx = 1, 0
-        xs = None
-        if return_all_timesteps and branch:
-            # ddpm.py:1072 stacks `imgs`, which holds [x_out, x_in] lists for the branch steps (:1043,1069)
-            raise TypeError("return_all_timesteps is only defined for the single-branch reverse process "
-                            "(the reference's torch.stack(imgs) fails on the per-branch lists, ddpm.py:1069-1072)")
-        hist = [x_T.clone()] if return_all_timesteps else None      # imgs = [img], ddpm.py:993
-        if branch:
-            assert self.objective == "pred_x0" and mask is not None
-            if mask_x:
-                assert len(torch.unique((mask >= 1.0).float())) == 2, "mask should be binary"
-            lo_clip = 0.5 if self.config["data"] == "mnist" else 0.95
-            cond_out, cond_in = torch.empty_like(cond), torch.empty_like(cond)
-            cabi.check(lib.ld_branch_conditions(cond.data_ptr(), mask.data_ptr(), cond_out.data_ptr(),
-                                                cond_in.data_ptr(), lo_clip, B, cond.shape[1], HW, st), "branch_conditions")
-            replaced = self._replaced_out(mask_x)
-            nb = B if replaced else 2 * B
-            plan = self.model.plan(nb, H, W, table_T=self.num_timesteps_ori)
-            if replaced:
-                plan.cond_in.copy_(cond_in)
-            else:
-                plan.cond_in[:B].copy_(cond_out)
-                plan.cond_in[B:].copy_(cond_in)
-            plan.run_cond(st)
-            x_in_view = plan.x_in if replaced else plan.x_in[B:]
-            x_out_view = torch.empty(shape, dtype=torch.float32, device=dev) if replaced else plan.x_in[:B]
-            x_out_view.copy_(x_T)
-            x_in_view.copy_(x_T)
-            mo_in = plan.model_out if replaced else plan.model_out[B:]
-            mo_out = cond_out if replaced else plan.model_out[:B]
-            fused = False
-            # the pairs before the fusion time: OOD and IND branch as two concurrent sub-batches (replayed graphs)
-            n_plain = 0
-            for (t_, tn_) in pairs:
-                if tn_ < 0 or (fuse and t_ <= t_fuse):
-                    break
-                n_plain += 1
-            if (not replaced and self.sub_batches > 1 and self.noise_source == "device" and not return_all_timesteps
-                    and n_plain >= 4 and not self.use_graph and (B >= self.min_sub_batch or self._sub_ok(B, H, W))):
-                key = ("ddim", B, H, W, bool(mask_x), T, S, float(eta))
-                if key not in self._subs:
-                    rows = []
-                    for (t_, tn_) in pairs:
-                        san_, c_, sg_ = (0.0, 0.0, 0.0) if tn_ < 0 else scalars(t_, tn_)
-                        rows.append([float(sr_all[t_]), float(srm1_all[t_]), float(sab_all[t_]), float(s1m_all[t_]), san_, c_, sg_,
-                                     1.0 if tn_ < 0 else 0.0])
-                    self._subs[key] = _DdimBranches(self, B, H, W, mask_x, [p_[0] for p_ in pairs], rows)
-                self._subs[key].run(x_out_view, x_in_view, cond_out, cond_in, mask, 0, n_plain, lo, hi)
-                idx, draw = n_plain, 1 + n_plain
-            while idx < len(pairs):
-                t, t_next = pairs[idx]
-                fwd(plan, t)
-                if mask_x and not replaced:
-                    cabi.check(lib.ld_mask_out(mo_out.data_ptr(), mask.data_ptr(), lo, B, C, HW, st), "mask_out")
-                if t_next < 0:
-                    step(x_out_view, mo_out, t, t_next, None)
-                    step(x_in_view, mo_in, t, t_next, None)
-                    idx += 1
-                    continue
-                self._noise(z, draw)
-                draw += 1
-                if fuse and t <= t_fuse:
-                    jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-                    san, c, sigma = scalars(t, t_next)
-                    cabi.check(lib.ld_fuse_ddim(x_out_view.data_ptr(), x_in_view.data_ptr(), mo_out.data_ptr(),
-                                                mo_in.data_ptr(), mask.data_ptr(), z.data_ptr(), jp.x_in.data_ptr(),
-                                                float(sr_all[t]), float(srm1_all[t]), san, c, sigma, lo, hi,
-                                                B, C, HW, st), "fuse_ddim")
-                    self._mask_x_set(False)                # ddpm.py:1024
-                    idx += 1
-                    fused = True
-                    break
-                step(x_out_view, mo_out, t, t_next, z)
-                step(x_in_view, mo_in, t, t_next, z)
-                idx += 1
-            if not fused:
-                xs = [x_out_view.clone(), x_in_view.clone()]
-        if xs is None:
-            jp = self.model.plan(B, H, W, table_T=self.num_timesteps_ori)
-            if idx == 0:
-                jp.x_in.copy_(x_T)
-            jp.cond_in.copy_(cond)
-            n_left = len(pairs) - idx
-            if (self.sub_batches == 2 and B % 2 == 0 and (B // 2 >= self.min_sub_batch or self._sub_ok(B // 2, H, W))
-                    and self.noise_source == "device" and not return_all_timesteps and n_left >= 4 and not self.use_graph):
-                # single-branch pairs as two concurrent halves of the batch (replayed graphs, sliced draws)
-                key = ("ddim-joint", B, H, W, T, S, float(eta))
-                if key not in self._subs:
-                    rows = []
-                    for (t_, tn_) in pairs:
-                        san_, c_, sg_ = (0.0, 0.0, 0.0) if tn_ < 0 else scalars(t_, tn_)
-                        rows.append([float(sr_all[t_]), float(srm1_all[t_]), float(sab_all[t_]), float(s1m_all[t_]), san_, c_, sg_,
-                                     1.0 if tn_ < 0 else 0.0])
-                    self._subs[key] = _DdimBranches(self, B // 2, H, W, False, [p_[0] for p_ in pairs], rows, shared=False)
-                h = B // 2
-                self._subs[key].run(jp.x_in[:h], jp.x_in[h:], cond[:h], cond[h:], None, idx, n_left, lo, hi)
-                return jp.x_in.clone()
-            jp.run_cond(st)
-            while idx < len(pairs):
-                t, t_next = pairs[idx]
-                fwd(jp, t)
-                if t_next >= 0:
-                    self._noise(z, draw)
-                    draw += 1
-                step(jp.x_in, jp.model_out, t, t_next, z if t_next >= 0 else None)
-                if hist is not None:
-                    hist.append(jp.x_in.clone())
-                idx += 1
-            return torch.stack(hist, dim=1) if hist is not None else jp.x_in.clone()      # ddpm.py:1072
-        return xs

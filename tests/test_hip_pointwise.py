@@ -8,6 +8,7 @@ smallest at which the code can go wrong (HW = 63 below one workgroup, n just abo
 workload's.  Every output buffer holds NaN before the launch.  ``-s`` prints d, the observed error and their ratio."""
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 
@@ -245,8 +246,55 @@ def test_k2_kernels_are_the_two_branch_kernels(sn, lohi):
     assert torch.equal(a["cond_out"], b["cond_k"][0]) and torch.equal(a["cond_in"], b["cond_k"][1])
 
 
+@pytest.mark.parametrize("lo_clip", [0.5, 0.95])
+@pytest.mark.parametrize("H", [28, 32])
+@pytest.mark.parametrize("Cc", [1, 3])
+def test_two_branch_kernels_equal_the_k_kernels_at_the_sampler_shapes(Cc, H, lo_clip):
+    """The sampler calls only the ``*_k`` kernels; a single-channel mask m runs as K = 2 with masks [m, 1 - (m >= 1)].  What
+    anchors "K = 2 is the reference's path" is this: on the same inputs ld_branch_conditions, ld_fuse_ddpm and ld_fuse_ddim
+    (with and without a noise pointer) give the bits of ld_branch_conditions_k, ld_fuse_ddpm_k and ld_fuse_ddim_k.  B = 2 at
+    the sampler's maps (28^2: HW is no power of two), masks holding 0.5 and 1.5 beside 0 and 1 (the >= 1 binarisation), and
+    exact zeros planted in the states and predictions so that both arms of ``a == 0 ? c : a`` and ``a0 == 0 ? alt : a0``
+    are taken on both sides (checked on the CPU with pointwise_ref's selectors)."""
+    from types import SimpleNamespace as NS
+    B, key = 2, 9000 + 100 * Cc + H
+    s = (B, Cc, H, H)
+    u = R.uni((B, 1, H, H), key, 0.0, 1.0)
+    mask = torch.zeros(B, 1, H, H)
+    mask[u < 0.75], mask[u < 0.50], mask[u < 0.25] = 0.5, 1.5, 1.0
+    masks = R.masks_two(mask)
+    assert {float(v) for v in mask.unique()} == {0.0, 0.5, 1.0, 1.5}
+    for lo, hi in R.RANGES:
+        xo, xi = R.values(s, key + 1, -2, 2), R.values(s, key + 2, -2, 2)
+        x0o, x0i = R.values(s, key + 3, lo - 1, hi + 1), R.values(s, key + 4, lo - 1, hi + 1)
+        two = NS(xo=xo, xi=xi, x0o=x0o, x0i=x0i, mask=mask, z=R.uni(s, key + 5), k=R._fuse_scalars(), lo=lo, hi=hi)
+        kk = NS(x_first=xo, x_rest=xi[None], x0_first=x0o, x0_rest=x0i[None], masks=masks, z=two.z, k=two.k, lo=lo, hi=hi)
+        # both arms of both selectors occur, in the two-branch and in the K-mask statement alike
+        sels = [{}, {}, {}, {}]
+        R.fuse_ddpm(xo, xi, x0o, x0i, mask, lo, hi, torch.float32, sels[0])
+        R.fuse_ddpm_k(xo, xi[None], x0o, x0i[None], masks, lo, hi, torch.float32, sels[1])
+        R.fuse_ddim(xo, xi, x0o, x0i, mask, two.z, two.k, lo, hi, torch.float32, sels[2])
+        R.fuse_ddim_k(xo, xi[None], x0o, x0i[None], masks, two.z, two.k, lo, hi, torch.float32, sels[3])
+        inside = (mask >= 1.0).expand(s)
+        for sel, name in ((sels[0], "a==0"), (sels[1], "a0==0"), (sels[2], "a0==0"), (sels[3], "a0==0")):
+            assert bool(sel[name].any()) and bool((~sel[name]).any()), (name, lo, hi)
+        assert bool((sels[0]["a==0"] & inside).any()), "no exactly-zero OOD state inside the mask"
+        a, b = run_fuse_ddpm(two), run_fuse_ddpm_k(kk)
+        assert np.array_equal(a["x"].numpy(), b["x"].numpy()) and np.array_equal(a["x0"].numpy(), b["x0"].numpy())
+        assert bool(torch.isfinite(a["x"]).all()) and bool(torch.isfinite(a["x0"]).all())
+        for z in (two.z, None):
+            two.z = kk.z = z
+            a, b = run_fuse_ddim(two), run_fuse_ddim_k(kk)
+            assert np.array_equal(a["x_next"].numpy(), b["x_next"].numpy()) and bool(torch.isfinite(a["x_next"]).all())
+    c = NS(cond=R.values(s, key + 6, 0.0, 2.0), mask=mask, masks=masks, lo_clip=R.f32(lo_clip))
+    a, b = run_branch_conditions(c), run_branch_conditions_k(c)
+    assert np.array_equal(a["cond_out"].numpy(), b["cond_k"][0].numpy())
+    assert np.array_equal(a["cond_in"].numpy(), b["cond_k"][1].numpy())
+    assert bool(torch.isfinite(b["cond_k"]).all())
+
+
 # ------------------------------------------------------------------------------------------------ head-of-step work
-GUARD = 64                                           # floats of NaN before and after every buffer a kernel writes
+GUARD = 64                                          # floats of NaN before and after every buffer a kernel writes
 RAGGED = 16 * (256 * 8 * 3 + 5)                      # bytes: the zeroing loop ends in a ragged tail
 T_TABLE = [41, 33, 25, 17, 9, 1]
 
