@@ -1228,6 +1228,27 @@ int ld_ds_seg_batch(const float* image, const void* label_u8, int N, int R, int 
 int ld_ds_mnist_cls_batch(const void* store_u8, const void* labels_u8, int N, int S, const ld_ds_row* table, int B, float* x,
                           long long* label, void* stream);
 
+/* ---- quality metrics (metrics.hip): per-sample, per-region error sums for MSE / PSNR / SSIM ------------------------------ */
+/* pred, ref fp32 NCHW [B, C, H, W] contiguous; mask [B, 1, H, W] fp32 or NULL.  out [B][3][4] fp64: region 0 = the whole image,
+ * 1 = OOD (mask >= 1, ld_recompose's convention), 2 = IND (the rest; with mask NULL regions 1 and 2 are zeros); fields n_elem
+ * (elements of the region over all channels), sse (d = pred - ref in fp32, widened, squared and added in double), n_win (SSIM
+ * windows counted) and ssim_sum.  SSIM: Wang et al., 11 x 11 Gaussian window (sigma 1.5, the 11 taps computed in double and
+ * rounded to fp32 once: ld_metric_taps), biased variances, K1 = 0.01, K2 = 0.03, C1 = (K1 L)^2 and C2 = (K2 L)^2 computed in double
+ * and rounded once, L = data_range; only windows wholly inside the image count (no padding: (H - 10) x (W - 10) per channel), and
+ * a window belongs to the region of its centre pixel.  Per window in fp32, no fused multiply-add: the five moments mu_x, mu_y,
+ * E[x^2], E[y^2], E[xy] by a horizontal pass, then a vertical one, taps added in index order; sx = E[x^2] - mu_x^2, sy, sxy alike;
+ * ssim = ((2 mu_x mu_y + C1)(2 sxy + C2)) / ((mu_x^2 + mu_y^2 + C1)(sx + sy + C2)) with IEEE division, widened to double.
+ * Two launches: one workgroup per (sample, channel, 32 x 32 tile of window centres) leaves 12 partial sums in `work`
+ * (ld_metric_work_doubles(B, C, H, W) doubles; 0 for a shape the call refuses), the second adds a sample's partial sums in
+ * (channel, tile row, tile column) order.  No floating-point atomics: two calls give the same bits, and the result of sample b
+ * depends neither on B nor on the other samples.  LD_EINVAL with nothing launched or written: a NULL pred, ref, work or out; B, C,
+ * H or W below 1; H or W below 11; a data_range that is not finite and positive; out or work not 8-byte aligned (pred, ref,
+ * mask: 4-byte); more than 2^31 - 1 tiles. */
+int ld_metric_taps(float* taps /* host, 11 floats */);
+int64_t ld_metric_work_doubles(int B, int C, int H, int W);
+int ld_metric_sums(const float* pred, const float* ref, const float* mask, double* work, double* out, int B, int C, int H, int W,
+                   float data_range, void* stream);
+
 /* ---- the one collective of the path: all-gather of every rank's finished samples, RCCL over xGMI ---- */
 /* RCCL is dlopen'ed on first use (the copy the process already mapped, e.g. torch's, is preferred; LD_RCCL_PATH
  * overrides), so the library loads without it.  ld_comm_unique_id on one rank -> hand the 128 bytes to every rank ->

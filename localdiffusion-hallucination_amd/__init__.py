@@ -33,7 +33,7 @@ from .weights import UnetConfig  # noqa: F401,E402
 __all__ = ["rng", "schedule", "weights", "tuning", "Tuning", "UnetConfig", "Unet", "GaussianDiffusion", "SegUNet",
            "SegTrainer", "PatchCore", "PatchCoreClassifier", "MnistClassifier", "MnistClassifierTrainer", "ResnetBlock",
            "LinearAttention", "Attention", "Downsample", "Upsample", "Conv2d", "BasicBlock", "ResUnet", "TimeMLP", "TrainableUnet", "DenoiserTrainer", "coreset",
-           "DeviceDataset", "BatchSource", "configure_runtime"]
+           "DeviceDataset", "BatchSource", "metrics", "quality_sums", "quality_report", "configure_runtime"]
 
 
 def __getattr__(name):
@@ -88,4 +88,8 @@ def __getattr__(name):
     if name in ("DeviceDataset", "BatchSource"):
         from . import dataset
         return getattr(dataset, name)
+    if name in ("metrics", "quality_sums", "quality_report"):
+        import importlib
+        mod = importlib.import_module(".metrics", __name__)
+        return mod if name == "metrics" else getattr(mod, name)
     raise AttributeError(name)

@@ -303,6 +303,9 @@ _SIGS = {
     "ld_ds_mri_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, f32, f32, f32, C.c_int, vp, vp, vp, vp]),
     "ld_ds_seg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, f32, vp, vp, vp]),
     "ld_ds_mnist_cls_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "ld_metric_taps": (C.c_int, [C.POINTER(f32)]),
+    "ld_metric_work_doubles": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ld_metric_sums": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
     "ld_comm_unique_id": (C.c_int, [vp]),
     "ld_comm_init": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
     "ld_comm_init_timeout": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_double]),

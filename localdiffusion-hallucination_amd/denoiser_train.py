@@ -226,6 +226,32 @@ class EmulatedRank:
         raise RuntimeError("EmulatedRank has no collective: pass apply(gathered=...)")
 
 
+def sharded_eval_loss(gathered, sizes, world):
+    """The host half of ``DenoiserTrainer.evaluate(sharded=True)``; needs no GPU.  ``gathered``: ``[world, rows, 2]`` float64
+    (numpy), copy ``r`` being rank ``r``'s table of per-row ``(sse, n_elem)`` over the rows of all test batches; ``sizes``: the
+    batches' row counts.  Each row's pair is read from the copy of the rank that owns the row (``dist.patch_owner`` of its
+    index in its batch) -- whatever another copy holds there is ignored and nothing is added across ranks; per batch the
+    rows' sums are added in row order and divided by the element count; the result is the mean over the batches in batch
+    order.  All in fp64, in one order: every rank gets the same Python float."""
+    from .dist import patch_owner
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 1:
+        raise ValueError(f"sharded_eval_loss: batch sizes {sizes}")
+    if getattr(gathered, "ndim", 0) != 3 or tuple(gathered.shape) != (world, sum(sizes), 2) or str(gathered.dtype) != "float64":
+        raise ValueError(f"sharded_eval_loss: gathered must be float64 [{world}, {sum(sizes)}, 2], got "
+                         f"{getattr(gathered, 'dtype', None)} {tuple(getattr(gathered, 'shape', ()))}")
+    total, at = 0.0, 0
+    for size in sizes:
+        sse, count = 0.0, 0.0
+        for i in range(size):
+            owner = patch_owner(i, size, world)
+            sse += float(gathered[owner, at + i, 0])
+            count += float(gathered[owner, at + i, 1])
+        total += sse / count
+        at += size
+    return total / len(sizes)
+
+
 def _positive(name, v, zero_ok=False):
     if not isinstance(v, (int, float)) or isinstance(v, bool) or math.isnan(v) or v < 0 or (v == 0 and not zero_ok):
         raise ValueError(f"DenoiserTrainer: {name} = {v!r} must be a {'non-negative' if zero_ok else 'positive'} number")
@@ -659,9 +685,30 @@ class DenoiserTrainer:
         self.diffusion.model.load_state_dict(self.ema_state_dict())          # (``Unet.load_state_dict`` invalidates its plans)
 
     @torch.no_grad()
-    def evaluate(self, batches, min_max_val):
+    def evaluate(self, batches, min_max_val, sharded=False, gathered=None):
         """ddpm.py:1574-1587: sample every ``(hr, lr)`` test batch from ``lr`` with the EMA weights and return the mean over
-        the batches of the mean squared error to ``hr``."""
+        the batches of the mean squared error to ``hr``.
+
+        ``sharded=True``: rank ``r`` samples only rows ``dist.shard_bounds(B_k, world, r)`` of test batch ``k``
+        (``evaluate_local``), ONE all-gather over the path ``_exchange`` uses leaves every rank's fp64 table of per-row
+        ``(sse, n_elem)`` on every rank, and every rank computes ``sharded_eval_loss`` of it on the host: each row's value from
+        its owner's copy, nothing added across ranks, so every rank returns the same Python float and takes the same "new
+        best" decision.  The squared errors are summed in fp64 (``ld_metric_sums``) where the unsharded path takes fp32
+        ``mse_loss``, so the two agree to fp32's summation error, not bit for bit.  ``gathered``: a ready
+        ``[world, rows, 2]`` fp64 tensor in place of the collective (an ``EmulatedRank`` needs it).  At world 1 the same path
+        runs on one rank."""
+        if sharded:
+            batches = list(batches)
+            send = self.evaluate_local(batches, min_max_val)
+            sizes = [int(hr.shape[0]) for hr, _ in batches]
+            if gathered is None:
+                gathered = self._exchange_eval(send)
+            elif not (isinstance(gathered, torch.Tensor) and gathered.dtype == torch.float64
+                      and tuple(gathered.shape) == (self.world,) + tuple(send.shape)):
+                raise ValueError(f"DenoiserTrainer: gathered must be a [{self.world}, {send.shape[0]}, 2] fp64 tensor")
+            return sharded_eval_loss(gathered.cpu().numpy(), sizes, self.world)          # (the evaluation's one wait)
+        if gathered is not None:
+            raise ValueError("DenoiserTrainer: gathered is an argument of evaluate(sharded=True)")
         self.sync_ema()
         losses = []
         for hr, lr in batches:
@@ -671,6 +718,59 @@ class DenoiserTrainer:
         if not losses:
             raise ValueError("DenoiserTrainer: no test batches")
         return sum(losses) / len(losses)
+
+    @torch.no_grad()
+    def evaluate_local(self, batches, min_max_val):
+        """The part of ``evaluate(sharded=True)`` in front of the collective: sample this rank's rows of every test batch
+        (``dist._sample_shard``: the noise stream stands at the shard's first row, so a row is what the whole batch would have
+        made of it; a rank without rows in a batch calls ``dist._idle_rank_advances``), ``ld_metric_sums`` on them, and the
+        whole-image ``(sse, n_elem)`` of each row into its slot of one fp64 ``[rows of all batches, 2]`` table on the device,
+        zeros elsewhere.  Returns that table, the rank's send buffer.  The metric launches and the table writes do not wait for
+        the GPU: the call waits no more than ``sync_ema`` and ``sample`` do."""
+        from . import dist
+        from .metrics import quality_sums
+        batches = list(batches)
+        if not batches:
+            raise ValueError("DenoiserTrainer: no test batches")
+        self.sync_ema()
+        sizes = [int(hr.shape[0]) for hr, _ in batches]
+        table = torch.zeros(sum(sizes), 2, dtype=torch.float64, device=self.device)
+        at = 0
+        for (hr, lr), size in zip(batches, sizes):
+            lo, hi = dist.shard_bounds(size, self.world, self.rank)
+            if hi > lo:
+                cond = lr[lo:hi].to(self.device, torch.float32)
+                out = dist._sample_shard(self.diffusion, lo, hi, hr[0].numel(), lambda: self.diffusion.sample(
+                    cond, None, batch_size=hi - lo, mask=None, min_max_val=min_max_val))
+                # (data_range only enters the SSIM fields, which this table does not take)
+                sums = quality_sums(out.to(torch.float32), hr[lo:hi].to(self.device, torch.float32), None, data_range=1.0)
+                table[at + lo:at + hi, 0] = sums[:, 0, 1]
+                table[at + lo:at + hi, 1] = sums[:, 0, 0]
+            else:
+                dist._idle_rank_advances(self.diffusion, None)
+            at += size
+        return table
+
+    def _exchange_eval(self, send):
+        """The sharded evaluation's one collective: every rank's table into ``[world, rows, 2]``, over ``_exchange``'s path."""
+        if not self.data_parallel:
+            return send[None]
+        if isinstance(self.comm, EmulatedRank):
+            raise RuntimeError("EmulatedRank has no collective: pass evaluate(sharded=True, gathered=...)")
+        recv = torch.empty((self.world,) + tuple(send.shape), dtype=send.dtype, device=send.device)
+        with cabi.prof_range("exchange"):
+            if self.comm is not None:
+                with torch.cuda.device(self.device):
+                    self.comm.all_gather(send, recv)
+            elif self.staged_gather:                       # gloo: host tensors (waits for the GPU; test-only)
+                import torch.distributed as tdist
+                host = torch.empty(recv.shape, dtype=recv.dtype)
+                tdist.all_gather_into_tensor(host.view(-1), send.cpu().view(-1), group=self.group)
+                recv = host
+            else:
+                import torch.distributed as tdist
+                tdist.all_gather_into_tensor(recv.view(-1), send.view(-1), group=self.group)
+        return recv
 
     def state(self):
         """``checkpoint_dict``'s result for this trainer (CPU tensors)."""
@@ -735,7 +835,7 @@ class DenoiserTrainer:
         return info
 
     # ------------------------------------------------------------------ the loop
-    def fit(self, batches, test_batches, num_steps, save_and_sample_every, out_dir, min_max_val=None):
+    def fit(self, batches, test_batches, num_steps, save_and_sample_every, out_dir, min_max_val=None, sharded_eval=False):
         """``Trainer.train`` (ddpm.py:1532-1606) until ``step == num_steps``: ``train_step(batches)`` (a list, trained on as it is
         at every step, or a ``BatchSource``, reshuffled and re-augmented at every step); every
         ``save_and_sample_every`` steps ``evaluate(test_batches)`` and, at a new best, ``save`` to
@@ -743,8 +843,11 @@ class DenoiserTrainer:
         layout pandas gives the reference's frames (an index column, ``epoch``, ``loss``); ``train_loss.csv`` holds every
         step (the reference appends each step's row to the evaluation frame, so its file keeps only the last one).
         ``min_max_val`` defaults to the reference's per data set (ddpm.py:1474-1489).  Returns the best evaluation loss.
-        Data-parallel: every rank evaluates every test batch (redundant, but no rank sits in a collective for minutes), only
-        rank 0 writes the files, and ``replica_digest()`` runs at every evaluation point."""
+        Data-parallel: by default every rank evaluates every test batch (redundant, but no rank sits in a collective for
+        minutes); ``sharded_eval=True`` evaluates with ``evaluate(sharded=True)`` -- every rank samples its rows of each test
+        batch and one all-gather of the per-row error sums gives every rank the same float, so the replicas take the same "new
+        best" decision (the loss is an fp64 sum there: equal to the default's to fp32's summation error, not bit for bit).
+        Only rank 0 writes the files, and ``replica_digest()`` runs at every evaluation point."""
         data = str(self.diffusion.config.get("data", ""))
         if min_max_val is None:
             min_max_val = (0.0, 1.0) if data == "mnist" else (-1.0, 1.0) if data == "mri" else (0.0, 2.0)
@@ -765,7 +868,7 @@ class DenoiserTrainer:
             if self.step % save_and_sample_every == 0:
                 if self.world > 1:
                     self.replica_digest()                     # (one wait beside a full sampling run)
-                ls = self.evaluate(test_batches, min_max_val)
+                ls = self.evaluate(test_batches, min_max_val, sharded=bool(sharded_eval))
                 if best > ls:
                     best = ls
                     num = 100 if data == "mnist" else 500

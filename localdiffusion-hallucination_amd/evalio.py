@@ -241,8 +241,28 @@ def patchcore_ood_mask(anomaly_map, rule, img_size=None):
     return m ** 2, binary
 
 
-def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda", batch_size=1):
-    """test.py's loop: sample every LR image, compare with HR.  Returns a dict of metrics."""
+def print_quality(quality):
+    """One line per region of a ``quality`` report (``evaluate(metrics=True)``)."""
+    for region in ("all", "ood", "ind"):
+        q = quality[region]
+        print(f"{region:>3}: MSE {q['mean_mse']:.6f}  PSNR {q['mean_psnr']:.2f} dB  SSIM {q['mean_ssim']:.4f}  "
+              f"({q['n_images']} images)")
+
+
+def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda", batch_size=1, metrics=False, data_range=None):
+    """test.py's loop: sample every LR image, compare with HR.  Returns a dict of metrics.
+
+    ``metrics=True`` adds ``"quality"``: ``metrics.quality_report`` of the final fused image against ``hr`` over ALL channels,
+    with ``masks`` as the region mask (``"all"`` / ``"ood"`` = mask >= 1 / ``"ind"``: per-image ``mse``, ``psnr``, ``ssim``, their
+    means and the counts), computed on the device with one read-back at the end, and ``metrics.json`` in ``out_dir``.
+    ``data_range`` defaults to ``min_max_val[1] - min_max_val[0]``.  ``test_loss`` keeps the reference's definition -- the LAST
+    channel only (test.py:416), a mean of per-batch fp32 means -- so for 3-channel data it is not ``quality["all"]["mse"]``.
+    A result that is not one fused [n, C, H, W] image per input (the two-branch layouts) is a ``ValueError`` with it."""
+    if metrics:
+        from . import metrics as _metrics
+        if data_range is None:
+            data_range = float(min_max_val[1]) - float(min_max_val[0])
+        sums = []
     preds, losses, times = [], [], []
     n = hr.shape[0]
     for i in range(0, n, batch_size):
@@ -258,12 +278,19 @@ def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda",
         times.append(time.time() - t0)
         if isinstance(out, list):
             out = torch.stack(out)
+        if metrics:
+            if out.dim() != 4 or out.shape[0] != cond.shape[0]:
+                raise ValueError(f"evaluate(metrics=True): the sampler returned {tuple(out.shape)}, not one fused image per input")
+            sums.append(_metrics.quality_sums(out.detach().to(torch.float32), hr[sl].to(device, torch.float32),
+                                              None if mask is None else mask.to(torch.float32), data_range=data_range))
         out = out.detach().cpu()
         losses.append(float(torch.nn.functional.mse_loss(out[..., [-1], :, :] if out.dim() == 4 else out[-1][:, [-1]],
                                                          hr[sl][:, [-1]])))
         preds.append(out.numpy())
     res = {"test_loss": float(np.mean(losses)), "avg_sampling_time": float(np.mean(times)),
            "n": n, "pred": np.concatenate(preds) if preds[0].ndim == 4 else np.stack(preds)}
+    if metrics:
+        res["quality"] = _metrics.report_from_sums(torch.cat(sums).cpu().numpy(), data_range)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         np.save(os.path.join(out_dir, "hr_all.npy"), hr.numpy())
@@ -271,4 +298,8 @@ def evaluate(diffusion, hr, lr, masks, min_max_val, out_dir=None, device="cuda",
         np.save(os.path.join(out_dir, "pred_all.npy"), res["pred"])
         if masks is not None:
             np.save(os.path.join(out_dir, "ad_masks.npy"), masks.numpy())
+        if metrics:
+            import json
+            with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+                json.dump(dict(_metrics.report_to_json(res["quality"]), test_loss=res["test_loss"], n=n), f, indent=1)
     return res

@@ -4,7 +4,7 @@ reads MNIST idx files, builds LR/HR pairs and the band mask, samples with branch
 prints "Test loss" / "Average sampling time" and writes hr_all / lr_all / pred_all / ad_masks .npy.
 
   python tools/run_eval.py --images MNIST/raw/t10k-images-idx3-ubyte.gz --labels MNIST/raw/t10k-labels-idx1-ubyte.gz \\
-         [--checkpoint results/.../model-best2900.pt] [--digit 3] [--n 4] [--timesteps 100] [--out eval_out]
+         [--checkpoint results/.../model-best2900.pt] [--digit 3] [--n 4] [--timesteps 100] [--out eval_out] [--metrics]
 Without --checkpoint the procedural weights of the tests are used (no trained weights ship with the reference).
 """
 import argparse
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--ddim", type=int, default=0, help="sampling_timesteps (0 = ancestral DDPM)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--metrics", action="store_true",
+                    help="MSE / PSNR / SSIM per image and per region (whole image, OOD mask, the rest); metrics.json with --out")
     a = ap.parse_args()
     imgs, labs = evalio.select_digits(evalio.read_idx(a.images), evalio.read_idx(a.labels), a.digit, a.n)
     hr, lr = evalio.mnist_pairs(imgs)
@@ -44,9 +46,11 @@ def main():
     if a.checkpoint:
         print("checkpoint:", checkpoint.load_reference_checkpoint(a.checkpoint, gd))
     gd = gd.to("cuda")
-    res = evalio.evaluate(gd, hr, lr, masks, (0.0, 2.0), out_dir=a.out)
+    res = evalio.evaluate(gd, hr, lr, masks, (0.0, 2.0), out_dir=a.out, metrics=a.metrics)
     print("Test loss: {:.4f}".format(res["test_loss"]))
     print("Average sampling time: {:.4f}".format(res["avg_sampling_time"]))
+    if a.metrics:
+        evalio.print_quality(res["quality"])
 
 
 if __name__ == "__main__":

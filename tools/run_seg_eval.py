@@ -6,7 +6,7 @@ loader leaves them; BRATS PNG decoding is not part of this), builds the OOD mask
 writes hr_all / lr_all / pred_all / ad_masks .npy.
 
   python tools/run_seg_eval.py --lr lr.npy --hr hr.npy [--seg-model t1seg.pth] [--checkpoint model-best.pt]
-         [--timesteps 1000] [--ddim 0] [--out eval_out]
+         [--timesteps 1000] [--ddim 0] [--out eval_out] [--metrics]
 Without --seg-model / --checkpoint the procedural weights of the tests are used (no trained weights ship with the reference).
 """
 import argparse
@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--mean-t1", type=float, default=MEAN_T1)
     ap.add_argument("--std-t1", type=float, default=STD_T1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--metrics", action="store_true",
+                    help="MSE / PSNR / SSIM per image and per region (whole image, OOD mask, the rest); metrics.json with --out")
     a = ap.parse_args()
     lr = torch.from_numpy(np.load(a.lr).astype(np.float32))
     hr = torch.from_numpy(np.load(a.hr).astype(np.float32))
@@ -68,9 +70,11 @@ def main():
         print("checkpoint:", checkpoint.load_reference_checkpoint(a.checkpoint, gd))
     gd = gd.to("cuda")
     lo_hi = (float(min(lr.min(), hr.min())), float(max(lr.max(), hr.max())))
-    res = evalio.evaluate(gd, hr, lr, masks, lo_hi, out_dir=a.out)
+    res = evalio.evaluate(gd, hr, lr, masks, lo_hi, out_dir=a.out, metrics=a.metrics)
     print("Test loss: {:.4f}".format(res["test_loss"]))
     print("Average sampling time: {:.4f}".format(res["avg_sampling_time"]))
+    if a.metrics:
+        evalio.print_quality(res["quality"])
 
 
 if __name__ == "__main__":

@@ -26,14 +26,15 @@ reference, and the whole data set is held on the GPU.
   python tools/train_denoiser.py --data mnist --store images.npy --labels labels.npy [--augmentations] [--no-shuffle]
   python tools/train_denoiser.py --data mnist --hr hr.npy --lr lr.npy [--steps 1000] [--batch-size 32] [--timesteps 250]
          [--objective pred_v] [--train-lr 1e-4] [--save-every 100] [--init model.pt] [--out results/denoiser]
-         [--gpus N] [--rank-timeout 86400] [--grace 30]
+         [--gpus N] [--rank-timeout 86400] [--grace 30] [--sharded-eval]
 Writes <out>/model-best<step rounded up>.pt (whenever the evaluation loss improves), train_loss.csv, loss.csv.
 
 ``--gpus N`` (one node): the tool starts N fresh rank processes of itself (``launch.launch_ranks``; this process makes no GPU
 call), each on its own GPU over RCCL (torch.distributed's "nccl").  ``--batch-size`` stays the GLOBAL batch: rank r trains on
 its rows of every batch (the reference's ``Accelerator(split_batches=True)``), the gradients are summed in rank order, and the
 replicas hold the same bits after every step; every batch size must be a multiple of N.  All ranks are seeded alike, every rank
-evaluates, rank 0 writes the files, and every rank prints its ``replica_digest()`` at the end.  ``--rank-timeout`` bounds the
+evaluates (every validation batch by default; with ``--sharded-eval`` its rows of each, one all-gather of the per-row error sums
+giving every rank the same loss), rank 0 writes the files, and every rank prints its ``replica_digest()`` at the end.  ``--rank-timeout`` bounds the
 whole run, ``--grace`` is what the other ranks get once one has failed.  ``--share-gpu`` is for tests only: the ranks share the
 visible GPUs, which RCCL refuses, so they meet over gloo and the gradient exchange is staged through pinned host memory -- a
 functional path, never a measurement; the log line says so.
@@ -99,6 +100,8 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node, one GPU each")
     ap.add_argument("--rank-timeout", type=float, default=86400.0, help="--gpus > 1: seconds that bound the whole run")
     ap.add_argument("--grace", type=float, default=30.0, help="--gpus > 1: seconds the other ranks get after one has failed")
+    ap.add_argument("--sharded-eval", action="store_true",
+                    help="evaluate with DenoiserTrainer.evaluate(sharded=True): every rank samples its rows of each validation batch")
     ap.add_argument("--share-gpu", action="store_true",
                     help="tests only: the ranks share the visible GPUs over gloo, gradients staged through host memory")
     a = ap.parse_args(argv)
@@ -239,7 +242,7 @@ def main(argv=None):
         kw = dict(group="default")
     trainer, train, val = setup(a, **kw)
     torch.manual_seed(a.seed)                                # every rank alike: t comes from this generator
-    best = trainer.fit(train, val, a.steps, a.save_every, a.out)
+    best = trainer.fit(train, val, a.steps, a.save_every, a.out, sharded_eval=a.sharded_eval)
     if rank == 0:
         n_train = len(train.dataset) if a.store is not None else sum(b[0].shape[0] for b in train)
         print(f"train images {n_train}, validation images {sum(b[0].shape[0] for b in val)}, "
