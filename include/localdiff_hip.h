@@ -185,6 +185,12 @@ typedef struct ld_conv3x3_args {
                            /* side_out NHWC [B,H,W,Cout] = W_side x + side_bias (no statistics).  NULL = none.              */
 } ld_conv3x3_args;
 int ld_conv3x3(const ld_conv3x3_args* args, void* stream);
+/* The kernel ld_conv3x3 would launch for *args under the current routing table, as an LD_ROUTE_CONV3X3 word,
+   without launching anything; a negative LD_E* code where ld_conv3x3 would refuse the arguments (ld_last_error
+   set as ld_conv3x3 sets it).  Pointers are tested for null only.  Needs no GPU.  Does not change ld_last_route.
+   It IS the decision ld_conv3x3 launches by, not a copy of it (a library built with --debug-variants can override the
+   decision from the environment in ways this query does not predict). */
+long long ld_conv3x3_route(const ld_conv3x3_args* args);
 
 /* ---- 1x1 convolution (GEMM over channels) -------------------------------------------------- */
 #define LD_EPI_PLAIN 0      /* out = W x + b                                                    */

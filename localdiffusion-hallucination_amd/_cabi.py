@@ -126,6 +126,7 @@ _SIGS = {
     "ld_range_push": (C.c_int, [C.c_char_p]),
     "ld_range_pop": (C.c_int, []),
     "ld_conv3x3": (C.c_int, [C.POINTER(Conv3x3Args), vp]),
+    "ld_conv3x3_route": (C.c_longlong, [C.POINTER(Conv3x3Args)]),
     "ld_conv1x1": (C.c_int, [C.POINTER(Conv1x1Args), vp]),
     "ld_pack_conv_weight": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ld_pack_conv_weight_terms": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

@@ -29,6 +29,15 @@ static inline long long ld_route3(int family, int mt, int nw, bool raw, bool sk,
 static inline long long ld_route1(int mt, int nw, int epi, int g, int lead) {
   return (long long)mt | (nw << 4) | (epi << 8) | (g << 12) | (lead << 16);
 }
+// ld_conv3x3's two special kernels, each as a pure host decision over validated arguments and the routing table, and the
+// launch that carries the decision out.  conv3x3.hip composes them with the generic kernel's tile choice into the ONE
+// routing decision (conv3x3_route there) that ld_conv3x3 launches by and ld_conv3x3_route reports; no eligibility test
+// lives anywhere else.
+bool ld_conv3x3_c32_takes(const ld_conv3x3_args* p);                       // conv3x3_c32.hip: the persistent LDS-DMA kernel
+int ld_conv3x3_c32_launch(const ld_conv3x3_args* p, hipStream_t st);
+enum LdS32Form { LD_S32_NONE = 0, LD_S32_ONE_CHUNK, LD_S32_PROLOGUE, LD_S32_TWO_CHUNKS };
+LdS32Form ld_conv3x3_s32_form(const ld_conv3x3_args* p);                   // conv3x3_s32.hip: the lean kernel, and which of its forms
+int ld_conv3x3_s32_launch(const ld_conv3x3_args* p, LdS32Form form, hipStream_t st);
 #define LD_HIP(call)                                                                  \
   do {                                                                                 \
     hipError_t e_ = (call);                                                            \

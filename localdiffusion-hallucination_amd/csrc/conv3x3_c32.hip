@@ -479,33 +479,40 @@ int launch_c32_lite(const C32Dev& a0, hipStream_t st) {
 
 }  // namespace
 
-// Returns 1 if this launch is handled here, 0 if the generic kernel must take it, <0 on error.
-int ld_conv3x3_c32_try(const ld_conv3x3_args* p, hipStream_t st) {
+#ifdef LD_DEBUG_VARIANTS
+// experiment (finding 66): launches of LD_CONV_C32_LITE .. min_tiles - 1 tiles -- the 4-patch launches of the
+// two-sub-batch regime -- on the 256-thread geometry (0 = off)
+static bool c32_lite(const ld_conv3x3_args* p, long tiles) {
+  static const long lite_min = getenv("LD_CONV_C32_LITE") ? atol(getenv("LD_CONV_C32_LITE")) : 0;
+  return lite_min > 0 && tiles >= lite_min && tiles < ld_tuning().conv_c32_min_tiles && p->dtype != LD_F32;
+}
+#else
+static constexpr bool c32_lite(const ld_conv3x3_args*, long) { return false; }
+#endif
+
+// Does the persistent kernel take these (validated) arguments under the current routing table?
+bool ld_conv3x3_c32_takes(const ld_conv3x3_args* p) {
   const LdTuning& tn = ld_tuning();
-  if (!tn.conv_c32 || p->addend || p->Cout != 32 || p->H < 32 || p->W < 32 || p->H % 16 != 0 || p->W % 16 != 0) return 0;
+  if (p->weight_terms == 2) return false;              // (the kernel keeps ONE chunk of weights in registers)
+  if (!tn.conv_c32 || p->addend || p->Cout != 32 || p->H < 32 || p->W < 32 || p->H % 16 != 0 || p->W % 16 != 0) return false;
   const int ck = p->dtype == LD_F32 ? 16 : 32;
   int ctot = 0;
   for (int s = 0; s < p->nsrc; ++s) ctot += p->src[s].C;
   // Single K-chunk only: measured in situ (cfg3) the ring gains 1-4 us per 32->32 @256^2 launch over the
   // register-staged kernel but LOSES 1-6 us on the two-chunk 64->32 ones (the kernel template still carries NCH).
-  if (ctot != ck || p->nsrc != 1) return 0;
-  if (p->out_stats && (p->out_groups <= 0 || 32 % p->out_groups != 0)) return 0;
-  const long min_tiles = tn.conv_c32_min_tiles;
+  if (ctot != ck || p->nsrc != 1) return false;
+  if (p->out_stats && (p->out_groups <= 0 || 32 % p->out_groups != 0)) return false;
   const long tiles = (long)(p->W / 16) * (p->H / 16) * p->B;
-#ifdef LD_DEBUG_VARIANTS
-  // experiment (finding 66): launches of LD_CONV_C32_LITE .. min_tiles - 1 tiles -- the 4-patch launches of the
-  // two-sub-batch regime -- on the 256-thread geometry (0 = off)
-  static const long lite_min = getenv("LD_CONV_C32_LITE") ? atol(getenv("LD_CONV_C32_LITE")) : 0;
-  static const int lite_ring = getenv("LD_CONV_C32_LITE_R") ? atoi(getenv("LD_CONV_C32_LITE_R")) : 4;
-  const bool lite = lite_min > 0 && tiles >= lite_min && tiles < min_tiles && p->dtype != LD_F32;
-#else
-  constexpr bool lite = false;
-#endif
-  if (tiles < min_tiles && !lite) return 0;            // too few tiles to amortise a persistent workgroup
+  if (tiles < tn.conv_c32_min_tiles && !c32_lite(p, tiles)) return false;   // too few tiles to amortise a persistent workgroup
   for (int s = 0; s < p->nsrc; ++s) {                  // the kernel uses 32-bit element offsets
     const long ld = p->src[s].pix_stride > 0 ? p->src[s].pix_stride : p->src[s].C;
-    if ((long)p->B * p->H * p->W * ld >= (1L << 31)) return 0;
+    if ((long)p->B * p->H * p->W * ld >= (1L << 31)) return false;
   }
+  return true;
+}
+
+// The launch of a call ld_conv3x3_c32_takes took.
+int ld_conv3x3_c32_launch(const ld_conv3x3_args* p, hipStream_t st) {
   C32Dev a;
   a.nsrc = p->nsrc;
   for (int s = 0; s < p->nsrc; ++s) a.s[s] = to_dev(p->src[s]);
@@ -519,7 +526,8 @@ int ld_conv3x3_c32_try(const ld_conv3x3_args* p, hipStream_t st) {
   static const int dbg = getenv("LD_CONV_DEBUG") ? atoi(getenv("LD_CONV_DEBUG")) : 0;
   a.dbg = dbg;
   static const int ring = getenv("LD_CONV_C32_R") ? atoi(getenv("LD_CONV_C32_R")) : 6;
-  if (lite) {
+  static const int lite_ring = getenv("LD_CONV_C32_LITE_R") ? atoi(getenv("LD_CONV_C32_LITE_R")) : 4;
+  if (c32_lite(p, (long)(p->W / 16) * (p->H / 16) * p->B)) {
     if (p->dtype == LD_F16) rc = lite_ring == 6 ? launch_c32_lite<f16, 6>(a, st) : launch_c32_lite<f16, 4>(a, st);
     else rc = lite_ring == 6 ? launch_c32_lite<bf16, 6>(a, st) : (lite_ring == 3 ? launch_c32_lite<bf16, 3>(a, st) : launch_c32_lite<bf16, 4>(a, st));
   } else if (p->dtype == LD_BF16 && ring == 4) rc = launch_c32<bf16, 1, 4>(a, st);
@@ -532,7 +540,7 @@ int ld_conv3x3_c32_try(const ld_conv3x3_args* p, hipStream_t st) {
   else if (p->dtype == LD_F16) rc = launch_c32<f16, 1, 6>(a, st);
   else rc = launch_c32<bf16, 1, 6>(a, st);
   if (rc == LD_OK) ld_count(LD_COUNTER_CONV3X3_C32);
-  return rc == LD_OK ? 1 : rc;
+  return rc;
 }
 
 // Debug hook (not part of the public ABI): cycle stamps of the last LD_CONV_DEBUG&32 launch (16 uint64).

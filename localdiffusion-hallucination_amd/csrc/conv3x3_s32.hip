@@ -21,7 +21,7 @@
 //   * the output leaves by write-through stores (store16_out, common.hip.h; finding 98): 32->32 @256^2 x 4 patches alone
 //     9.3 / 9.6 / 13.6 us (plain / statistics / prologue) = 0.50 / 0.48 / 0.34 of 8 TB/s, x 8 patches 13.4 / 15.2 / 23.5 (0.63 /
 //     0.55 / 0.36) -- which also retired the persistent LDS-DMA kernel (conv3x3_c32.hip) from the default routing (finding 99).
-// Routing: ld_conv3x3_s32_try (below); everything it does not take falls through to the generic kernel.
+// Routing: ld_conv3x3_s32_form (below) says whether this kernel takes a call; conv3x3.hip's conv3x3_route composes it with the rest.
 #include "common.hip.h"
 
 namespace {
@@ -296,41 +296,47 @@ int launch_s32(const ld_conv3x3_args* p, hipStream_t st) {
 
 }  // namespace
 
-// Returns 1 if this launch is handled here, 0 if another kernel must take it, < 0 on error.
-int ld_conv3x3_s32_try(const ld_conv3x3_args* p, hipStream_t st) {
+// Does the lean kernel take these (validated) arguments under the current routing table, and in which of its forms?
+LdS32Form ld_conv3x3_s32_form(const ld_conv3x3_args* p) {
   const LdTuning& tn = ld_tuning();
-  if (!tn.conv_s32 || !ld_dtype_16(p->dtype) || p->Cout != 32 || p->addend || p->weight_terms == 2) return 0;
-  if (p->H % 16 != 0 || p->W % 16 != 0 || p->H >= 65536 || p->W >= 32768) return 0;
+  if (!tn.conv_s32 || !ld_dtype_16(p->dtype) || p->Cout != 32 || p->addend || p->weight_terms == 2) return LD_S32_NONE;
+  if (p->H % 16 != 0 || p->W % 16 != 0 || p->H >= 65536 || p->W >= 32768) return LD_S32_NONE;
   const long tiles = (long)(p->W / 16) * (p->H / 16) * p->B;
-  if (tiles < tn.conv_s32_min_tiles) return 0;
+  if (tiles < tn.conv_s32_min_tiles) return LD_S32_NONE;
   int ctot = 0;
   bool pro = false;
   for (int s = 0; s < p->nsrc; ++s) {
     const ld_src& S = p->src[s];
-    if (S.upsample) return 0;
+    if (S.upsample) return LD_S32_NONE;
     const long ld = S.pix_stride > 0 ? S.pix_stride : S.C;
-    if ((long)p->H * p->W * ld * 2 >= (1L << 32)) return 0;          // 32-bit byte offsets inside an image
+    if ((long)p->H * p->W * ld * 2 >= (1L << 32)) return LD_S32_NONE;          // 32-bit byte offsets inside an image
     ctot += S.C;
     pro = pro || S.gn_stats != nullptr;
   }
-  if (ctot != 32 && ctot != 64) return 0;
-  if (p->nsrc == 2 && (p->src[0].C != 32 || p->src[1].C != 32)) return 0;
+  if (ctot != 32 && ctot != 64) return LD_S32_NONE;
+  if (p->nsrc == 2 && (p->src[0].C != 32 || p->src[1].C != 32)) return LD_S32_NONE;
   if (pro) {
     // the register-coefficient prologue: one 32-channel source, 8 groups, the timestep's FiLM row at a fixed address
     const ld_src& S = p->src[0];
-    if (p->nsrc != 1 || S.C != 32 || S.gn_groups != 8 || p->t_ptr != nullptr) return 0;
-    if (!S.gn_gamma || !S.gn_beta) return 0;
+    if (p->nsrc != 1 || S.C != 32 || S.gn_groups != 8 || p->t_ptr != nullptr) return LD_S32_NONE;
+    if (!S.gn_gamma || !S.gn_beta) return LD_S32_NONE;
   }
   if (p->out_stats) {
     const int og = p->out_groups;
-    if (og <= 0 || 32 % og != 0 || 32 / og < 4) return 0;
+    if (og <= 0 || 32 % og != 0 || 32 / og < 4) return LD_S32_NONE;
   }
   // conv_s32 is a bit mask: 1 = single-chunk launches without a prologue, 2 = with the GroupNorm prologue, 4 = two chunks
-  if (!(tn.conv_s32 & (pro ? 2 : (ctot == 32 ? 1 : 4)))) return 0;
+  const LdS32Form form = pro ? LD_S32_PROLOGUE : (ctot == 32 ? LD_S32_ONE_CHUNK : LD_S32_TWO_CHUNKS);
+  const int bit = form == LD_S32_PROLOGUE ? 2 : (form == LD_S32_ONE_CHUNK ? 1 : 4);
+  return (tn.conv_s32 & bit) ? form : LD_S32_NONE;
+}
+
+// The launch of a call ld_conv3x3_s32_form took, in that form.
+int ld_conv3x3_s32_launch(const ld_conv3x3_args* p, LdS32Form form, hipStream_t st) {
   int rc;
-  if (pro) rc = LD_DISPATCH16(p->dtype, launch_s32<T, 1, true>(p, st));
-  else if (ctot == 32) rc = LD_DISPATCH16(p->dtype, launch_s32<T, 1, false>(p, st));
+  if (form == LD_S32_PROLOGUE) rc = LD_DISPATCH16(p->dtype, launch_s32<T, 1, true>(p, st));
+  else if (form == LD_S32_ONE_CHUNK) rc = LD_DISPATCH16(p->dtype, launch_s32<T, 1, false>(p, st));
   else rc = LD_DISPATCH16(p->dtype, launch_s32<T, 2, false>(p, st));
   if (rc == LD_OK) ld_count(LD_COUNTER_CONV3X3_S32);
-  return rc == LD_OK ? 1 : rc;
+  return rc;
 }

@@ -35,14 +35,13 @@ def peak_live(size: Sequence[int], first: Sequence[int], last: Sequence[int]) ->
 
 
 def check_declared(declared: Sequence[set], scanned: Sequence[set], op_names: Sequence[str], buf_names: Sequence[str]) -> None:
-    """A plan's launches DECLARE the pooled buffers they read and write (``_Plan.decl``); the reflection scan of the same
-    launches (pointers in ctypes argument blocks, tensors captured by raw launches) is the cross-check -- and the only
-    thing that can PATCH a pointer.  They must agree launch by launch:
-      * a buffer the scan finds but the launch does not declare would get no liveness from the declarations: its memory
-        would be re-used while the launch still touches it;
-      * a buffer a launch declares but the scan cannot find is held in a form that cannot be re-pointed at the pool (a
-        plain integer, a pointer computed past a tracked range, a tensor inside an object): the launch would keep reading
-        or writing the freed allocation.
+    """A plan's launch records DECLARE the pooled buffers they read and write (``_Launch.reads`` / ``writes``: ``declared``);
+    what each record HOLDS (``scanned``: pointer-typed fields of its ctypes argument block, tensors of its positional argument
+    list) is the cross-check -- and the only thing that can be patched or re-pointed.  They must agree launch by launch:
+      * a buffer a launch holds but does not declare would get no liveness from the declarations: its memory would be
+        re-used while the launch still touches it;
+      * a buffer a launch declares but does not hold is passed in a form that cannot be re-pointed at the pool (a plain
+        integer, a pointer computed past a tracked range): the launch would keep reading or writing the freed allocation.
     Either is a RuntimeError that names the launch and the buffer."""
     for i, (d, f) in enumerate(zip(declared, scanned)):
         extra, missing = sorted(f - d), sorted(d - f)
@@ -51,7 +50,8 @@ def check_declared(declared: Sequence[set], scanned: Sequence[set], op_names: Se
                                "declare in reads= / writes=: their liveness would be wrong")
         if missing:
             raise RuntimeError(f"pool: launch {i} ({op_names[i]}) declares pooled buffer(s) {[buf_names[k] for k in missing]} but holds no "
-                               "patchable reference to them (a ctypes pointer field or a captured tensor): it cannot be re-pointed at the pool")
+                               "patchable reference to them (a pointer field of its argument block or a tensor in its argument list): it cannot be "
+                               "re-pointed at the pool")
 
 
 def intervals_from_declared(declared: Sequence[set], n_bufs: int, live_out: set) -> Tuple[List[int], List[int]]:

@@ -320,6 +320,44 @@ class Unet(nn.Module):
         return p.model_out.clone()
 
 
+_DNAME = {cabi.LD_F32: "f32", cabi.LD_BF16: "bf16", cabi.LD_F16: "f16"}
+
+
+def conv3x3_family(route, dtype):
+    """The family label of an LD_ROUTE_CONV3X3 word (include/localdiff_hip.h), in the spellings the committed profiles and
+    bench.py match on."""
+    d = _DNAME[dtype]
+    if route & 15:
+        return f"conv3x3_s32<{d}>" if route & 15 == 1 else f"conv3x3_c32<{d}>"
+    return f"conv3x3<{d},{(route >> 4) & 15},{(route >> 8) & 15}>"
+
+
+class _Launch:
+    """One launch of a plan: ``fn(*args, stream)`` of the library, checked; called with the stream.
+
+    ``args`` is ONE ctypes argument block, or a positional list in which a tensor stands for its device pointer and None
+    for a null pointer.  ``reads`` / ``writes`` are the tensors the launch DECLARES (the pool's liveness); what it HOLDS is
+    read off ``args`` (_Plan._pool_buffers).  ``bind()`` resolves ``args`` to what ctypes is handed, once, after pooling.
+    ``poison``: (address, bytes) regions overwritten with 0xFF behind the launch (Tuning.pool_verify)."""
+    __slots__ = ("fn", "args", "what", "meta", "reads", "writes", "bound", "poison")
+
+    def __init__(self, fn, args, what, meta=None, reads=(), writes=()):
+        self.fn, self.args, self.what = fn, args, what
+        self.meta = dict(what=what, **(meta or {}))
+        self.reads, self.writes = [t for t in reads if t is not None], [t for t in writes if t is not None]
+        self.bound, self.poison = None, ()
+
+    def bind(self):
+        a = self.args
+        self.bound = (C.byref(a),) if isinstance(a, C.Structure) else tuple(v.data_ptr() if isinstance(v, torch.Tensor) else v for v in a)
+
+    def __call__(self, st):
+        cabi.check(self.fn(*self.bound, st), self.what)
+        if self.poison:
+            for ptr, nbytes in self.poison:
+                cabi.check(cabi.lib().ld_memset_bytes(ptr, 0xFF, nbytes, st), "pool verify")
+
+
 class _Plan:
     """Static buffers + the C-ABI call list of one denoiser evaluation at a fixed shape.
 
@@ -343,10 +381,8 @@ class _Plan:
         self.keep = []
         self._track = None                         # buffers of the main trunk, while buffer_reuse collects them
         self.named = {}                            # oracle tap name -> NHWC buffer (parity tests)
-        self.meta = {}                             # index in ops_main -> {what, family, bytes, flops}
-        self.decl = {}                             # index in ops_main -> (tensors read, tensors written): what the launch DECLARES (pool liveness)
         self.live_out = []                         # tensors of the main trunk something reads AFTER the launch list (the sampler's fused final step)
-        self.ops_time, self.ops_cond, self.ops_main = [], [], []
+        self.ops_time, self.ops_cond, self.ops_main = [], [], []      # _Launch records
         self.nslot = 0
         self.stats = torch.zeros(160, B, cabi.STAT_STRIPES, 16, 2, dtype=torch.float64, device=self.dev)
         self.cond_slots = 16                       # slots [0,16) belong to the conditioning encoder
@@ -387,6 +423,9 @@ class _Plan:
         if self._track is not None:
             self._pool_buffers()
             self._track = None
+        for op in self.ops_time + self.ops_cond + self.ops_main:
+            op.bind()                              # tensors -> addresses, once, now that the pool has placed them
+        self.meta = {i: op.meta for i, op in enumerate(self.ops_main)}     # index in ops_main -> {what, family, bytes, flops, ...}
         self._slots_used = self._slot_cursor       # statistics slots [cond_slots, _slots_used) are zeroed per evaluation
         s_, km_ = self.stats[self.cond_slots:self._slots_used], self.kmax_arena[:self._kmax_cursor]
         self._begin_args = (s_.data_ptr(), s_.numel() * 8, km_.data_ptr() if km_.numel() else None, km_.numel() * 4)
@@ -404,12 +443,6 @@ class _Plan:
             torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------ helpers
-    def _kt(self, name):
-        """An entry of the library's launch-routing table (the plan's family labels follow the dispatcher's rule)."""
-        v = C.c_longlong()
-        cabi.check(self.lib.ld_tuning_get(name.encode(), C.byref(v)), "tuning_get")
-        return int(v.value)
-
     def _separate_act(self, px, c):
         """block1's GroupNorm + FiLM + SiLU as a separate pass (instead of block2's prologue): small, wide maps
         (Tuning.separate_act / sep_act_max_px / sep_act_min_c; DESIGN findings 5, 68)."""
@@ -434,13 +467,13 @@ class _Plan:
         addresses per evaluation otherwise, 2.5x the Infinity Cache, and every output line is written back to HBM before its
         address is seen again.
 
-        Liveness is DECLARED (round 6): every launch of ``ops_main`` carries the tensors it reads and writes (``self.decl``,
-        filled by the builders), tensors read after the list are in ``self.live_out``.  The launch list is still analysed as
-        it stands -- ctypes argument blocks scanned for pointers into the tracked buffers, raw launches for the tensors
-        their closures capture -- because that is what PATCHES the pointers and re-points the tensors; the scan is also
-        the cross-check of the declarations (pool.check_declared: a buffer a launch touches without declaring it, or
-        declares without a patchable reference, raises).  After patching everything is scanned again, plain integers
-        included: nothing may still point into an old allocation.  ``named`` taps of pooled buffers are dropped.
+        Liveness is DECLARED: every record of ``ops_main`` carries the tensors it reads and writes (``reads`` / ``writes``,
+        filled by the builders), tensors read after the list are in ``self.live_out``.  What a launch HOLDS is read off its
+        record: the tensors of a positional argument list, the pointer-typed fields of a ctypes block.  Those are what gets
+        PATCHED (fields) or re-pointed (tensors), and they cross-check the declarations (pool.check_declared: a buffer a
+        launch holds without declaring it, or declares without holding it, raises); a tracked address passed as a plain
+        integer cannot be re-pointed and raises too.  After patching, no pointer of any record may lie in an old
+        allocation.  ``named`` taps of pooled buffers are dropped.
         ``Tuning.pool_verify`` (LD_POOL_VERIFY=1): every buffer is overwritten with 0xFF bytes (NaN in every storage type)
         right behind the launch of its last declared use, so an undeclared later read shows in the samples."""
         import bisect
@@ -484,44 +517,39 @@ class _Plan:
                 for e in v.values():
                     yield from tensors(e, depth + 1)
 
-        def held(op):
-            """what a launch closure holds: default arguments and closure cells"""
-            for d in (getattr(op, "__defaults__", None) or ()):
-                yield d
-            for cell in (getattr(op, "__closure__", None) or ()):
-                try:
-                    yield cell.cell_contents
-                except ValueError:
-                    continue
-
-        # ---- the reflection scan: per launch, the tracked buffers it references in a PATCHABLE form
-        scanned, patches = [set() for _ in range(n_ops)], []
-        for i, op in enumerate(self.ops_main):
-            def hit(obj, name, k, delta, i=i):
-                scanned[i].add(k)
-                patches.append((obj, name, k, delta))
-            for v in held(op):
-                if hasattr(v, "_obj"):                       # C.byref(args) of a _call launch
-                    scan_struct(v._obj, hit)
-                for t in tensors(v):
-                    k = owner(t.data_ptr()) if t.is_cuda else None
-                    if k is not None:
-                        scanned[i].add(k)
-        # ---- the declarations, and their agreement with the scan
-        def declared_set(ts):
+        def holds(op, hit):
+            """the tracked buffers a record holds: tensors of its argument list (returned), pointer fields of its block (``hit``)"""
+            if isinstance(op.args, C.Structure):
+                scan_struct(op.args, hit)
+                return set()
             out = set()
-            for t in ts:
-                k = owner(t.data_ptr()) if (t is not None and t.is_cuda) else None
-                if k is not None:
-                    out.add(k)
-            return out
-        declared = [declared_set(self.decl.get(i, ((), ()))[0]) | declared_set(self.decl.get(i, ((), ()))[1]) for i in range(n_ops)]
-        op_names = [self.meta.get(i, {}).get("what", "?") for i in range(n_ops)]
+            for v, typ in zip(op.args, op.fn.argtypes):
+                if isinstance(v, torch.Tensor):
+                    out.add(owner(v.data_ptr()) if v.is_cuda else None)
+                elif typ is cabi.vp and isinstance(v, int) and owner(v) is not None:
+                    raise RuntimeError(f"pool: {op.what} passes an address inside pooled buffer {buf_names[owner(v)]} as a plain integer: "
+                                       "no patchable reference, it cannot be re-pointed at the pool")
+            return out - {None}
+
+        def owned(ts):
+            return {owner(t.data_ptr()) for t in ts if t.is_cuda} - {None}
+
+        # ---- per launch: the tracked buffers it holds (pointer fields are collected for patching), and those it declares
+        op_names = [op.what for op in self.ops_main]
         buf_names = [f"#{k} {tuple(t.shape)}" for k, t in enumerate(bufs)]
+        scanned, patches = [], []
+        for op in self.ops_main:
+            fields = set()
+
+            def hit(obj, name, k, delta, fields=fields):
+                fields.add(k)
+                patches.append((obj, name, k, delta))
+            scanned.append(holds(op, hit) | fields)
+        declared = [owned(op.reads) | owned(op.writes) for op in self.ops_main]
         check_declared(declared, scanned, op_names, buf_names)
-        live_out = declared_set(self.live_out)
+        live_out = owned(self.live_out)
         for name, v in self.__dict__.items():              # cross-check: a tracked buffer reachable from a plan attribute is read
-            if name in ("_track", "keep", "named", "decl", "live_out"):     # by something outside the launch list: it must be declared
+            if name in ("_track", "keep", "named", "live_out"):             # by something outside the launch list: it must be declared
                 continue
             for t in tensors(v):
                 k = owner(t.data_ptr()) if t.is_cuda else None
@@ -543,26 +571,12 @@ class _Plan:
             assert t.data_ptr() == base + offset[k]
             if last[k] < n_ops:
                 pooled.add(id(t))
-        # ---- after patching: NOTHING a launch holds may still point into an old allocation -- pointer fields, tensors, and plain
-        # integers (a data_ptr() taken at build time would have been missed by the scan above and is caught here)
-        def stale(v):
-            return isinstance(v, int) and not isinstance(v, bool) and owner(v) is not None
-        cur = [0]
-
-        def still(obj, name, k, delta):
-            raise RuntimeError(f"pool: launch {cur[0]} ({op_names[cur[0]]}) field {name} still points into the old allocation of {buf_names[k]}")
+        # ---- after patching: no pointer of any record may still lie in an old allocation
         for i, op in enumerate(self.ops_main):
-            cur[0] = i
-            for v in held(op):
-                if hasattr(v, "_obj"):
-                    scan_struct(v._obj, still)
-                vals = list(v) if isinstance(v, (tuple, list)) else (list(v.values()) if isinstance(v, dict) else [v])
-                for e in vals:
-                    if stale(e):
-                        raise RuntimeError(f"pool: launch {i} ({op_names[i]}) holds the old address of {buf_names[owner(e)]} as a plain integer")
-                for t in tensors(v):
-                    if t.is_cuda and owner(t.data_ptr()) is not None:
-                        raise RuntimeError(f"pool: launch {i} ({op_names[i]}) holds a tensor that was not re-pointed at the pool")
+            def still(obj, name, k, delta, i=i):
+                raise RuntimeError(f"pool: launch {i} ({op_names[i]}) field {name} still points into the old allocation of {buf_names[k]}")
+            if holds(op, still):
+                raise RuntimeError(f"pool: launch {i} ({op_names[i]}) holds a tensor that was not re-pointed at the pool")
         self.named = {k: v for k, v in self.named.items() if id(v) not in pooled}
         peak = peak_live(size, first, last)
         self.pool_stats = dict(buffers=len(bufs), bytes_unshared=sum(size), bytes_pool=top, bytes_peak_live=peak)
@@ -572,13 +586,8 @@ class _Plan:
             for k in range(len(bufs)):
                 if 0 <= last[k] < n_ops:
                     dying.setdefault(last[k], []).append((base + offset[k], size[k]))
-            lib = self.lib
             for i, regions in dying.items():
-                def poisoned(st, op=self.ops_main[i], regions=tuple(regions)):
-                    op(st)
-                    for ptr, nbytes in regions:
-                        cabi.check(lib.ld_memset_bytes(ptr, 0xFF, nbytes, st), "pool verify")
-                self.ops_main[i] = poisoned
+                self.ops_main[i].poison = tuple(regions)
             self.pool_stats["verify_poisoned_buffers"] = sum(len(r) for r in dying.values())
 
     def slot(self):
@@ -586,11 +595,6 @@ class _Plan:
         self._slot_cursor += 1
         assert s < self.stats.shape[0]
         return self.stats[s]
-
-    def t_ptr(self):
-        """The step-counter argument of the launches that apply FiLM: none -- in table mode the row of the current step is
-        at a fixed address (film_cur), with per-sample timesteps the rows are indexed by the batch element."""
-        return None
 
     def src(self, t, c, stride=0, ups=0, gn=None, act=cabi.ACT_NONE, film=None):
         s = cabi.Src()
@@ -611,20 +615,13 @@ class _Plan:
         return s
 
     def _call(self, ops, fn, args, what, meta=None, reads=(), writes=()):
-        """``reads`` / ``writes``: the tensors this launch reads and writes (the pool's liveness comes from these declarations;
-        the reflection scan of ``args`` cross-checks them and patches the pointers: _pool_buffers)."""
-        self.keep.append(args)
-        ref = C.byref(args)
-        ops.append(lambda st, fn=fn, ref=ref, what=what: cabi.check(fn(ref, st), what))
-        if ops is self.ops_main:
-            self.meta[len(ops) - 1] = dict(what=what, **(meta or {}))
-            self.decl[len(ops) - 1] = ([t for t in reads if t is not None], [t for t in writes if t is not None])
+        """A launch that takes ONE argument block.  ``reads`` / ``writes``: the tensors it reads and writes (the pool's liveness
+        comes from these declarations; the pointer fields of ``args`` cross-check them and are patched: _pool_buffers)."""
+        ops.append(_Launch(fn, args, what, meta, reads, writes))
 
-    def _raw(self, ops, fn, what, nbytes=0, flops=0, reads=(), writes=()):
-        ops.append(fn)
-        if ops is self.ops_main:
-            self.meta[len(ops) - 1] = dict(what=what, family=what, bytes=nbytes, flops=flops)
-            self.decl[len(ops) - 1] = ([t for t in reads if t is not None], [t for t in writes if t is not None])
+    def _raw(self, ops, fn, args, what, nbytes=0, flops=0, reads=(), writes=()):
+        """A launch that takes positional arguments (tensors for device pointers, None for null); its family is ``what``."""
+        ops.append(_Launch(fn, args, what, dict(family=what, bytes=nbytes, flops=flops), reads, writes))
 
     def conv3(self, ops, srcs, wname, cout, h, w, stats=None, groups=8, weight=None, bias=None, addend=None, side=None):
         """``side`` = (packed 1x1 weight, bias): the ResnetBlock's res_conv over the same input as a second output of the launch
@@ -649,38 +646,20 @@ class _Plan:
         if stats is not None:
             a.out_stats, a.out_groups = stats.data_ptr(), groups
         a.B, a.H, a.W, a.Cout = self.B, h, w, cout
-        a.t_ptr = self.t_ptr()
-        a.dtype = self.dt
+        a.dtype = self.dt          # (t_ptr stays null: the step's FiLM row is at a fixed address, per-sample rows go by batch element: src())
         cin = sum(s.C for s in srcs)
         npx = self.B * h * w
-        mt4 = cout % 64 == 0 and ((w + 15) // 16) * ((h + 7) // 8) * (cout // 64) * self.B >= 256
-        blocks16 = ((w + 15) // 16) * ((h + 15) // 16) * (cout // (64 if mt4 else 32)) * self.B
-        big = blocks16 >= 512 and h >= 16 and not mt4
-        big = big or (mt4 and h >= 16 and blocks16 >= self._kt("conv_big4_min"))    # mirrors conv3x3.hip:dispatch
-        dname = {cabi.LD_F32: "f32", cabi.LD_BF16: "bf16", cabi.LD_F16: "f16"}[self.dt]
-        if side is not None:
-            big = False                                # mirrors conv3x3.hip:dispatch (the side output rides on the 8-row tiles)
-        fam = f"conv3x3<{dname},{4 if mt4 else 2},{4 if big else 2}>"
-        ck = 16 if self.dt == cabi.LD_F32 else 32
-        if side is not None:
-            pass                                       # (only the generic kernel has the side output)
-        elif (cout == 32 and len(srcs) == 1 and cin == ck and addend is None and h >= 32 and w >= 32 and h % 16 == 0
-                and w % 16 == 0 and (w // 16) * (h // 16) * self.B >= self._kt("conv_c32_min_tiles")
-                and self._kt("conv_c32") and a.weight_terms != 2):
-            fam = f"conv3x3_c32<{dname}>"              # the persistent LDS-DMA kernel takes it (conv3x3_c32.hip)
-        elif (self.dt != cabi.LD_F32 and cout == 32 and addend is None and a.weight_terms != 2 and h % 16 == 0 and w % 16 == 0
-              and (w // 16) * (h // 16) * self.B >= self._kt("conv_s32_min_tiles") and not any(s.upsample for s in srcs)
-              and cin in (32, 64) and (len(srcs) == 1 or all(s.C == 32 for s in srcs)) and groups in (1, 2, 4, 8)):
-            pro = any(s.gn_stats for s in srcs)        # mirrors ld_conv3x3_s32_try (conv3x3_s32.hip)
-            bit = 2 if pro else (1 if cin == 32 else 4)
-            if (self._kt("conv_s32") & bit) and (not pro or (len(srcs) == 1 and srcs[0].C == 32 and srcs[0].gn_groups == 8)):
-                fam = f"conv3x3_s32<{dname}>"
+        # the kernel this launch runs on is the library's decision, under the routing table as it stands (the net's Tuning.kernel,
+        # applied by packed()): asked, never mirrored -- the family label is that word's spelling
+        route = int(self.lib.ld_conv3x3_route(C.byref(a)))
+        if route < 0:
+            cabi.check(route, "conv3x3 " + wname)
         in_el = sum(s.C * (npx // 4 if s.upsample else npx) for s in srcs)
         # (algorithmic bytes / flops, SURVEY 8d: with a side output the launch also carries res_conv's -- its input, read here once
         #  for both, counted for both as the reference's two modules would)
         side_b = (in_el + npx * cout + cin * cout) * self.esize + 4 * cout if side is not None else 0
         self._call(ops, self.lib.ld_conv3x3, a, "conv3x3 " + wname + (" + res_conv" if side is not None else ""),
-                   dict(family=fam, bytes=(in_el + npx * cout + 9 * cin * cout) * self.esize + 4 * cout + side_b,
+                   dict(family=conv3x3_family(route, self.dt), route=route, bytes=(in_el + npx * cout + 9 * cin * cout) * self.esize + 4 * cout + side_b,
                         flops=2 * (9 + (1 if side is not None else 0)) * cin * cout * npx, shape=f"{cin}->{cout}@{h}x{w}"),
                    reads=[s._tensor for s in srcs] + [addend], writes=[out, side_out])
         return out if side is None else (out, side_out)
@@ -719,7 +698,7 @@ class _Plan:
         g.final_act, g.pool = final_act, pool
         out = self.buf(h // 2 if pool else h, w // 2 if pool else w, c)
         g.out = out.data_ptr()
-        g.B, g.H, g.W, g.t_ptr, g.dtype = self.B, h, w, self.t_ptr(), self.dt
+        g.B, g.H, g.W, g.dtype = self.B, h, w, self.dt
         nel = self.B * h * w * c
         self._call(ops, self.lib.ld_gn_apply, g, "gn_apply",
                    dict(family="gn_apply", bytes=(nel * (2 if b_src is not None else 1) + nel // (4 if pool else 1)) * self.esize, flops=0),
@@ -737,16 +716,13 @@ class _Plan:
         freqs = self.P["freqs"]
         n, td = self.rows, cfg.time_dim
         if cfg.learned_sinusoidal_dim:            # RandomOrLearnedSinusoidalPosEmb (ddpm.py:151-165): [t, sin(2 pi w t), cos(2 pi w t)]
-            wts = f["time_mlp.0.weights"]
-            self.ops_time.append(lambda st: cabi.check(lib.ld_time_mlp_fourier(
-                times.data_ptr(), n, wts.data_ptr(), cfg.learned_sinusoidal_dim, f["time_mlp.1.weight"].data_ptr(),
-                f["time_mlp.1.bias"].data_ptr(), f["time_mlp.3.weight"].data_ptr(), f["time_mlp.3.bias"].data_ptr(),
-                td, self.temb.data_ptr(), st), "time_mlp (learned Fourier features)"))
+            self._raw(self.ops_time, lib.ld_time_mlp_fourier,
+                      [times, n, f["time_mlp.0.weights"], cfg.learned_sinusoidal_dim, f["time_mlp.1.weight"], f["time_mlp.1.bias"],
+                       f["time_mlp.3.weight"], f["time_mlp.3.bias"], td, self.temb], "time_mlp (learned Fourier features)")
         else:
-            self.ops_time.append(lambda st: cabi.check(lib.ld_time_mlp(
-                times.data_ptr(), n, freqs.data_ptr(), cfg.dim, f["time_mlp.1.weight"].data_ptr(),
-                f["time_mlp.1.bias"].data_ptr(), f["time_mlp.3.weight"].data_ptr(), f["time_mlp.3.bias"].data_ptr(),
-                td, self.temb.data_ptr(), st), "time_mlp"))
+            self._raw(self.ops_time, lib.ld_time_mlp,
+                      [times, n, freqs, cfg.dim, f["time_mlp.1.weight"], f["time_mlp.1.bias"], f["time_mlp.3.weight"],
+                       f["time_mlp.3.bias"], td, self.temb], "time_mlp")
         for name in f:
             if name.endswith(".mlp.1.weight") and not name.startswith("conv_fusion"):
                 p = name[:-len(".mlp.1.weight")]
@@ -755,9 +731,7 @@ class _Plan:
                 self.films[p] = film
                 self._film_off[id(film)] = self.film_row
                 self.film_row += two_c
-                w, b = f[name], f[p + ".mlp.1.bias"]
-                self.ops_time.append(lambda st, w=w, b=b, film=film, two_c=two_c: cabi.check(lib.ld_film(
-                    self.temb.data_ptr(), n, td, w.data_ptr(), b.data_ptr(), two_c, film.data_ptr(), st), "film"))
+                self._raw(self.ops_time, lib.ld_film, [self.temb, n, td, f[name], f[p + ".mlp.1.bias"], two_c, film], "film")
 
     # ------------------------------------------------------------------ blocks
     def resnet_block(self, ops, p, srcs_fn, cin_total, cout, h, w, res_tensor=None):
@@ -851,26 +825,18 @@ class _Plan:
         wfold = self._tracked(torch.empty(B, c * hid, dtype=self.tdt, device=self.dev))
         wout = f[p + ".to_out.0.weight"].reshape(c, hid).contiguous()
         wq, wkv = self.P["wq"][p], self.P["wkv"][p]
-        kshift = self.P["kshift"].get(p)
-        ksp = kshift.data_ptr() if kshift is not None else None
-        qshift = self.P["qshift"].get(p)
-        qsp = qshift.data_ptr() if qshift is not None else None
+        kshift, qshift = self.P["kshift"].get(p), self.P["qshift"].get(p)
         bias, g2 = f[p + ".to_out.0.bias"], self.P["g2"][p + ".to_out.1.g"]
         out = self.buf(h, w, c)
         self.keep += [ctx, wfold, wout, wq, wkv, kshift, qshift, bias, g2, out, x]
         npx = B * n
         terms = self.P.get("attn_terms", {}).get(p, 1)
-        self._raw(ops, lambda st: cabi.check(lib.ld_linattn_kvctx_terms(x.data_ptr(), wkv.data_ptr(), ksp, ctx.data_ptr(), B, n, c,
-                                                                        heads, 32, nchunks, dt, terms, st), "linattn_kvctx"),
+        self._raw(ops, lib.ld_linattn_kvctx_terms, [x, wkv, kshift, ctx, B, n, c, heads, 32, nchunks, dt, terms],
                   "linattn_kvctx", nbytes=npx * c * es, flops=2 * npx * c * 2 * hid * (1 if kshift is not None else 2) + 2 * npx * hid * 32,
                   reads=[x], writes=[ctx])
-        self._raw(ops, lambda st: cabi.check(lib.ld_linattn_ctxfold(ctx.data_ptr(), nchunks, wout.data_ptr(), wfold.data_ptr(), B, c,
-                                                                    heads, 32, 1, dt, st), "linattn_ctxfold"),
+        self._raw(ops, lib.ld_linattn_ctxfold, [ctx, nchunks, wout, wfold, B, c, heads, 32, 1, dt],
                   "linattn_ctxfold", nbytes=B * c * hid * es, flops=2 * B * c * hid * 32, reads=[ctx], writes=[wfold])
-        scale = cfg.attn_dim_head ** -0.5
-        self._raw(ops, lambda st: cabi.check(lib.ld_linattn_out_terms(x.data_ptr(), wq.data_ptr(), qsp, wfold.data_ptr(), bias.data_ptr(),
-                                                                      g2.data_ptr(), out.data_ptr(), B, n, c, scale, dt, terms, st),
-                                             "linattn_out"),
+        self._raw(ops, lib.ld_linattn_out_terms, [x, wq, qshift, wfold, bias, g2, out, B, n, c, cfg.attn_dim_head ** -0.5, dt, terms],
                   "linattn_out", nbytes=2 * npx * c * es, flops=2 * npx * hid * c * 2, reads=[x, wfold], writes=[out])
         return out
 
@@ -892,11 +858,9 @@ class _Plan:
         self.keep += [kmax, ctx, wfold, wout, qkv]
         dt, heads = self.dt, cfg.attn_heads
         es = self.esize
-        self._raw(ops, lambda st: cabi.check(lib.ld_linattn_ctx(qkv.data_ptr(), kmax.data_ptr(), ctx.data_ptr(),
-                                                                B, n, heads, 32, nchunks, dt, st), "linattn_ctx"),
+        self._raw(ops, lib.ld_linattn_ctx, [qkv, kmax, ctx, B, n, heads, 32, nchunks, dt],
                   "linattn_ctx", nbytes=2 * B * n * hid * es, flops=2 * B * n * hid * 32, reads=[qkv], writes=[ctx])
-        self._raw(ops, lambda st: cabi.check(lib.ld_linattn_ctxfold(ctx.data_ptr(), nchunks, wout.data_ptr(), wfold.data_ptr(),
-                                                                    B, c, heads, 32, 0, dt, st), "linattn_ctxfold"),
+        self._raw(ops, lib.ld_linattn_ctxfold, [ctx, nchunks, wout, wfold, B, c, heads, 32, 0, dt],
                   "linattn_ctxfold", nbytes=B * c * hid * es, flops=2 * B * c * hid * 32, reads=[ctx], writes=[wfold])
         q = self.src(qkv, hid, stride=3 * hid)
         return self.conv1(ops, [q], wfold, c, h, w, bias=f[p + ".to_out.0.bias"], epi=cabi.EPI_RMS_RES,
@@ -912,9 +876,7 @@ class _Plan:
         att = self.buf(h, w, hid)
         dt, heads = self.dt, cfg.attn_heads
         self.keep += [qkv, att]
-        self._raw(ops, lambda st: cabi.check(lib.ld_attention(qkv.data_ptr(), att.data_ptr(), B, n, heads, 32, dt, st),
-                                             "attention"),
-                  "attention", nbytes=4 * B * n * hid * self.esize, flops=4 * B * n * n * hid, reads=[qkv], writes=[att])
+        self._raw(ops, lib.ld_attention, [qkv, att, B, n, heads, 32, dt], "attention", nbytes=4 * B * n * hid * self.esize, flops=4 * B * n * n * hid, reads=[qkv], writes=[att])
         return self.conv1(ops, [self.src(att, hid)], self.P["w"][p + ".to_out.weight"], c, h, w,
                           bias=f[p + ".to_out.bias"], epi=cabi.EPI_RES, residual=x, what="full to_out " + p)
 
@@ -932,11 +894,8 @@ class _Plan:
         def image_conv(wname, c_out, stats):
             out = self.buf(h, w, c_out)
             wt, bs = f[wname + ".weight"], f[wname + ".bias"]
-            B, dt = self.B, self.dt
             self.keep += [out, wt, bs]
-            ops.append(lambda st: cabi.check(lib.ld_conv_image(
-                self.cond_in.data_ptr(), wt.data_ptr(), bs.data_ptr(), out.data_ptr(), stats.data_ptr(), G,
-                B, cin, h, w, 3, dt, st), "conv_image " + wname))
+            self._raw(ops, lib.ld_conv_image, [self.cond_in, wt, bs, out, stats, G, self.B, cin, h, w, 3, self.dt], "conv_image " + wname)
             return out
 
         if image:
@@ -969,26 +928,17 @@ class _Plan:
         H, W = self.H, self.W
         r = self.buf(H, W, cfg.init_dim)
         wi, bi = f["init_conv.weight"], f["init_conv.bias"]
-        if self.dt != cabi.LD_F32 and cfg.init_dim == 32:        # implicit GEMM on MFMA (hi/lo split: fp32-accurate)
-            wstem = self.P["stem"]
-            self.keep.append(wstem)
-
-            def stem_begin(st, delta, idx_ptr, t_table):        # init_conv + the head-of-step work in ONE launch (ld_conv_stem_begin)
-                za, ba, zb, bb = self._begin_args
-                rows, row_floats, cur = self._film_args
-                g = cabi.StepBeginArgs(za, ba, zb, bb, self._t_dev_ptr, int(delta), idx_ptr, t_table, rows, row_floats, cur)
-                cabi.check(lib.ld_conv_stem_begin(self.x_in.data_ptr(), wstem.data_ptr(), bi.data_ptr(), r.data_ptr(), B, cfg.channels,
-                                                  H, W, self.dt, C.byref(g), st), "init_conv + step_begin")
-            self._stem_begin = stem_begin
-            self._raw(ops, lambda st: cabi.check(lib.ld_conv_stem(
-                self.x_in.data_ptr(), wstem.data_ptr(), bi.data_ptr(), r.data_ptr(), B, cfg.channels, H, W, self.dt, st),
-                "init_conv"), "conv_image7x7",
-                nbytes=B * H * W * (4 * cfg.channels + self.esize * cfg.init_dim), flops=2 * 49 * cfg.channels * cfg.init_dim * B * H * W, writes=[r])
+        stem_cost = dict(nbytes=B * H * W * (4 * cfg.channels + self.esize * cfg.init_dim), flops=2 * 49 * cfg.channels * cfg.init_dim * B * H * W)
+        # 16-bit storage: implicit GEMM on MFMA (hi/lo split: fp32-accurate); run_main can issue launch 0 as ld_conv_stem_begin,
+        # which takes the same arguments plus the head-of-step block
+        self._mfma_stem = self.dt != cabi.LD_F32 and cfg.init_dim == 32
+        if self._mfma_stem:
+            self.keep.append(self.P["stem"])
+            self._raw(ops, lib.ld_conv_stem, [self.x_in, self.P["stem"], bi, r, B, cfg.channels, H, W, self.dt], "conv_image7x7",
+                      writes=[r], **stem_cost)
         else:
-            self._raw(ops, lambda st: cabi.check(lib.ld_conv_image(
-                self.x_in.data_ptr(), wi.data_ptr(), bi.data_ptr(), r.data_ptr(), None, 1, B, cfg.channels, H, W, 7,
-                self.dt, st), "init_conv"), "conv_image7x7",
-                nbytes=B * H * W * (4 * cfg.channels + self.esize * cfg.init_dim), flops=2 * 49 * cfg.channels * cfg.init_dim * B * H * W, writes=[r])
+            self._raw(ops, lib.ld_conv_image, [self.x_in, wi, bi, r, None, 1, B, cfg.channels, H, W, 7, self.dt], "conv_image7x7",
+                      writes=[r], **stem_cost)
         self.named["init_conv"] = r
         x, c, h, w = r, cfg.init_dim, H, W
         skips = []
@@ -1031,18 +981,13 @@ class _Plan:
                 x = self.conv3(ops, [self.src(x, c)], p + ".3", cin, h, w)
             self.named[p + ".3"] = x
             c = cin
-        if self.tn.recompute_stem and self._track is not None and self.dt != cabi.LD_F32 and cfg.init_dim == 32:
+        r_cat = r
+        if self.tn.recompute_stem and self._track is not None and self._mfma_stem:
             # the final block concatenates init_conv's output, which would otherwise stay live for the whole evaluation
             # (one of six 16 MB tensors at the peak of a 4-patch plan): evaluate init_conv again here instead
-            r2 = self.buf(H, W, cfg.init_dim)
-            wstem2 = self.P["stem"]
-            self._raw(ops, lambda st, r2=r2: cabi.check(lib.ld_conv_stem(
-                self.x_in.data_ptr(), wstem2.data_ptr(), bi.data_ptr(), r2.data_ptr(), B, cfg.channels, H, W, self.dt, st),
-                "init_conv (again)"), "conv_image7x7",
-                nbytes=B * H * W * (4 * cfg.channels + self.esize * cfg.init_dim), flops=2 * 49 * cfg.channels * cfg.init_dim * B * H * W, writes=[r2])
-            r_cat = r2                                   # (``r`` itself stays bound: the first launch's closures write it)
-        else:
-            r_cat = r
+            r_cat = self.buf(H, W, cfg.init_dim)
+            self._raw(ops, lib.ld_conv_stem, [self.x_in, self.P["stem"], bi, r_cat, B, cfg.channels, H, W, self.dt], "conv_image7x7",
+                      writes=[r_cat], **stem_cost)
         x = self.resnet_block(ops, "final_res_block", lambda x=x, c=c, r_cat=r_cat: [self.src(x, c), self.src(r_cat, cfg.init_dim)],
                               c + cfg.init_dim, cfg.dim, h, w)
         wf = f["final_conv.weight"].reshape(cfg.out_dim, cfg.dim).contiguous()
@@ -1050,10 +995,8 @@ class _Plan:
         self.keep += [wf, bf, x, r]
         self.final = (x, wf, bf)              # operands of the last op (diffusion.py fuses it with the sampler update)
         self.live_out.append(x)               # ... which reads x AFTER the launch list: declared live to the end of the evaluation
-        self._raw(ops, lambda st, x=x: cabi.check(lib.ld_final_conv(
-            x.data_ptr(), wf.data_ptr(), bf.data_ptr(), self.model_out.data_ptr(), B, H, W, cfg.dim, cfg.out_dim,
-            self.dt, st), "final_conv"), "final_conv",
-            nbytes=B * H * W * (self.esize * cfg.dim + 4 * cfg.out_dim), flops=2 * cfg.dim * cfg.out_dim * B * H * W, reads=[x])
+        self._raw(ops, lib.ld_final_conv, [x, wf, bf, self.model_out, B, H, W, cfg.dim, cfg.out_dim, self.dt], "final_conv",
+                  nbytes=B * H * W * (self.esize * cfg.dim + 4 * cfg.out_dim), flops=2 * cfg.dim * cfg.out_dim * B * H * W, reads=[x])
 
     def __del__(self):
         try:
@@ -1120,9 +1063,10 @@ class _Plan:
         self.lib.ld_range_push(b"step")            # roctx: host-side issue of one denoiser evaluation (or its capture)
         try:
             ops = self.ops_main[:-1] if skip_final else self.ops_main
-            stem_begin = getattr(self, "_stem_begin", None) if self.tn.fused_step_begin else None
-            if stem_begin is not None:             # 16-bit storage: the head-of-step work rides in init_conv's launch
-                stem_begin(st, 0 if idx_ptr is not None else int(step_delta), idx_ptr, t_table)
+            if self._mfma_stem and self.tn.fused_step_begin:   # 16-bit storage: the head-of-step work rides in init_conv's launch
+                g = cabi.StepBeginArgs(*self._begin_args, self._t_dev_ptr, 0 if idx_ptr is not None else int(step_delta), idx_ptr, t_table,
+                                       *self._film_args)
+                cabi.check(self.lib.ld_conv_stem_begin(*ops[0].bound, C.byref(g), st), "init_conv + step_begin")
                 ops = ops[1:]
             elif idx_ptr is not None:              # strided sampling: t_dev = t_table[++idx] (ld_step_begin)
                 cabi.check(self.lib.ld_step_begin_film(*self._begin_args, self._t_dev_ptr, 0, idx_ptr, t_table, *self._film_args, st),

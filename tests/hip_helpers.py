@@ -97,7 +97,14 @@ def conv3x3(srcs, wpacked, bias, B, H, W, cout, dtype, stats=None, groups=8, t_p
     if side is not None:
         side_out = nans(B, H, W, cout, dtype=TDT[dtype])
         a.side_weight, a.side_bias, a.side_out = side[0].data_ptr(), side[1].data_ptr(), side_out.data_ptr()
-    cabi.check(cabi.lib().ld_conv3x3(C.byref(a), st()), "conv3x3")
+    # the routing decision, asked before the launch, must be what the launch then reports (and refuse what the launch refuses)
+    lib = cabi.lib()
+    predicted = int(lib.ld_conv3x3_route(C.byref(a)))
+    rc = lib.ld_conv3x3(C.byref(a), st())
+    assert (predicted if predicted < 0 else 0) == rc, (predicted, rc)
+    cabi.check(rc, "conv3x3")
+    ran = int(lib.ld_last_route(cabi.ROUTE_CONV3X3))
+    assert ran == predicted, (hex(ran), hex(predicted))
     return out if side is None else (out, side_out)
 
 

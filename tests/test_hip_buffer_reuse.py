@@ -141,9 +141,9 @@ def test_pool_verify_64_patch_shape():
 
 
 def test_an_undeclared_pointer_fails_loudly(monkeypatch):
-    """A launch that touches a pooled buffer without declaring it (here: a raw launch closing over the first block's output)
-    must stop the plan build -- its liveness would be wrong and the buffer would be re-used while the launch still reads it.
-    And a declared buffer held only as a plain integer address cannot be re-pointed at the pool: also an error."""
+    """A launch that holds a pooled buffer without declaring it (here: a launch record with the first block's output in its
+    argument list) must stop the plan build -- its liveness would be wrong and the buffer would be re-used while the launch
+    still reads it.  And a declared buffer held only as a plain integer address cannot be re-pointed at the pool: also an error."""
     from localdiffusion_hallucination_amd import unet as unet_mod
     orig = unet_mod._Plan._build_main
 
@@ -152,10 +152,9 @@ def test_an_undeclared_pointer_fails_loudly(monkeypatch):
             orig(self)
             victim = self._track[3]
             if kind == "undeclared":
-                self._raw(self.ops_main, lambda st, victim=victim: None, "rogue launch")
+                self._raw(self.ops_main, self.lib.ld_memset_zero, [victim, 0], "rogue launch")
             else:
-                addr = victim.data_ptr()
-                self._raw(self.ops_main, lambda st, addr=addr: None, "integer launch", reads=[victim])
+                self._raw(self.ops_main, self.lib.ld_memset_zero, [victim.data_ptr(), 0], "integer launch", reads=[victim])
         return patched
     for kind, pat in (("undeclared", "rogue launch.*does not\\s+declare"), ("integer", "integer launch.*no patchable reference")):
         monkeypatch.setattr(unet_mod._Plan, "_build_main", make(kind))
